@@ -6,15 +6,24 @@ from "array of binary changes in HOST memory" to "patch IR + envelope in HOST me
 container parse + SHA-256 + column decode -> causal schedule -> op-set merge -> RGA order -> whole-document patch IR, D2H.
 `value` = ops / T_replay.
 
+A plain run sets up, pre-warms, runs the W warm-up steps, times the K steps and prints ONE compact JSON line with the contract keys
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, ...). Everything else
+this file measures or checks runs with --full only:
+
 stdout carries ONE compact JSON line (< 6 KB, strict JSON: compact_line) -- the contract keys, `t_device_ms`, the whole-path `roofline`
 (N_ops x A / T_device with A = E + R + P algorithmic bytes per op) with its dominant kernel as measured by a
 rocprofv3-traced child of this run, `cpu_baseline`, and one short row per sub-workload. The whole record -- live per-kernel table with PMC
 bytes, phase brackets, every sub-workload in full (c4_text_multi, c3_map_lww, c2_text_typing, the headline log shuffled / DEFLATEd / x4,
-c5_doc_mixed = Backend.load), sharding model, save / history / applyChanges / JS end-to-end timings -- goes to --detail
-(gpurun_out/bench_detail.json) and to stderr. Before anything is timed the engine's getPatch text of the workload is compared with
-the CPU oracle's on the same bytes (sha256; N = 1): a mismatch ends the run without a line.
+c5_doc_mixed = Backend.load), sharding model, save / history / applyChanges / JS end-to-end timings -- goes to the --detail file and
+to stderr. Before anything is timed the engine's getPatch text of the workload is compared with the CPU oracle's on the same bytes
+(sha256; N = 1): a mismatch ends the run without a line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4_text_single] [--scale 1.0] [--no-sublines]
+--dump-outputs DIR (either mode) writes what the last timed step returned to its caller -- the patch IR record tables and envelope of
+am355_fetch_ir and the arena they point into -- as DIR/<name>.npy in float64 (float32 for byte arrays), at most 64 MB in all (a fixed,
+seeded sample of the rows of the large arrays beyond that). The inputs are generated from fixed seeds: the same arguments give the
+same inputs, so two builds can be compared output for output.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4_text_single] [--scale 1.0] [--dump-outputs DIR] [--full [--no-sublines]]
 
 For N > 1 the driver launches this file under torch.distributed.run, one rank per GPU: every rank replays its own document of
 the same shape (different seed); value = total ops of all ranks / max time over ranks ("weak": one document needs one GPU for
@@ -24,6 +33,7 @@ objects it owns, the patch-IR fragments are all-gathered over RCCL and stitched 
 the single-GPU time of the same log measured in the same run.
 """
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -162,7 +172,7 @@ def live_kernel_table(timeout_s=170):
     # (the child's whole record goes to a file of its own: tools/kernel_table.py reads n_preds / n_list_elems from it, and the parent's
     # --detail file must not be overwritten by a child's)
     child_detail = os.path.join(tmp, "child_detail.json")
-    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--prewarm", "0.3", "--no-sublines", "--no-cpu-baseline",
+    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "3", "--prewarm", "0.3", "--no-sublines", "--no-cpu-baseline",
              "--detail", child_detail]
     t0 = time.perf_counter()
     try:
@@ -190,7 +200,7 @@ def live_kernel_table(timeout_s=170):
             child_rec = json.load(f)
         cmd = [sys.executable, os.path.join(ROOT, "tools", "kernel_table.py"), "--db", db, "--line", child_detail, "--replays", "13",
                "--out", os.path.join(tmp, "table.json"), "--source",
-               "measured in this run: rocprofv3 --kernel-trace --stats / --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --steps 10 --warmup 3 --no-sublines --no-cpu-baseline"]
+               "measured in this run: rocprofv3 --kernel-trace --stats / --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --full --steps 10 --warmup 3 --no-sublines --no-cpu-baseline"]
         if csvs.get("pf") and csvs.get("pw"):
             cmd += ["--fetch", csvs["pf"], "--write", csvs["pw"]]
         if subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=120).returncode != 0:
@@ -407,6 +417,87 @@ def timed(fn, steps, sync):
         fn()
     sync()
     return time.perf_counter() - t0
+
+
+class PatchIR(ctypes.Structure):
+    """am355_patch_ir (include/am355.h): the host-side result of am355_fetch_ir."""
+    _fields_ = [("n_objects", ctypes.c_uint32), ("n_map", ctypes.c_uint32), ("n_edits", ctypes.c_uint32), ("n_values", ctypes.c_uint32),
+                ("objects", ctypes.c_void_p), ("map", ctypes.c_void_p), ("edits", ctypes.c_void_p),
+                ("max_op", ctypes.c_uint64), ("n_actors", ctypes.c_uint32), ("actor_off", ctypes.c_void_p), ("actor_bytes", ctypes.c_void_p),
+                ("n_clock", ctypes.c_uint32), ("clock_actor", ctypes.c_void_p), ("clock_seq", ctypes.c_void_p),
+                ("n_heads", ctypes.c_uint32), ("heads", ctypes.c_void_p), ("pending", ctypes.c_uint32),
+                ("arena", ctypes.c_void_p), ("arena_len", ctypes.c_uint64)]
+
+
+DUMP_LIMIT = 64 << 20   # bytes of .npy data that --dump-outputs writes at most
+MAP_COUNTER = 1         # AM355_MAP_COUNTER: the map record's counter field is a counter total (else it carries nothing)
+EDIT_COUNTER = 32       # AM355_EDIT_COUNTER: the edit record's pad word is the high word of a counter total (else it carries nothing)
+
+
+def _host_array(ptr, dtype, count):
+    if not count:
+        return np.zeros(0, dtype=dtype)
+    return np.frombuffer((ctypes.c_uint8 * (count * np.dtype(dtype).itemsize)).from_address(ptr), dtype=dtype).copy()
+
+
+def patch_ir_arrays(eng):
+    """The patch IR + envelope of the last step as a caller receives them (am355_fetch_ir), as float arrays: the record tables row by row
+    (objects: id_ctr, id_actor, type, map_begin, map_end, edit_begin, edit_end; map: id_ctr, id_actor, key_off, key_len, val_tl, val_off,
+    flags, counter; edits incl. the sentinel: flags, index, id_ctr, id_actor, elem_ctr, elem_actor, first, val_tl, val_off, counter high
+    word), the envelope, and the arena the records point into. Engine-internal words (make_row, padding) are left out."""
+    ir = PatchIR()
+    eng._check(eng._L.am355_fetch_ir(eng._h, ctypes.byref(ir)))
+    objects = _host_array(ir.objects, np.uint32, 8 * ir.n_objects).reshape(-1, 8)[:, :7]
+    map_u32 = _host_array(ir.map, np.uint32, 10 * ir.n_map).reshape(-1, 10)
+    counter = map_u32[:, 8:10].copy().view(np.int64)[:, 0]
+    counter[(map_u32[:, 6] & MAP_COUNTER) == 0] = 0
+    edits = _host_array(ir.edits, np.uint32, 10 * (ir.n_edits + 1)).reshape(-1, 10)
+    edits[(edits[:, 0] & EDIT_COUNTER) == 0, 9] = 0
+    actor_off = _host_array(ir.actor_off, np.uint32, ir.n_actors + 1 if ir.n_actors else 0)
+    return {
+        "envelope": np.array([ir.n_objects, ir.n_map, ir.n_edits, ir.n_values, ir.max_op, ir.n_actors, ir.n_clock, ir.n_heads, ir.pending, ir.arena_len],
+                             dtype=np.float64),
+        "objects": objects.astype(np.float64),
+        "map": np.concatenate([map_u32[:, :7].astype(np.float64), counter[:, None].astype(np.float64)], axis=1),
+        "edits": edits.astype(np.float64),
+        "actor_off": actor_off.astype(np.float64),
+        "actor_bytes": _host_array(ir.actor_bytes, np.uint8, int(actor_off[-1]) if actor_off.size else 0).astype(np.float32),
+        "clock_actor": _host_array(ir.clock_actor, np.uint32, ir.n_clock).astype(np.float64),
+        "clock_seq": _host_array(ir.clock_seq, np.uint64, ir.n_clock).astype(np.float64),
+        "heads": _host_array(ir.heads, np.uint8, 32 * ir.n_heads).reshape(-1, 32).astype(np.float32),
+        "arena": _host_array(ir.arena, np.uint8, int(ir.arena_len)).astype(np.float32),
+    }
+
+
+def fit_dump(arrays, limit=DUMP_LIMIT, seed=0x5EED0D):
+    """At most `limit` bytes: arrays of up to 1 MB are kept whole; if the rest does not fit, each larger array is cut to the same fraction
+    of its rows, chosen by a fixed seed (sorted), and written as <name>_sample with the row numbers as <name>_sample_rows."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total <= limit:
+        return dict(arrays)
+    big = {k: a for k, a in arrays.items() if a.nbytes > (1 << 20)}
+    small = total - sum(a.nbytes for a in big.values())
+    per_row = sum(len(a) * (a.nbytes // max(len(a), 1) + 8) for a in big.values())
+    frac = (limit * 0.98 - small) / per_row
+    out = {}
+    for k, a in arrays.items():
+        if k not in big:
+            out[k] = a
+            continue
+        rows = np.sort(np.random.default_rng(seed).choice(len(a), max(1, int(len(a) * frac)), replace=False))
+        out[k + "_sample"] = a[rows]
+        out[k + "_sample_rows"] = rows.astype(np.float64)
+    return out
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what the last timed step computed, one DIR/<name>.npy per array."""
+    arrays = fit_dump(patch_ir_arrays(eng))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    print(f"outputs of the last timed step: {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values())} bytes -> {out_dir}", file=sys.stderr)
+    return arrays
 
 
 def algorithmic_bytes(st):
@@ -666,6 +757,9 @@ def parse_args(argv=None):
     ap.add_argument("--no-live-trace", action="store_true", help="do not run the rocprofv3-traced child that fills roofline.kernels (the committed table is embedded instead)")
     ap.add_argument("--no-shard", action="store_true", help="N > 1: skip the objectId-sharded measurement that follows the replica measurement")
     ap.add_argument("--subline-scale", type=float, default=1.0, help="scale of the sub-workloads (tests run the line builder at a small one)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the timed steps: parity gate, T_device, phases, roofline and kernel table, "
+                                                        "CPU baselines, sub-workloads, save / history / applyChanges, JS and sharded sections")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"), help="where the full record goes (the stdout line is the compact one)")
     return ap.parse_args(argv)
 
@@ -678,7 +772,8 @@ def run(args, eng, rank, world, dist, device, barrier, sync):
     w = Workload(eng, args.workload, args.scale, dist_util.rank_seed(BASE_SEED[args.workload], rank))
     # ---- the in-run parity gate (before any timing counts): the engine's getPatch text of the workload about to be
     # timed == the CPU oracle's on the same bytes (sha256 of the text). N = 1 only (the oracle leg runs on rank 0 at N = 1).
-    parity_in_run = "skipped (--no-cpu-baseline)" if args.no_cpu_baseline else "skipped (N > 1: the oracle leg runs at N = 1 only)" if world > 1 else None
+    parity_in_run = ("skipped (plain run: --full checks it)" if not args.full else "skipped (--no-cpu-baseline)" if args.no_cpu_baseline
+                     else "skipped (N > 1: the oracle leg runs at N = 1 only)" if world > 1 else None)
     if parity_in_run is None:
         w.step_replay()
         got = hashlib.sha256(eng.patch_json().encode()).hexdigest()
@@ -700,8 +795,21 @@ def run(args, eng, rank, world, dist, device, barrier, sync):
         w.step_replay()
     # ---- the timed region of `value`: K steps of T_replay (host buffers in -> patch IR in host memory) ----
     elapsed = timed(w.step_replay, args.steps, barrier)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
     st = eng.stats()
     elapsed, total_ops = dist_util.aggregate(elapsed, float(st.n_ops) * args.steps, dist, device)
+    out = {
+        "metric": "CRDT ops/sec applied (bulk replay)", "value": total_ops / elapsed, "unit": "ops/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u32", "data": "synthetic",
+        "config": {"workload": w.describe(st) + "; one document per GPU",
+                   "timed_region": "T_replay (SURVEY.md §8d): binary changes in host memory -> host inflate/staging -> H2D -> replay -> patch IR + envelope in host memory",
+                   "parity": PARITY, "parity_checked_in_run": parity_in_run, "fast_path": int(st.fast_path),
+                   "untimed_before_the_K_steps": f"{args.prewarm} s of steps + {args.warmup} warm-up steps"},
+    }
+    if not args.full:
+        return out if rank == 0 else None
     # ---- T_device (not `value`): the replay alone, inputs resident in HBM ----
     w.stage()
     for _ in range(3):
@@ -717,7 +825,6 @@ def run(args, eng, rank, world, dist, device, barrier, sync):
     if rank != 0:
         return None
     st = eng.stats()
-    value = total_ops / elapsed
     t_device_ms = t_dev / args.steps * 1e3
     n_preds = int(eng.rows()["pred_num"].sum())
     A = algorithmic_bytes(st)
@@ -757,17 +864,10 @@ def run(args, eng, rank, world, dist, device, barrier, sync):
         t0 = time.perf_counter()
         saved = eng.save()
         save_info = {"ms": (time.perf_counter() - t0) * 1e3, "doc_bytes": len(saved)}
-    out = {
-        "metric": "CRDT ops/sec applied (bulk replay)", "value": value, "unit": "ops/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u32", "data": "synthetic",
-        "config": {"workload": w.describe(st) + "; one document per GPU",
-                   "timed_region": "T_replay (SURVEY.md §8d): binary changes in host memory -> host inflate/staging -> H2D -> replay -> patch IR + envelope in host memory",
-                   "parity": PARITY, "parity_checked_in_run": parity_in_run, "fast_path": int(st.fast_path),
-                   "untimed_before_the_K_steps": f"{args.prewarm} s of steps + {args.warmup} warm-up steps"},
+    out.update({
         "t_device_ops_per_s": st.n_ops / (t_device_ms * 1e-3), "t_device_ms": t_device_ms,
         "phases_ms": phases, "algorithmic_bytes_per_op": A, "n_list_elems": int(st.n_list_elems), "save": save_info, "roofline": roofline,
-    }
+    })
     if sharded is not None:
         out["sharded"] = sharded
     if sharded_c5 is not None:
@@ -882,6 +982,9 @@ def compact_line(d):
     line["ms_per_step"] = _r(d["ms_per_step"], 5)
     line["config"] = {"workload": cfg["workload"][:300], "timed_region": cfg["timed_region"][:200], "parity": cfg["parity"][:200],
                       "parity_checked_in_run": cfg["parity_checked_in_run"], "fast_path": cfg["fast_path"]}
+    if "t_device_ms" not in d:   # (a plain run: the contract keys and the config are all it has)
+        line["detail"] = d.get("detail_file")
+        return line
     line["t_device_ms"] = _r(d["t_device_ms"], 5)
     line["algorithmic_bytes_per_op"] = {k: _r(v) for k, v in d["algorithmic_bytes_per_op"].items()}
     rf = d["roofline"]

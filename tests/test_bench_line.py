@@ -8,6 +8,7 @@ import json
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 import bench
@@ -31,7 +32,7 @@ def record(tmp_path_factory):
     subprocess.check_call(["make", "-s", "-C", EMU_DIR])
     eng = engine.Engine(0, EMU_LIB)
     path = str(tmp_path_factory.mktemp("bench") / "bench_detail.json")
-    args = bench.parse_args(["--steps", "2", "--warmup", "1", "--prewarm", "0", "--scale", "0.02", "--subline-scale", "0.004", "--no-live-trace", "--detail", path])
+    args = bench.parse_args(["--full", "--steps", "2", "--warmup", "1", "--prewarm", "0", "--scale", "0.02", "--subline-scale", "0.004", "--no-live-trace", "--detail", path])
     saved = bench.js_end_to_end, bench.reference_js_baseline, bench.sharded_js, bench.js_apply_latency
     bench.js_apply_latency = lambda log, calls=60: {"ms_per_call": 0.3, "first_call_ms": 1.5, "calls": 60, "ms": {}, "timed_region": "stub"}
     bench.sharded_js = lambda *a, **k: {"workload": "stub", "n_gpus": 1, "engine_ms_per_step": 1.0, "ops_per_s": 1.0e9, "per_rank_ms": [], "parity": "patch text sha256 == the unsharded engine's"}
@@ -96,9 +97,58 @@ def test_parity_gate_refuses_to_time_a_wrong_patch(monkeypatch):
     subprocess.check_call(["make", "-s", "-C", EMU_DIR])
     eng = engine.Engine(0, EMU_LIB)
     monkeypatch.setattr(bench, "oracle_patch_sha256", lambda log: "0" * 64)
-    args = bench.parse_args(["--steps", "1", "--warmup", "0", "--prewarm", "0", "--scale", "0.02", "--no-sublines", "--no-live-trace"])
+    args = bench.parse_args(["--full", "--steps", "1", "--warmup", "0", "--prewarm", "0", "--scale", "0.02", "--no-sublines", "--no-live-trace"])
     try:
         with pytest.raises(SystemExit, match="PARITY GATE FAILED"):
             bench.run(args, eng, 0, 1, None, None, lambda: None, lambda: None)
     finally:
         eng.close()
+
+
+def _plain_run(tmp_path, name, monkeypatch):
+    eng = engine.Engine(0, EMU_LIB)
+    args = bench.parse_args(["--steps", "3", "--warmup", "2", "--prewarm", "0", "--scale", "0.02", "--dump-outputs", str(tmp_path / name),
+                             "--detail", str(tmp_path / (name + ".json"))])
+    steps = []
+    step = bench.Workload.step_replay
+    monkeypatch.setattr(bench.Workload, "step_replay", lambda self: (steps.append(1), step(self)))
+    try:
+        detail = bench.run(args, eng, 0, 1, None, None, lambda: None, lambda: None)
+    finally:
+        eng.close()
+    return detail, len(steps)
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_ones_outputs(tmp_path, monkeypatch):
+    """Without --full the run is the warm-up and the K timed steps: no oracle, no T_device, no sub-workloads. --dump-outputs writes the
+    patch IR of the last timed step as float .npy files, the same for the same arguments."""
+    subprocess.check_call(["make", "-s", "-C", EMU_DIR])
+    for leg in ("oracle_patch_sha256", "measure_phases", "cpu_baseline", "subline", "apply_changes_section", "live_kernel_table"):
+        monkeypatch.setattr(bench, leg, lambda *a, leg=leg, **k: pytest.fail(leg + " ran in a plain run"))
+    detail, n_steps = _plain_run(tmp_path, "a", monkeypatch)
+    assert n_steps == 2 + 3
+    d = strict(bench.emit(detail, None))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["unit"] == "ops/s" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert not {"t_device_ms", "roofline", "cpu_baseline", "workloads"} & set(d)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert {"envelope.npy", "objects.npy", "map.npy", "edits.npy", "arena.npy"} <= set(files)
+    arrays = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= bench.DUMP_LIMIT
+    env = arrays["envelope.npy"]
+    assert arrays["edits.npy"].shape == (env[2] + 1, 10) and arrays["edits.npy"][-1, 6] == env[3]   # (sentinel: first == n_values)
+    assert arrays["arena.npy"].size == env[9] > 0
+    _plain_run(tmp_path, "b", monkeypatch)
+    assert sorted(os.listdir(tmp_path / "b")) == files
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), arrays[f]), f
+
+
+def test_dump_beyond_the_limit_is_a_fixed_sample():
+    arrays = {"big": np.arange(3_000_000, dtype=np.float32), "rows": np.ones((200_000, 10)), "small": np.zeros(10)}
+    a, b = bench.fit_dump(arrays, limit=8 << 20), bench.fit_dump(arrays, limit=8 << 20)
+    assert sum(x.nbytes for x in a.values()) <= 8 << 20 and set(a) == {"big_sample", "big_sample_rows", "rows_sample", "rows_sample_rows", "small"}
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.array_equal(a["big_sample"], a["big_sample_rows"].astype(np.float32)) and a["rows_sample"].shape[1] == 10

@@ -8,7 +8,7 @@ cp $L /tmp/lib_orig.so
 for r in $(seq $rounds); do for v in "$@"; do
   lib=${v%%:*}; envs=""; [ "$v" != "$lib" ] && envs=${v#*:}
   cp _ab/lib_$lib.so $L
-  env $envs timeout -k 5 100 python bench.py --steps 60 --warmup 10 --no-sublines --no-cpu-baseline --detail /tmp/ab.json $AB_ARGS > /dev/null 2>&1
+  env $envs timeout -k 5 100 python bench.py --full --steps 60 --warmup 10 --no-sublines --no-cpu-baseline --detail /tmp/ab.json $AB_ARGS > /dev/null 2>&1
   python - "$v" <<PY
 import json,sys
 p=json.loads(open("/tmp/ab.json").read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@
   python tools/kernel_table.py --db run_results.db --fetch F_counter_collection.csv --write W_counter_collection.csv \
          --line bench_line.json --replays 26 --out profiles/r02_kernel_table.json > profiles/r02_kernel_table.txt
 
-Inputs: the rocpd database of `rocprofv3 --kernel-trace --stats -- python bench.py --no-sublines --no-cpu-baseline` (kernel
+Inputs: the rocpd database of `rocprofv3 --kernel-trace --stats -- python bench.py --full --no-sublines --no-cpu-baseline` (kernel
 durations, launches), the two PMC passes of the same command (FETCH_SIZE / WRITE_SIZE per dispatch, KB), and that run's bench line
 (n_ops, encoded bytes, pred entries, patch-IR bytes, list elements). For every kernel: launches per replay, average duration,
 ALGORITHMIC bytes per launch (the formula is printed with it), HBM bytes from the counters (FETCH doubled for the wide streaming
