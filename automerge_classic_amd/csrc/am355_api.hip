@@ -9,15 +9,9 @@
 //   envelope                       backend/new.js:1870-1873, 2064-2067 (maxOp, clock, deps, pendingChanges)
 #include "am355_ctx.h"
 
-extern "C" am355_ctx* am355_create(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) return nullptr;
-  // every replay has a few host round trips of some microseconds each: wait for them actively (refused, harmlessly, when the
-  // host process has already initialised the device with other flags)
-  (void)hipSetDeviceFlags(hipDeviceScheduleSpin);
-  if (hipSetDevice(device) != hipSuccess) return nullptr;
-  am355_ctx* c = new am355_ctx();
-  c->device = device;
+// the context's host threads, streams, events and signal words; false: something could not be made (the caller deletes the context,
+// which destroys what was)
+static bool ctx_init(am355_ctx* c) {
   {
     unsigned hw = std::thread::hardware_concurrency();
     const char* env = getenv("AM355_HOST_THREADS");
@@ -28,7 +22,8 @@ extern "C" am355_ctx* am355_create(int device) {
   // ALU-dense SHA-256 waves slow the latency-bound parse/decode waves down
   int prio_low = 0, prio_high = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);
-  if (hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_high) != hipSuccess) { delete c; return nullptr; }
+  auto make_stream = [](Stream& s, int prio) { return hipStreamCreateWithPriority(&s.h, hipStreamNonBlocking, prio) == hipSuccess; };
+  if (!make_stream(c->stream, prio_high)) return false;
   {
     // The hash stream (one lane per change: ~65 waves of dependent SHA-256 rounds for 4 k changes) gets its own few compute
     // units when AM355_HASH_CUS=n asks for it (hipExtStreamCreateWithCUMask: its waves then never share a SIMD with the
@@ -38,61 +33,54 @@ extern "C" am355_ctx* am355_create(int device) {
     bool made = false;
     if (want > 0) {
       hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > want) {
+      if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > want) {
         int n_cu = prop.multiProcessorCount;
         std::vector<uint32_t> mask((size_t)(n_cu + 31) / 32, 0u);
         for (int k = 0; k < want; k++) { int cu = n_cu - 1 - k; mask[(size_t)cu / 32] |= 1u << (cu % 32); }
-        made = hipExtStreamCreateWithCUMask(&c->stream2, (uint32_t)mask.size(), mask.data()) == hipSuccess;
+        made = hipExtStreamCreateWithCUMask(&c->stream2.h, (uint32_t)mask.size(), mask.data()) == hipSuccess;
       }
     }
-    if (!made && hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_low) != hipSuccess) { delete c; return nullptr; }
+    if (!made && !make_stream(c->stream2, prio_low)) return false;
   }
-  if (hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, prio_high) != hipSuccess) { delete c; return nullptr; }
-  if (hipStreamCreateWithPriority(&c->stream4, hipStreamNonBlocking, prio_high) != hipSuccess) { delete c; return nullptr; }
-  if (hipEventCreate(&c->ev_fork) != hipSuccess || hipEventCreate(&c->ev_join) != hipSuccess) { delete c; return nullptr; }
-  for (auto& e : c->ev)
-    if (hipEventCreate(&e) != hipSuccess) { delete c; return nullptr; }
-  if (hipEventCreate(&c->ev_parse) != hipSuccess || hipEventCreate(&c->ev_b0) != hipSuccess || hipEventCreate(&c->ev_b1) != hipSuccess) { delete c; return nullptr; }
-  if (hipEventCreate(&c->ev_counts) != hipSuccess || hipEventCreate(&c->ev_runs) != hipSuccess || hipEventCreate(&c->ev_s1) != hipSuccess) { delete c; return nullptr; }
-  if (hipEventCreate(&c->ev_plan) != hipSuccess || hipEventCreate(&c->ev_tables) != hipSuccess || hipEventCreate(&c->ev_fills) != hipSuccess) { delete c; return nullptr; }
-  if (hipEventCreate(&c->ev_sched) != hipSuccess) { delete c; return nullptr; }
-  if (!c->h_sig.ensure(sizeof(HostSignals))) { delete c; return nullptr; }
+  if (!make_stream(c->stream3, prio_high) || !make_stream(c->stream4, prio_high)) return false;
+  for (Event* e : {&c->ev_fork, &c->ev_join, &c->ev[0], &c->ev[1], &c->ev[2], &c->ev[3], &c->ev[4], &c->ev[5], &c->ev[6], &c->ev[7], &c->ev_parse, &c->ev_b0, &c->ev_b1,
+                   &c->ev_counts, &c->ev_runs, &c->ev_s1, &c->ev_plan, &c->ev_tables, &c->ev_fills, &c->ev_sched})
+    if (hipEventCreate(&e->h) != hipSuccess) return false;
+  if (!c->h_sig.ensure(sizeof(HostSignals))) return false;
   memset(c->h_sig.p, 0, sizeof(HostSignals));
   if (const char* e = getenv("AM355_PHASE_EVENTS")) c->phase_events = strcmp(e, "0") != 0;
   if (const char* e = getenv("AM355_STAGE1_FILLS")) c->inline_fills = strcmp(e, "stream") != 0;
+  return true;
+}
+
+extern "C" am355_ctx* am355_create(int device) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) return nullptr;
+  // every replay has a few host round trips of some microseconds each: wait for them actively (refused, harmlessly, when the
+  // host process has already initialised the device with other flags)
+  (void)hipSetDeviceFlags(hipDeviceScheduleSpin);
+  if (hipSetDevice(device) != hipSuccess) return nullptr;
+  am355_ctx* c = new am355_ctx();
+  c->device = device;
+  if (!ctx_init(c)) { delete c; return nullptr; }
   return c;
 }
 
+// Everything that may still touch a member comes to rest first: the lane's job captures the context, the checksum thread reads
+// doc_bytes, the streams' commands read and write the buffers. (The host pool works inside calls only.) Nothing is running after
+// that, so the order in which the members then go -- the reverse of their declaration -- does not matter: buffers, streams and events
+// release themselves, the threads of `pool`, `lane` and `doc_sum` are idle and joined by their owners.
+am355_ctx::~am355_ctx() {
+  (void)hipSetDevice(device);   // (canary_forget asks for the current device; another context may have changed it)
+  if (lane) lane->wait();
+  (void)doc_sum.wait();
+  for (const Stream* s : {&stream, &stream2, &stream3, &stream4})
+    if (s->h) (void)hipStreamSynchronize(s->h);   // (null: am355_create failed before it was made)
+  if (shard_comm) (void)am355_shard_finalize(this);   // (ncclCommDestroy)
+}
+
 extern "C" void am355_destroy(am355_ctx* c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipStreamSynchronize(c->stream2);
-  (void)hipStreamSynchronize(c->stream3);
-  if (c->stream4) (void)hipStreamSynchronize(c->stream4);
-  for (DevBuf* b : {&c->d_entries, &c->d_amap_base, &c->d_amap_prov, &c->d_slots, &c->d_first_idx, &c->d_hashes, &c->d_hash_tab, &c->d_min_idx, &c->d_has_dep,
-                    &c->d_words, &c->d_slot_rank, &c->d_scan1, &c->d_plan_sums, &c->d_dep_idx, &c->d_self_idx, &c->d_rank_ids})
-    b->release();
-  for (HostBuf* b : {&c->h_slots, &c->h_hashes, &c->h_has_dep, &c->h_words, &c->h_stage, &c->h_s1, &c->h_dep_idx, &c->h_self_idx, &c->h_amap, &c->h_amap_base}) b->release();
-  c->d_s1.release();
-  for (hipEvent_t e : {c->ev_parse, c->ev_b0, c->ev_b1, c->ev_counts, c->ev_runs, c->ev_s1, c->ev_plan, c->ev_tables, c->ev_fills, c->ev_sched})
-    if (e) (void)hipEventDestroy(e);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  if (c->stream3) (void)hipStreamDestroy(c->stream3);
-  if (c->stream4) (void)hipStreamDestroy(c->stream4);
-  for (hipEvent_t e : {c->ev_fork, c->ev_join})
-    if (e) (void)hipEventDestroy(e);
-  if (c->shard_comm) (void)am355_shard_finalize(c);   // (ncclCommDestroy)
-  c->d_shard_send.release(); c->d_shard_recv.release(); c->d_shard_sizes.release(); c->h_shard_sizes.release(); c->h_shard_frags.release();
-  c->d_delta.release(); c->d_delta_edit.release(); c->d_sched.release(); c->h_sched.release(); c->d_hist.release(); c->d_pass.release(); c->d_breaks.release(); c->h_delta_tabs.release(); c->h_breaks_ahead.release(); c->h_delta.release(); c->d_sync.release();
-  for (DevBuf* b : {&c->d_arena, &c->d_offsets, &c->d_metas, &c->d_plans, &c->d_amap, &c->d_tables, &c->d_cols, &c->d_pred,
-                    &c->d_merge, &c->d_sort, &c->d_ir, &c->d_counts, &c->d_big, &c->d_bigvals, &c->d_ks, &c->d_save, &c->d_enc, &c->d_encout})
-    b->release();
-  for (HostBuf* b : {&c->h_metas, &c->h_offsets, &c->h_sig, &c->h_counts, &c->h_ir, &c->h_rows, &c->h_biginfo, &c->h_encout}) b->release();
-  for (auto& e : c->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;   // (of a null pointer: nothing)
 }
 
 extern "C" const char* am355_last_error(const am355_ctx* c) { return c ? c->err.c_str() : "no context (no GPU?)"; }
@@ -189,7 +177,6 @@ extern "C" int am355_test_sort(am355_ctx* c, uint64_t* keys, uint32_t* vals, uin
   (void)hipMemcpyAsync(vals, res ? vb.p : va.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st);
   HIPCHK(c, hipStreamSynchronize(st));
   HIPCHK(c, hipGetLastError());
-  ka.release(); kb.release(); va.release(); vb.release(); ws.release();
   return AM355_OK;
 }
 
@@ -204,7 +191,6 @@ extern "C" int am355_test_scan(am355_ctx* c, const uint32_t* in, uint32_t* out, 
   (void)hipMemcpyAsync(out, di.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st);
   (void)hipMemcpyAsync(total, dt.p, 4, hipMemcpyDeviceToHost, st);
   HIPCHK(c, hipStreamSynchronize(st));
-  di.release(); dt.release(); ws.release();
   return AM355_OK;
 }
 

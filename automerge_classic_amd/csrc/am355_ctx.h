@@ -42,82 +42,74 @@ using namespace am355;
 
 namespace am355_host {   // (host-side helpers of the C ABI's translation units)
 
-struct DevBuf {
+// A block of device or pinned host memory that frees itself. Mem: where it lives, and how much more than asked for ensure() takes.
+template <class Mem>
+struct Buf {
   void* p = nullptr;
   size_t cap = 0;
-  uint32_t lost = 0;   // times the CONTENT was given up (ensure that had to grow, release): what a kept state checks (am355_replay.hip resident_mark)
+  uint32_t lost = 0;   // times the CONTENT was given up (an ensure that had to grow): what a kept state checks (am355_replay.hip resident_mark)
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  ~Buf() { drop(); }
   bool ensure(size_t bytes) {
     if (bytes <= cap) return true;
     lost++;
-    canary_forget(p, cap);
-    // (a buffer that grows AGAIN belongs to a document that is growing call by call -- Backend.applyChanges in a loop --: half as much
-    // again, so that a reallocation, ~1 ms of hipFree + hipMalloc, comes once in dozens of calls instead of once in a few)
-    const size_t slack = cap ? bytes / 2 : bytes / 8;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = bytes + slack + 256 + (canary_on() ? (128u << 10) : 0u);
-    if (hipMalloc(&p, want) != hipSuccess) return false;
+    const size_t want = bytes + Mem::slack(bytes, cap) + 256;
+    drop();
+    if (Mem::alloc(&p, want) != hipSuccess) return false;
     cap = want;
     return true;
   }
-  // grows like ensure() but carries the first `keep` bytes over (device-to-device copy, synchronous)
+  // grows like ensure() but carries the first `keep` bytes over (synchronous)
   bool ensure_keep(size_t bytes, size_t keep) {
     if (bytes <= cap) return true;
     size_t want = bytes + bytes / 2 + 256;
     void* q = nullptr;
-    if (hipMalloc(&q, want) != hipSuccess) return false;
-    if (p && keep && hipMemcpy(q, p, keep, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipFree(q); return false; }
-    canary_forget(p, cap);
-    if (p) (void)hipFree(p);
+    if (Mem::alloc(&q, want) != hipSuccess) return false;
+    if (p && keep && !Mem::copy(q, p, keep)) { Mem::free(q, 0); return false; }
+    drop();
     p = q;
     cap = want;
     return true;
   }
-  void release() {
-    lost++;
-    canary_forget(p, cap);
-    if (p) (void)hipFree(p);
+  template <class T> T* as() { return (T*)p; }
+ private:
+  void drop() {
+    if (p) Mem::free(p, cap);
     p = nullptr;
     cap = 0;
   }
-  template <class T> T* as() { return (T*)p; }
 };
+struct DeviceMem {
+  static hipError_t alloc(void** p, size_t n) { return hipMalloc(p, n); }
+  static void free(void* p, size_t n) { canary_forget(p, n); (void)hipFree(p); }
+  static bool copy(void* dst, const void* src, size_t n) { return hipMemcpy(dst, src, n, hipMemcpyDeviceToDevice) == hipSuccess; }
+  // (a buffer that grows AGAIN belongs to a document that is growing call by call -- Backend.applyChanges in a loop --: half as much
+  // again, so that a reallocation, ~1 ms of hipFree + hipMalloc, comes once in dozens of calls instead of once in a few)
+  static size_t slack(size_t bytes, size_t cap) { return (cap ? bytes / 2 : bytes / 8) + (canary_on() ? (128u << 10) : 0u); }
+};
+struct PinnedMem {
+  static hipError_t alloc(void** p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
+  static void free(void* p, size_t) { (void)hipHostFree(p); }
+  static bool copy(void* dst, const void* src, size_t n) { memcpy(dst, src, n); return true; }
+  static size_t slack(size_t bytes, size_t) { return bytes / 8; }
+};
+using DevBuf = Buf<DeviceMem>;
+using HostBuf = Buf<PinnedMem>;
 
-struct HostBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  uint32_t lost = 0;   // as DevBuf::lost
-  // grows like ensure() but carries the first `keep` bytes over
-  bool ensure_keep(size_t bytes, size_t keep) {
-    if (bytes <= cap) return true;
-    size_t want = bytes + bytes / 2 + 256;
-    void* q = nullptr;
-    if (hipHostMalloc(&q, want, hipHostMallocDefault) != hipSuccess) return false;
-    if (p && keep) memcpy(q, p, keep);
-    if (p) (void)hipHostFree(p);
-    p = q;
-    cap = want;
-    return true;
-  }
-  bool ensure(size_t bytes) {
-    if (bytes <= cap) return true;
-    lost++;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = bytes + bytes / 8 + 256;
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) return false;
-    cap = want;
-    return true;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T> T* as() { return (T*)p; }
+// A stream / an event of the context: destroyed with its holder, handed to the runtime and to launches as the plain handle.
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+  H h = nullptr;
+  Handle() = default;
+  Handle(const Handle&) = delete;
+  Handle& operator=(const Handle&) = delete;
+  ~Handle() { if (h) (void)Destroy(h); }
+  operator H() const { return h; }
 };
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+using Event = Handle<hipEvent_t, hipEventDestroy>;
 
 // Byte vector in pinned host memory (the raw arena: the H2D copy of pageable memory is a synchronous bounce through the
 // driver's own staging buffer).
@@ -313,15 +305,16 @@ struct Hash32Hasher {
 using namespace am355_host;
 
 struct am355_ctx {
+  ~am355_ctx();  // am355_api.hip: quiesces, then the members release what they hold
   int device = 0;
-  hipStream_t stream = nullptr;   // decode / merge critical path
-  hipStream_t stream2 = nullptr;  // SHA-256 + dependency resolution, off the critical path
-  hipStream_t stream3 = nullptr;  // second decoder class, side by side with the first
-  hipStream_t stream4 = nullptr;  // small copies that must not queue behind kernels or fills (digests to the host, host-built tables to HBM)
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t ev[8] = {};
-  hipEvent_t ev_parse = nullptr, ev_b0 = nullptr, ev_b1 = nullptr;
-  hipEvent_t ev_counts = nullptr, ev_runs = nullptr;  // merge stage: counter read-backs that do not drain the stream
+  Stream stream;    // decode / merge critical path
+  Stream stream2;   // SHA-256 + dependency resolution, off the critical path
+  Stream stream3;   // second decoder class, side by side with the first
+  Stream stream4;   // small copies that must not queue behind kernels or fills (digests to the host, host-built tables to HBM)
+  Event ev_fork, ev_join;
+  Event ev[8];
+  Event ev_parse, ev_b0, ev_b1;
+  Event ev_counts, ev_runs;  // merge stage: counter read-backs that do not drain the stream
   std::string err;
   uint32_t flags = 0;
 
@@ -356,10 +349,10 @@ struct am355_ctx {
   bool offsets_on_device = false;      // d_offsets holds raw_off of every staged change (a batch staged behind a kept state defers the copy)
   HostBuf h_metas, h_offsets, h_sig;   // h_sig: HostSignals (device -> host result words without a copy)
   uint32_t sig_seq = 0;
-  hipEvent_t ev_s1 = nullptr;          // the per-change digests (briefs) have arrived on the host
-  hipEvent_t ev_fills = nullptr;       // merge fills done (when they run on stream4)
-  hipEvent_t ev_sched = nullptr;   // host copies of the device scheduler's order / pass numbers complete (stream4)
-  hipEvent_t ev_plan = nullptr, ev_tables = nullptr;  // k_plan_apply done (stream4 copies the digests behind it) | host-built tables in HBM
+  Event ev_s1;                         // the per-change digests (briefs) have arrived on the host
+  Event ev_fills;                      // merge fills done (when they run on stream4)
+  Event ev_sched;                  // host copies of the device scheduler's order / pass numbers complete (stream4)
+  Event ev_plan, ev_tables;        // k_plan_apply done (stream4 copies the digests behind it) | host-built tables in HBM
   void* counts_zeroed_at = nullptr; size_t counts_zeroed = 0;  // the counter block was cleared beside stage 1 (address, bytes)
   // AM355_PHASE_EVENTS=1: HIP events between the phases of a change replay (am355_stats.ms_parse / ms_decode / ms_merge / ms_order). Off by
   // default: every event record between two kernels of the main stream is a packet of its own in front of the next dispatch.

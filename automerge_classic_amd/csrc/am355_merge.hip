@@ -1548,36 +1548,39 @@ void merge_bind_counts(MergeBufs& b, void* block) {
   b.cs_erec.group_sum = g + 5 * groups;
 }
 
-void merge_prepare(MergeBufs& b, hipStream_t aux, int what, const FillRanges* extra) {
+bool merge_prepare(MergeBufs& b, hipStream_t aux, int what, const FillRanges* extra) {
   uint32_t N = b.n_ops;
   if (b.row_stride == 0 && b.first_row == 0) {
     (void)hipMemsetAsync(b.zero_base, 0, b.zero_bytes, aux);  // succ_cnt, inc_cnt, val_cnt, inc_sum, last_inc
     if (extra) launch_fill_ranges(*extra, aux);
-    if (!N) return;
+    if (!N) return true;
     (void)hipMemsetAsync(b.fill_base, 0xff, b.fill_bytes, aux);  // order, first_child, child_head
-    return;
+    return true;
   }
   // arrays carved for a capacity (am355_apply_changes: the rows stay where they are from call to call) are filled by their rows, in
   // one launch; the accumulators of kept rows [0, first_row) keep what the earlier rows left in them
   const size_t F = b.first_row, M = (size_t)N + 1 - F;
   FillRanges f;
+  bool fits = true;
   if (what & MERGE_FILL_ROWS) {
-    f.add(b.succ_cnt + F, 4 * M, 0);
-    f.add(b.inc_cnt + F, 4 * M, 0);
-    f.add(b.inc_sum + F, 8 * M, 0);
-    f.add(b.last_inc + F, 8 * M, 0);
+    fits &= f.add(b.succ_cnt + F, 4 * M, 0);
+    fits &= f.add(b.inc_cnt + F, 4 * M, 0);
+    fits &= f.add(b.inc_sum + F, 8 * M, 0);
+    fits &= f.add(b.last_inc + F, 8 * M, 0);
   }
   if (what & MERGE_FILL_TABLES) {
-    f.add(b.val_cnt, 4 * ((size_t)N + 1), 0);   // (recounted by k_emit over all rows)
+    fits &= f.add(b.val_cnt, 4 * ((size_t)N + 1), 0);   // (recounted by k_emit over all rows)
     if (N) {
-      f.add(b.order, 4 * ((size_t)N + 2), 0xffffffffu);
-      f.add(b.first_child, 4 * (2 * (size_t)N + 4), 0xffffffffu);
-      f.add(b.child_head, 4 * (2 * (size_t)N + 3), 0xffffffffu);
+      fits &= f.add(b.order, 4 * ((size_t)N + 2), 0xffffffffu);
+      fits &= f.add(b.first_child, 4 * (2 * (size_t)N + 4), 0xffffffffu);
+      fits &= f.add(b.child_head, 4 * (2 * (size_t)N + 3), 0xffffffffu);
     }
   }
   if (extra)   // (the caller's own clears ride in the same launch)
-    for (uint32_t k = 0; k < extra->n && f.n < 8; k++) { f.p[f.n] = extra->p[k]; f.n_words[f.n] = extra->n_words[k]; f.value[f.n] = extra->value[k]; f.n++; }
+    for (uint32_t k = 0; k < extra->n; k++) fits &= f.add(extra->p[k], 4 * (size_t)extra->n_words[k], extra->value[k]);
+  if (!fits) return false;
   launch_fill_ranges(f, aux);
+  return true;
 }
 
 // map emissions: LSD over (trigger id | key length | key chunks last..first | object)

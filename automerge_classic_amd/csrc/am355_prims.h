@@ -5,24 +5,35 @@
 #include <stddef.h>
 
 namespace am355 {
+// Ranges one launch of the two tables below takes (they are kernel arguments: the capacity is part of their layout).
+constexpr uint32_t LAUNCH_RANGES = 8;
 // Several word ranges filled with a value each in ONE launch (a memset per range costs a launch gap each). Ranges of <= 64 words
 // are written by one thread in the order given (they may overlap: a later range wins); longer ones must not overlap.
+// add(): false when the table is full (nothing is added).
 struct FillRanges {
-  uint32_t* p[8];
-  uint32_t n_words[8];
-  uint32_t value[8];
+  uint32_t* p[LAUNCH_RANGES];
+  uint32_t n_words[LAUNCH_RANGES];
+  uint32_t value[LAUNCH_RANGES];
   uint32_t n = 0;
-  void add(void* q, size_t bytes, uint32_t v) { p[n] = (uint32_t*)q; n_words[n] = (uint32_t)((bytes + 3) / 4); value[n] = v; n++; }
+  bool add(void* q, size_t bytes, uint32_t v) {
+    if (n == LAUNCH_RANGES) return false;
+    p[n] = (uint32_t*)q; n_words[n] = (uint32_t)((bytes + 3) / 4); value[n] = v; n++;
+    return true;
+  }
 };
 void launch_fill_ranges(const FillRanges& f, hipStream_t st);
 // Small host -> device copies as ONE launch: the kernel reads the (pinned, device-visible) sources over the link itself. A copy command
 // costs the host ~5-8 us whatever its size; a call of Backend.applyChanges with a one-change batch has five of a few hundred bytes each.
 struct CopyRanges {
-  void* dst[8];
-  const void* src[8];
-  uint32_t bytes[8];
+  void* dst[LAUNCH_RANGES];
+  const void* src[LAUNCH_RANGES];
+  uint32_t bytes[LAUNCH_RANGES];
   uint32_t n = 0;
-  void add(void* d, const void* s, size_t b) { dst[n] = d; src[n] = s; bytes[n] = (uint32_t)b; n++; }
+  bool add(void* d, const void* s, size_t b) {
+    if (n == LAUNCH_RANGES) return false;
+    dst[n] = d; src[n] = s; bytes[n] = (uint32_t)b; n++;
+    return true;
+  }
 };
 void launch_copy_ranges(const CopyRanges& r, hipStream_t st);
 // Result words of a phase into pinned host memory, then the sequence number (signal_host, am355_device.h), as a one-thread launch of its

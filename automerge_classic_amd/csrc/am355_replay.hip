@@ -676,7 +676,7 @@ static int run_device(am355_ctx* c, const std::vector<uint32_t>* slot_rank) {
   HIPCHK(c, hipMemsetAsync(c->d_counts.p, 0, c->mb.counts_bytes, st));
   HIPCHK(c, hipEventRecord(c->ev_fork, st));
   HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_fork, 0));
-  merge_prepare(c->mb, c->stream3);
+  if (!merge_prepare(c->mb, c->stream3)) return fail(c, AM355_E_DEVICE, "merge fills: more ranges than one launch takes");
   HIPCHK(c, hipEventRecord(c->ev[2], st));  // brackets the decode launch only
   launch_decode_columns(c->d_arena.as<uint8_t>(), c->d_metas.as<ChangeMeta>(), (const ChangePlan*)d_tables, n_small, n_large, (uint32_t)np - n_small - n_large, d_amap,
                         d_rank, c->cols, &c->d_counts.as<Counts>()->flags, st, c->stream3, c->shard_rank, c->shard_world);
@@ -686,7 +686,7 @@ static int run_device(am355_ctx* c, const std::vector<uint32_t>* slot_rank) {
 
   // ---- stage 2: merge (the decode flags land in the same counter block and are read with the first counters) ----
   Counts* hc = c->h_counts.as<Counts>();
-  merge_run(c->mb, c->ir, hc, st, (c->phase_events || !c->mb.sig) ? c->ev_counts : nullptr, c->ev_runs);
+  merge_run(c->mb, c->ir, hc, st, (c->phase_events || !c->mb.sig) ? c->ev_counts.h : nullptr, c->ev_runs);
   HIPCHK(c, hipEventRecord(c->ev[5], st));
   if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
   c->counts = *hc;
@@ -780,7 +780,7 @@ static int run_device_planned(am355_ctx* c, const PlanTotals& tot, uint32_t n_di
   // (stream3 carries the second decoder class -- 0.1-0.27 ms for a batch of fat changes --: the fills, which depend on nothing, would
   // start behind it and k_resolve would wait for them; they go to stream4 then)
   hipStream_t fill_stream = second_class ? c->stream4 : c->stream3;
-  merge_prepare(c->mb, fill_stream);
+  if (!merge_prepare(c->mb, fill_stream)) return fail(c, AM355_E_DEVICE, "merge fills: more ranges than one launch takes");
   if (second_class) {
     HIPCHK(c, hipEventRecord(c->ev_join, c->stream3));
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_join, 0));
@@ -808,7 +808,7 @@ static int run_device_planned(am355_ctx* c, const PlanTotals& tot, uint32_t n_di
   }
   lap("tables enqueued");
   Counts* hc = c->h_counts.as<Counts>();
-  merge_run(c->mb, c->ir, hc, st, (c->phase_events || !c->mb.sig) ? c->ev_counts : nullptr, c->ev_runs);
+  merge_run(c->mb, c->ir, hc, st, (c->phase_events || !c->mb.sig) ? c->ev_counts.h : nullptr, c->ev_runs);
   HIPCHK(c, hipEventRecord(c->ev[5], st));
   if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
   c->counts = *hc;
@@ -999,7 +999,9 @@ int backend_load_impl(am355_ctx* c, const uint8_t* doc, size_t len) {
 // the kept accumulators). A batch of plain list edits is then merged into the stored order (am355_resorder.hip); for any other the
 // whole-document order / patch tables are rebuilt by the kernels of merge_run as in a full replay. What a call no longer pays is
 // stage 1, the decode and the resolution of the old rows -- and, for list edits, the ordering of the old elements.
-// Returns AM355_OK, an error, or RESIDENT_FALLBACK: nothing of the state was touched, replay_impl goes on with the full replay.
+// Returns AM355_OK, an error, or RESIDENT_FALLBACK: replay_impl goes on with the full replay. The kept state may be dirty by then (a
+// batch that fails its hash / dependency checks has already been decoded into the kept arrays): the full replay carves and fills
+// them anew from the staged bytes.
 // ---------------------------------------------------------------------------------------------------------
 enum { RESIDENT_FALLBACK = 1 };
 
@@ -1367,7 +1369,7 @@ static int replay_resident(am355_ctx* c) {
     FillRanges extra;
     extra.add(c->d_counts.p, b.counts_bytes, 0);
     if (try_resorder) extra.add(ro.obj_add, (size_t)((uint8_t*)(ro.words + 8) - (uint8_t*)ro.obj_add), 0);   // obj_add | words (neighbours in the block, resorder_bind)
-    merge_prepare(b, st, MERGE_FILL_ROWS, &extra);   // (the new rows' accumulators; in this stream: the decode of a small batch is too short to hide a second stream's join)
+    if (!merge_prepare(b, st, MERGE_FILL_ROWS, &extra)) return fail(c, AM355_E_DEVICE, "merge fills: more ranges than one launch takes");   // (the new rows' accumulators; in this stream: the decode of a small batch is too short to hide a second stream's join)
   }
   // (launch_decode_columns puts a class on the second stream only when the small class and the lane-serial one are both there and no
   // large one: a handful of changes otherwise decode in ONE launch on `st`, and the fork / join would be four runtime calls for nothing)
@@ -1378,7 +1380,7 @@ static int replay_resident(am355_ctx* c) {
     HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_fork, 0));
   }
   launch_decode_columns(c->d_arena.as<uint8_t>(), c->d_metas.as<ChangeMeta>(), (const ChangePlan*)d_tables, n_small, n_large, n_serial,
-                        (const uint32_t*)(d_tables + o_x), nullptr, c->cols, &c->d_counts.as<Counts>()->flags, st, second_stream ? c->stream3 : nullptr, 0, 1);
+                        (const uint32_t*)(d_tables + o_x), nullptr, c->cols, &c->d_counts.as<Counts>()->flags, st, second_stream ? c->stream3.h : nullptr, 0, 1);
   if (second_stream) {
     HIPCHK(c, hipEventRecord(c->ev_join, c->stream3));
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_join, 0));
@@ -1467,7 +1469,7 @@ static int replay_resident(am355_ctx* c) {
     }
   }
   if (!merged_in_place && !maps_only) {
-    merge_prepare(b, st, MERGE_FILL_TABLES);
+    if (!merge_prepare(b, st, MERGE_FILL_TABLES)) return fail(c, AM355_E_DEVICE, "merge fills: more ranges than one launch takes");
     merge_run(b, c->ir, hc, st, nullptr, c->ev_runs, true);
     lap("merge_run done");
     if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
@@ -1502,7 +1504,7 @@ int ensure_ir_fresh(am355_ctx* c) {
   if (!c->d_counts.ensure(merge_counts_bytes(N))) return fail(c, AM355_E_NOMEM, "device allocation failed (merge)");
   merge_bind_counts(b, c->d_counts.p);
   HIPCHK(c, hipMemsetAsync(c->d_counts.p, 0, b.counts_bytes, st));
-  merge_prepare(b, st);
+  if (!merge_prepare(b, st)) return fail(c, AM355_E_DEVICE, "merge fills: more ranges than one launch takes");
   Counts* hc = c->h_counts.as<Counts>();
   merge_run(b, c->ir, hc, st, nullptr, c->ev_runs);
   if (hc->flags) { c->staged = c->replayed = false; return error_for_flags(c, hc->flags, "op set rejected"); }

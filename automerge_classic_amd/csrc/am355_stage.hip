@@ -39,8 +39,8 @@ int queue_upload(am355_ctx* c, void* dst, const void* src, size_t bytes) {
     HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
     return AM355_OK;
   }
-  if (c->pending_up.n == 8) { int rc = flush_uploads(c); if (rc) return rc; }
-  c->pending_up.add(dst, src, bytes);
+  if (c->pending_up.n == LAUNCH_RANGES) { int rc = flush_uploads(c); if (rc) return rc; }
+  if (!c->pending_up.add(dst, src, bytes)) return fail(c, AM355_E_DEVICE, "upload queue full");
   return AM355_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <ucontext.h>
 
 const char* emu_current_kernel = nullptr;
+std::atomic<long> emu_live[EMU_LIVE_KINDS];
 thread_local emu_uint3 threadIdx, blockIdx;
 thread_local dim3 blockDim, gridDim;
 
@@ -180,4 +181,9 @@ extern "C" long am355_emu_pinflate(const uint8_t* in, size_t in_len, uint8_t* ou
   if (v.size() > out_cap) return -1;
   if (!v.empty()) memcpy(out, v.data(), v.size());
   return (long)v.size();
+}
+
+// ---- test hook (tests/test_resource_accounting.py): live device allocations, pinned allocations, streams, events ----
+extern "C" void am355_emu_live(long out[4]) {
+  for (int k = 0; k < EMU_LIVE_KINDS; k++) out[k] = emu_live[k].load();
 }

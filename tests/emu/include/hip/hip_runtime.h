@@ -39,7 +39,24 @@ typedef int hipError_t;
 enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorNoDevice = 100, hipErrorNotReady = 600 };
 typedef struct emu_stream* hipStream_t;
 typedef struct emu_event* hipEvent_t;
+struct emu_stream { char unused; };
 struct emu_event { std::chrono::steady_clock::time_point t; };
+// Live resources, counted up where one is made and down where it is given back (am355_emu_live in emu_runtime.cpp;
+// tests/test_resource_accounting.py: a context that is destroyed leaves none behind).
+enum { EMU_LIVE_DEVICE, EMU_LIVE_PINNED, EMU_LIVE_STREAMS, EMU_LIVE_EVENTS, EMU_LIVE_KINDS };
+extern std::atomic<long> emu_live[EMU_LIVE_KINDS];
+inline hipError_t emu_alloc(int kind, void** p, size_t n) {
+  *p = malloc(n ? n : 1);
+  if (!*p) return 1;
+  emu_live[kind]++;
+  return 0;
+}
+inline hipError_t emu_free(int kind, void* p) {
+  if (p) emu_live[kind]--;
+  free(p);
+  return 0;
+}
+inline hipError_t emu_stream_create(hipStream_t* s) { *s = new emu_stream(); emu_live[EMU_LIVE_STREAMS]++; return 0; }
 enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice, hipMemcpyHostToHost, hipMemcpyDefault };
 
 inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "hipSuccess" : "emulated hip error"; }
@@ -47,31 +64,31 @@ inline hipError_t hipGetLastError() { return hipSuccess; }
 inline hipError_t hipSetDevice(int) { return hipSuccess; }
 inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
-inline hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorInvalidValue; }
-inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorInvalidValue; }
-inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+inline hipError_t hipMalloc(void** p, size_t n) { return emu_alloc(EMU_LIVE_DEVICE, p, n); }
+inline hipError_t hipFree(void* p) { return emu_free(EMU_LIVE_DEVICE, p); }
+inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { return emu_alloc(EMU_LIVE_PINNED, p, n); }
+inline hipError_t hipHostFree(void* p) { return emu_free(EMU_LIVE_PINNED, p); }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) { if (n) memcpy(d, s, n); return hipSuccess; }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memcpy(d, s, n); return hipSuccess; }
 inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t = nullptr) { if (n) memset(d, v, n); return hipSuccess; }
-inline hipError_t hipStreamCreate(hipStream_t* s) { *s = nullptr; return hipSuccess; }
-inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = nullptr; return hipSuccess; }
-inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
-inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = nullptr; return hipSuccess; }
+inline hipError_t hipStreamCreate(hipStream_t* s) { return emu_stream_create(s); }
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return emu_stream_create(s); }
+inline hipError_t hipStreamDestroy(hipStream_t s) { if (s) emu_live[EMU_LIVE_STREAMS]--; delete s; return hipSuccess; }
+inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { return emu_stream_create(s); }
 inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *hi = 0; return hipSuccess; }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 constexpr unsigned hipDeviceScheduleSpin = 1;
 inline hipError_t hipSetDeviceFlags(unsigned) { return hipSuccess; }
-inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new emu_event(); return hipSuccess; }
-inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new emu_event(); emu_live[EMU_LIVE_EVENTS]++; return hipSuccess; }
+inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) emu_live[EMU_LIVE_EVENTS]--; delete e; return hipSuccess; }
 inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t = nullptr) { e->t = std::chrono::steady_clock::now(); return hipSuccess; }
 inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 inline hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
 inline hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }
 struct hipDeviceProp_t { int multiProcessorCount = 1; };
 inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { *p = hipDeviceProp_t{}; return hipSuccess; }
-inline hipError_t hipExtStreamCreateWithCUMask(hipStream_t* s, uint32_t, const uint32_t*) { *s = nullptr; return hipSuccess; }
+inline hipError_t hipExtStreamCreateWithCUMask(hipStream_t* s, uint32_t, const uint32_t*) { return emu_stream_create(s); }
 inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned = 0) { return hipSuccess; }
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
   *ms = std::chrono::duration<float, std::milli>(b->t - a->t).count();
