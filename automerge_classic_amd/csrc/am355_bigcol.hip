@@ -192,7 +192,7 @@ void bigcol_index_tokens(const uint8_t* arena, const BigColDesc& d, BigColWork& 
   (void)hipMemsetAsync(w.info, 0, sizeof(BigColInfo), st);
   exclusive_scan_terminators(arena, L, w.term_ex, &w.info->n_tokens, w.scan_ws, st);  // (index of every number = terminators in front of it)
   AM355_LAUNCH_INDEPENDENT(kb_col_ranges, dim3(1), dim3(WAVE), st, d, (const uint32_t*)w.term_ex, w.info);
-  AM355_LAUNCH_INDEPENDENT(kb_token_ends, grid_for(L), dim3(BLOCK), st, arena, L, (const uint32_t*)w.term_ex, w.tok_end);
+  if (L) AM355_LAUNCH_INDEPENDENT(kb_token_ends, grid_for(L), dim3(BLOCK), st, arena, L, (const uint32_t*)w.term_ex, w.tok_end);   // (a document without ops has no bytes here: an empty grid is a refused launch)
 }
 
 // Step 2: records and row starts, over n_tokens numbers (read back by the caller).
@@ -786,7 +786,7 @@ void keystr_index_finish(KeyStage& s, bool unresolved, uint32_t** run_start, uin
   chain_mark(k.ja, L, k.mark_v, s.chain_ws, st);     // 3. literal items
   AM355_LAUNCH_INDEPENDENT(kk_item_flags, grid_for((cap + 3) / 4), dim3(BLOCK), st, L, k);
   exclusive_scan_u32(k.item_ex, k.item_ex, cap, k.n_runs, k.scan_ws, st);
-  AM355_LAUNCH_INDEPENDENT(kk_items, grid_for(L), dim3(BLOCK), st, s.col, s.col_abs, L, k, flags);
+  if (L) AM355_LAUNCH_INDEPENDENT(kk_items, grid_for(L), dim3(BLOCK), st, s.col, s.col_abs, L, k, flags);   // (an empty key column: no grid to launch)
   exclusive_scan_u32(k.rows, k.run_start, cap, nullptr, k.scan_ws, st);
   AM355_LAUNCH_INDEPENDENT(kk_run_pairs, grid_for(cap), dim3(BLOCK), st, s.arena, k, flags);
 }

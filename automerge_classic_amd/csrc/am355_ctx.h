@@ -538,7 +538,15 @@ static inline int fail(am355_ctx* c, int code, const char* fmt, ...) {
 template <class F>
 static inline int guarded(am355_ctx* c, F body) {
   try {
+    // A launch the runtime refuses (an empty grid, say) runs nothing and reports nothing: the error waits in the calling thread until
+    // somebody reads it -- in whichever call, of whichever context, next asks hipGetLastError. So: whatever the thread carries in is
+    // dropped here (it is not this call's), and what this call leaves behind fails THIS call.
+    (void)hipGetLastError();
     int rc = body();
+    if (rc == AM355_OK && c) {
+      const hipError_t left = hipGetLastError();
+      if (left != hipSuccess) return fail(c, AM355_E_DEVICE, "a HIP call of this API call failed unnoticed: %s", hipGetErrorString(left));
+    }
     if (canary_on() && c) {  // AM355_CANARY=1 (am355_canary.h): did a kernel of this call write past one of its arrays?
       char msg[320];
       if (!canary_check(msg, sizeof msg)) return fail(c, AM355_E_DEVICE, "%s", msg);

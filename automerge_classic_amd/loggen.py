@@ -22,7 +22,7 @@ class _Params(ctypes.Structure):
         ("kind", ctypes.c_uint32), ("n_actors", ctypes.c_uint32), ("n_rounds", ctypes.c_uint32),
         ("ins_per_change", ctypes.c_uint32), ("del_per_change", ctypes.c_uint32), ("n_objects", ctypes.c_uint32),
         ("n_keys", ctypes.c_uint32), ("ops_per_change", ctypes.c_uint32), ("n_ops", ctypes.c_uint64),
-        ("seed", ctypes.c_uint64), ("deflate", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("seed", ctypes.c_uint64), ("deflate", ctypes.c_uint32), ("runs_per_change", ctypes.c_uint32),
     ]
 
 
@@ -110,10 +110,12 @@ class ChangeLog:
 
 
 def generate(kind, *, n_actors=0, n_rounds=0, ins_per_change=0, del_per_change=0, n_objects=0, n_keys=0,
-             ops_per_change=0, n_ops=0, seed=0x5EED0000, deflate=False, name=""):
+             ops_per_change=0, n_ops=0, seed=0x5EED0000, deflate=False, name="", runs_per_change=0):
+    """`runs_per_change` (KIND_TEXT_CONCURRENT): r > 1 makes a change draw a new insertion position, among the elements visible before
+    the round, every ins_per_change // r insertions -- several runs per change; 0 (the default): one run, the logs as they always were."""
     lib = _load()
     p = _Params(kind, n_actors, n_rounds, ins_per_change, del_per_change, n_objects, n_keys, ops_per_change,
-                n_ops, seed, 1 if deflate else 0, 0)
+                n_ops, seed, 1 if deflate else 0, runs_per_change)
     log = _Log()
     rc = lib.amlog_generate(ctypes.byref(p), ctypes.byref(log))
     if rc != 0:

@@ -5,7 +5,8 @@
 //   kind 0  text_typing      one actor typing into one Text object (BASELINE config 2)
 //   kind 1  map_lww          many actors concurrently overwriting root-map keys in synced rounds (config 3)
 //   kind 2  text_concurrent  many actors inserting runs / deleting elements in Text objects in synced
-//                            rounds; n_objects = 1 (single object, config 4 headline) or >1 (shardable)
+//                            rounds; n_objects = 1 (single object, config 4 headline) or >1 (shardable);
+//                            runs_per_change > 1: several runs per change, each behind an element of its own
 // PRNG: splitmix64. C ABI so Python (ctypes) and the N-API addon can both call it.
 #include <array>
 #include "wire.hpp"
@@ -28,7 +29,7 @@ typedef struct {
   uint64_t n_ops;           // kind 0: number of character inserts
   uint64_t seed;
   uint32_t deflate;         // 1: DEFLATE changes >= 256 bytes like the reference encoder
-  uint32_t reserved;
+  uint32_t runs_per_change; // kind 2: r > 1 splits a change's insertions into r runs, each at a position of its own (0, 1: one run)
 } amlog_params;
 
 typedef struct {
@@ -172,6 +173,8 @@ void gen_text_concurrent(const amlog_params& p, Sink& sink, std::vector<Bytes>& 
   Rng rng(p.seed);
   uint32_t A = p.n_actors ? p.n_actors : 64, R = p.n_rounds ? p.n_rounds : 64;
   uint32_t n_ins = p.ins_per_change ? p.ins_per_change : 200, n_del = p.del_per_change, NO = p.n_objects ? p.n_objects : 1;
+  // (runs_per_change = 0 or 1 draws nothing more than before: the logs of the existing configurations keep their bytes)
+  const uint32_t run_len = p.runs_per_change > 1 ? std::max(1u, n_ins / p.runs_per_change) : 0;
   actors = make_actors(rng, A);
   // setup change by actor 0: one makeText per object at root keys "text" (single) or "t00".."tNN"
   Change setup;
@@ -199,6 +202,12 @@ void gen_text_concurrent(const amlog_params& p, Sink& sink, std::vector<Bytes>& 
       uint64_t pos = rng.below(vis.size() + 1);
       Id ref = pos == 0 ? Id{0, 0} : vis[pos - 1];
       for (uint32_t i = 0; i < n_ins; i++) {
+        if (run_len && i && i % run_len == 0) {
+          // the next run: a position of its own among the elements visible before the round (a batch of such changes has several
+          // new elements per change whose reference element is old)
+          pos = rng.below(vis.size() + 1);
+          ref = pos == 0 ? Id{0, 0} : vis[pos - 1];
+        }
         c.ops.push_back(insert_op(obj, ref, rand_char(rng)));
         ref = Id{ctr++, a};
         added[o].push_back(ref);

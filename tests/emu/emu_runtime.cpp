@@ -6,6 +6,9 @@
 
 const char* emu_current_kernel = nullptr;
 std::atomic<long> emu_live[EMU_LIVE_KINDS];
+thread_local hipError_t emu_last_error = hipSuccess;
+std::atomic<long> emu_refused_launches{0};
+const char* emu_refused_kernel = nullptr;
 thread_local emu_uint3 threadIdx, blockIdx;
 thread_local dim3 blockDim, gridDim;
 
@@ -184,6 +187,12 @@ extern "C" long am355_emu_pinflate(const uint8_t* in, size_t in_len, uint8_t* ou
 }
 
 // ---- test hook (tests/test_resource_accounting.py): live device allocations, pinned allocations, streams, events ----
+// Launches refused so far (an empty grid or block, a block of more than 1024 threads), and the kernel of the last one ("" if none).
+extern "C" long am355_emu_refused_launches(const char** last_kernel) {
+  if (last_kernel) *last_kernel = emu_refused_kernel ? emu_refused_kernel : "";
+  return emu_refused_launches.load();
+}
+
 extern "C" void am355_emu_live(long out[4]) {
   for (int k = 0; k < EMU_LIVE_KINDS; k++) out[k] = emu_live[k].load();
 }

@@ -36,7 +36,7 @@ struct dim3 {
 };
 
 typedef int hipError_t;
-enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorNoDevice = 100, hipErrorNotReady = 600 };
+enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorInvalidConfiguration = 9, hipErrorNoDevice = 100, hipErrorNotReady = 600 };
 typedef struct emu_stream* hipStream_t;
 typedef struct emu_event* hipEvent_t;
 struct emu_stream { char unused; };
@@ -59,8 +59,16 @@ inline hipError_t emu_free(int kind, void* p) {
 inline hipError_t emu_stream_create(hipStream_t* s) { *s = new emu_stream(); emu_live[EMU_LIVE_STREAMS]++; return 0; }
 enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice, hipMemcpyHostToHost, hipMemcpyDefault };
 
-inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "hipSuccess" : "emulated hip error"; }
-inline hipError_t hipGetLastError() { return hipSuccess; }
+inline const char* hipGetErrorString(hipError_t e) {
+  return e == hipSuccess ? "hipSuccess" : e == hipErrorInvalidConfiguration ? "invalid configuration argument" : "emulated hip error";
+}
+// A launch the HIP runtime refuses -- an empty grid or block, more than 1024 threads in a block -- runs nothing there and leaves
+// hipErrorInvalidConfiguration as the calling thread's last error until somebody reads it: in whichever call, of whichever context, that
+// happens to be. Here too; the refused launches are counted and the last one is named (am355_emu_refused_launches in emu_runtime.cpp).
+extern thread_local hipError_t emu_last_error;
+extern std::atomic<long> emu_refused_launches;
+extern const char* emu_refused_kernel;
+inline hipError_t hipGetLastError() { hipError_t e = emu_last_error; emu_last_error = hipSuccess; return e; }
 inline hipError_t hipSetDevice(int) { return hipSuccess; }
 inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
@@ -159,6 +167,15 @@ extern thread_local bool in_coop;
 // kernels (plus atomics), run as a plain loop on the calling thread (much faster under emulation).
 template <class K, class... A>
 inline void emu_launch(bool coop, K kernel, dim3 grid, dim3 block, A... args) {
+  const unsigned long long n_blocks = (unsigned long long)grid.x * grid.y * grid.z, n_threads = (unsigned long long)block.x * block.y * block.z;
+  if (n_blocks == 0 || n_threads == 0 || n_threads > 1024) {
+    emu_last_error = hipErrorInvalidConfiguration;
+    emu_refused_launches++;
+    emu_refused_kernel = emu_current_kernel;
+    fprintf(stderr, "emu: launch of %s refused: grid %u x %u x %u, block %u x %u x %u (invalid configuration argument)\n", emu_current_kernel ? emu_current_kernel : "?",
+            grid.x, grid.y, grid.z, block.x, block.y, block.z);
+    return;
+  }
   if (coop) {
     emu::rt().run(grid, block, [=]() { kernel(args...); });
   } else {
@@ -174,7 +191,7 @@ inline void emu_launch(bool coop, K kernel, dim3 grid, dim3 block, A... args) {
 }
 // The engine launches every kernel through one of these two macros (see am355_device.h).
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) emu_current_kernel = #kernel, emu_launch(true, kernel, dim3(grid), dim3(block), __VA_ARGS__)
-#define AM355_LAUNCH_INDEPENDENT(kernel, grid, block, stream, ...) emu_launch(false, kernel, dim3(grid), dim3(block), __VA_ARGS__)
+#define AM355_LAUNCH_INDEPENDENT(kernel, grid, block, stream, ...) emu_current_kernel = #kernel, emu_launch(false, kernel, dim3(grid), dim3(block), __VA_ARGS__)
 
 inline void emu_require_coop(const char* what) {
   if (!emu::in_coop) { fprintf(stderr, "emu: %s used in a kernel launched with AM355_LAUNCH_INDEPENDENT\n", what); abort(); }

@@ -212,7 +212,7 @@ def test_generated_logs_in_batches_match_the_oracle_emulated(emu_lib, kind, kw, 
         eng.close()
 
 
-def test_partition_variants_agree_emulated(emu_lib, monkeypatch):
+def check_partition_variants_agree(make_engine, monkeypatch):
     """The dominance counts of the list edits by their four versions -- all partition levels in LDS in a workgroup of 256 (<= 1024 items),
     pairs of 256-item tiles over the whole device (kd_dom_tiles / kd_dom_cross, <= 65536 items), all levels in LDS in a workgroup of 1024
     with the items held once (<= 11264 items, kd_partition_lds_big), three launches per level -- give the oracle's patches, on batches of a
@@ -228,7 +228,7 @@ def test_partition_variants_agree_emulated(emu_lib, monkeypatch):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        engs = [engine.Engine(0, emu_lib) for _ in range(3)]
+        engs = [make_engine() for _ in range(3)]
         try:
             check_against_oracle_session(engs[0], split_log(log, 2))
             check_against_oracle_session(engs[1], split_log(log, 16))
@@ -240,18 +240,26 @@ def test_partition_variants_agree_emulated(emu_lib, monkeypatch):
     assert texts[0] == texts[1] == texts[2] == texts[3] == texts[4]
 
 
-def test_batch_of_exactly_1024_edit_items_emulated(emu_lib):
+def test_partition_variants_agree_emulated(emu_lib, monkeypatch):
+    check_partition_variants_agree(lambda: engine.Engine(0, emu_lib), monkeypatch)
+
+
+def check_batch_of_exactly_1024_edit_items(make_engine):
     """A batch whose list edits are EXACTLY the 1024 items the single-workgroup partition holds (partition_lds_block, four items per thread
     of 256): the prefix entry behind the last item was nobody's to write, and the group's zero count came from stale LDS
     (tools/soak_resident.py, seed 7019: every edit of the batch at one index, in position order)."""
     log = loggen.generate(loggen.KIND_TEXT_TYPING, n_ops=1229, ops_per_change=41, seed=7019)
     arena, offs = bytes(log.arena), [int(x) for x in log.offsets]
     ch = [arena[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
-    eng = engine.Engine(0, emu_lib)
+    eng = make_engine()
     try:
         check_against_oracle_session(eng, [ch[:6], ch[6:31]])
     finally:
         eng.close()
+
+
+def test_batch_of_exactly_1024_edit_items_emulated(emu_lib):
+    check_batch_of_exactly_1024_edit_items(lambda: engine.Engine(0, emu_lib))
 
 
 def _one_by_one(log, head):
@@ -380,7 +388,7 @@ def test_resident_map_batches_leave_the_lists_alone_emulated(emu_lib, monkeypatc
             session.close()
 
 
-def test_resident_batches_that_fail_behind_the_device_work_emulated(emu_lib, monkeypatch):
+def check_resident_batches_that_fail_behind_the_device_work(make_engine, monkeypatch):
     """The batch's hashes, the duplicate check and the dependency check run on the host BEHIND the enqueue of its decode / resolution /
     list merge (replay_resident, hashes_and_dependencies): a batch that fails there has already changed the kept arrays, and the full
     replay that follows must start from the staged bytes. Text merged in place: a batch that repeats an applied change among new ones,
@@ -400,7 +408,7 @@ def test_resident_batches_that_fail_behind_the_device_work_emulated(emu_lib, mon
                [ch[18]], [ch[19]],
                [ch[20], ch[20], ch[21]],         # one change twice in a batch
                [ch[22]], [ch[23]]] + [[c] for c in ch[24:]]
-    eng = engine.Engine(0, emu_lib)
+    eng = make_engine()
     try:
         check_against_oracle_session(eng, batches)
         served, fell_back, in_place = eng.resident_counters()
@@ -409,7 +417,7 @@ def test_resident_batches_that_fail_behind_the_device_work_emulated(emu_lib, mon
         eng.close()
     # a wrong checksum in the middle of a batch
     bad = bytearray(ch[12]); bad[5] ^= 0x40
-    eng = engine.Engine(0, emu_lib)
+    eng = make_engine()
     session = oracle_lib.OracleSession()
     try:
         for batch in (ch[:10], [ch[10]], [ch[11]]):
@@ -434,8 +442,11 @@ def test_resident_batches_that_fail_behind_the_device_work_emulated(emu_lib, mon
         eng.close()
 
 
-@pytest.mark.parametrize("chunk", [0, 5])
-def test_resident_list_order_merged_in_place_emulated(emu_lib, monkeypatch, chunk):
+def test_resident_batches_that_fail_behind_the_device_work_emulated(emu_lib, monkeypatch):
+    check_resident_batches_that_fail_behind_the_device_work(lambda: engine.Engine(0, emu_lib), monkeypatch)
+
+
+def check_resident_list_order_merged_in_place(make_engine, monkeypatch, chunk):
     """(chunk = 5: AM355_RESORDER_CHUNK -- a batch is merged five rows at a time, each chunk against the order the chunks in front left,
     the order ping-ponging between its two arrays: what a batch of more than 4096 rows goes through.)
     am355_resorder.hip: the new elements of a small list-only batch are ranked against the STORED order (forward scan for the first
@@ -461,7 +472,7 @@ def test_resident_list_order_merged_in_place_emulated(emu_lib, monkeypatch, chun
             batches.append(ch[k:k + size])
             k += size
             size = size % 3 + 1
-        eng = engine.Engine(0, emu_lib)
+        eng = make_engine()
         session = oracle_lib.OracleSession()
         try:
             for i, batch in enumerate(batches):
@@ -472,7 +483,7 @@ def test_resident_list_order_merged_in_place_emulated(emu_lib, monkeypatch, chun
                     assert dict(_ordered(eng.patch_json()))["diffs"] == dict(_ordered(session.patch_json()))["diffs"], f"getPatch after batch {i}"
             assert dict(_ordered(eng.patch_json()))["diffs"] == dict(_ordered(session.patch_json()))["diffs"]
             doc = eng.save()
-            eng2 = engine.Engine(0, emu_lib)
+            eng2 = make_engine()
             eng2.load_changes(log)
             eng2.replay()
             assert bytes(doc) == bytes(eng2.save())    # Backend.save of the state the in-place merges built == of the bulk replay
@@ -483,7 +494,12 @@ def test_resident_list_order_merged_in_place_emulated(emu_lib, monkeypatch, chun
             eng.close()
 
 
-def test_resident_new_elements_of_two_objects_sharing_a_gap_emulated(emu_lib, monkeypatch):
+@pytest.mark.parametrize("chunk", [0, 5])
+def test_resident_list_order_merged_in_place_emulated(emu_lib, monkeypatch, chunk):
+    check_resident_list_order_merged_in_place(lambda: engine.Engine(0, emu_lib), monkeypatch, chunk)
+
+
+def check_resident_new_elements_of_two_objects_sharing_a_gap(make_engine, monkeypatch):
     """The end of one list object is the first position of the next: a batch that appends to the first and inserts at the head of the
     second has new elements with the SAME gap in two objects -- the object in front first, whatever the ids (found by
     tools/soak_resident.py, seed 2118: kr_order ranked them by id alone and the merged order interleaved the objects)."""
@@ -496,7 +512,7 @@ def test_resident_new_elements_of_two_objects_sharing_a_gap_emulated(emu_lib, mo
         batches.append(ch[k:k + size])
         k += size
     assert k >= len(ch)
-    eng = engine.Engine(0, emu_lib)
+    eng = make_engine()
     session = oracle_lib.OracleSession()
     try:
         for i, batch in enumerate(b for b in batches if b):
@@ -509,7 +525,11 @@ def test_resident_new_elements_of_two_objects_sharing_a_gap_emulated(emu_lib, mo
         eng.close()
 
 
-def test_batches_behind_the_staged_changes_or_restaged_emulated(emu_lib, monkeypatch):
+def test_resident_new_elements_of_two_objects_sharing_a_gap_emulated(emu_lib, monkeypatch):
+    check_resident_new_elements_of_two_objects_sharing_a_gap(lambda: engine.Engine(0, emu_lib), monkeypatch)
+
+
+def check_batches_behind_the_staged_changes_or_restaged(make_engine, monkeypatch):
     """A batch onto a state whose changes are all applied is staged behind them (only the batch is copied); AM355_APPLY_RESTAGE=1
     rebuilds the whole queue instead, as a call with queued changes does. Same patches either way, deflated batches included."""
     log = loggen.generate(loggen.KIND_TEXT_CONCURRENT, n_actors=5, n_rounds=4, ins_per_change=14, del_per_change=4, n_objects=2, seed=41)
@@ -520,13 +540,17 @@ def test_batches_behind_the_staged_changes_or_restaged_emulated(emu_lib, monkeyp
     for restage in (False, True):
         if restage:
             monkeypatch.setenv("AM355_APPLY_RESTAGE", "1")
-        eng = engine.Engine(0, emu_lib)
+        eng = make_engine()
         try:
             check_against_oracle_session(eng, batches)
             texts.append(eng.patch_json())
         finally:
             eng.close()
     assert texts[0] == texts[1]
+
+
+def test_batches_behind_the_staged_changes_or_restaged_emulated(emu_lib, monkeypatch):
+    check_batches_behind_the_staged_changes_or_restaged(lambda: engine.Engine(0, emu_lib), monkeypatch)
 
 
 def test_apply_after_load_changes_and_queue_emulated(emu_lib):
@@ -827,6 +851,43 @@ def test_resident_state_200_small_batches_gpu():
         assert served >= 195 and fell_back <= 2 and in_place >= 150, (served, fell_back, in_place)
     finally:
         eng.close()
+
+
+def _gpu_engine():
+    return engine.Engine(0)
+
+
+@pytest.mark.gpu
+def test_partition_variants_agree_gpu(monkeypatch):
+    """check_partition_variants_agree on the device, same switches (read per call): the only way kd_partition_lds_big -- 1024 threads,
+    11 items each -- and the level-by-level partitions of small batches run on hardware at all."""
+    check_partition_variants_agree(_gpu_engine, monkeypatch)
+
+
+@pytest.mark.gpu
+def test_batch_of_exactly_1024_edit_items_gpu():
+    check_batch_of_exactly_1024_edit_items(_gpu_engine)
+
+
+@pytest.mark.gpu
+def test_resident_batches_that_fail_behind_the_device_work_gpu(monkeypatch):
+    check_resident_batches_that_fail_behind_the_device_work(_gpu_engine, monkeypatch)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("chunk", [0, 5])
+def test_resident_list_order_merged_in_place_gpu(monkeypatch, chunk):
+    check_resident_list_order_merged_in_place(_gpu_engine, monkeypatch, chunk)
+
+
+@pytest.mark.gpu
+def test_resident_new_elements_of_two_objects_sharing_a_gap_gpu(monkeypatch):
+    check_resident_new_elements_of_two_objects_sharing_a_gap(_gpu_engine, monkeypatch)
+
+
+@pytest.mark.gpu
+def test_batches_behind_the_staged_changes_or_restaged_gpu(monkeypatch):
+    check_batches_behind_the_staged_changes_or_restaged(_gpu_engine, monkeypatch)
 
 
 @pytest.mark.gpu
