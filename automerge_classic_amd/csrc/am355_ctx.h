@@ -503,6 +503,10 @@ struct am355_ctx {
   uint32_t res_dep_base = 0;                       // changes >= this were applied by resident calls: their dependency indexes live in ...
   std::vector<uint32_t> res_dep_first, res_dep_index;   // ... CSR over (change - res_dep_base)
   uint64_t n_resident_calls = 0, n_resident_fallbacks = 0;
+  // am355_set_resident_new_actors: a batch whose authors the document does not know yet is served on the kept state -- the actors are
+  // inserted into the sorted table and the ranks the state holds are renumbered (am355_prims.h RemapRanges) -- instead of by the full replay
+  bool resident_new_actors = false;
+  uint64_t n_new_actor_calls = 0, n_rank_rewrites = 0;   // resident calls that inserted actors | those of them that launched the rank rewrite
   std::string resident_why;                        // why the last attempt fell back (diagnostics, AM355_TRACE)
 
   // objectId sharding (am355_set_shard): this context merges the objects rank `shard_rank` of `shard_world` owns

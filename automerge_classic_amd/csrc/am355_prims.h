@@ -36,6 +36,30 @@ struct CopyRanges {
   }
 };
 void launch_copy_ranges(const CopyRanges& r, hipStream_t st);
+// Actor ranks rewritten where they are stored, x = table[x] for every x < n_old, in ONE launch (replay_resident: actors inserted into the
+// sorted actor table renumber the ranks the kept state holds; a monotone renumbering, so no comparison between kept rows changes).
+// A range is `count` rank words `stride` words apart: 1 = a dense column (16-byte loads and stores between its 16-byte boundaries), more =
+// a field of a record table. guard != 0: the word `guard` words from the rank tells whether the rank means anything -- a record whose
+// guard word equals guard_skip stays as it is (the _root object's id, an accumulator nothing was written to). Values >= n_old (NONE32 for
+// _root, ...) stay bit-identical in every range. add(): false when the table is full (nothing is added).
+constexpr uint32_t REMAP_WG_ROWS = 1024;    // ranks of a dense column one workgroup rewrites per step of its grid-stride loop (4 per thread)
+constexpr uint32_t REMAP_LDS_RANKS = 4096;  // the table is staged in LDS up to this many old ranks (16 KB), read through L2 beyond
+struct RemapRanges {
+  uint32_t* p[LAUNCH_RANGES];
+  uint32_t count[LAUNCH_RANGES];
+  uint32_t stride[LAUNCH_RANGES];
+  int32_t guard[LAUNCH_RANGES];
+  uint32_t guard_skip[LAUNCH_RANGES];
+  uint32_t n = 0;
+  bool add(uint32_t* first_rank, size_t n_ranks, uint32_t stride_words = 1, int32_t guard_at = 0, uint32_t skip = 0) {
+    if (n == LAUNCH_RANGES || n_ranks > 0xffffffffu || !stride_words) return false;
+    if (!n_ranks) return true;
+    p[n] = first_rank; count[n] = (uint32_t)n_ranks; stride[n] = stride_words; guard[n] = guard_at; guard_skip[n] = skip; n++;
+    return true;
+  }
+};
+// d_table: [n_old] device words, table[old rank] = new rank
+void launch_remap_ranks(const RemapRanges& r, const uint32_t* d_table, uint32_t n_old, hipStream_t st);
 // Result words of a phase into pinned host memory, then the sequence number (signal_host, am355_device.h), as a one-thread launch of its
 // own behind the phase: for phases that end in a library scan or in one of several kernels. Two source ranges, a then b (n_b may be 0).
 void launch_signal_words(const uint32_t* src_a, uint32_t n_a, const uint32_t* src_b, uint32_t n_b, uint32_t* host_words, volatile uint32_t* host_seq, uint32_t seq,

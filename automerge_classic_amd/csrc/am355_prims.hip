@@ -982,6 +982,62 @@ void launch_signal_words(const uint32_t* src_a, uint32_t n_a, const uint32_t* sr
   hipLaunchKernelGGL(k_signal_words, dim3(1), dim3(WAVE), 0, st, src_a, n_a, src_b, n_b, host_words, host_seq, seq);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// actor ranks rewritten in place: x = table[x] for x < n_old (am355_prims.h RemapRanges). A pure bandwidth pass: grid-stride, a dense
+// column in 16-byte words between its 16-byte boundaries (written back only where a rank moved), the table in LDS when it fits.
+// ---------------------------------------------------------------------------------------------------------
+template <bool IN_LDS>
+__global__ __launch_bounds__(BLOCK) void k_remap_ranks(RemapRanges r, const uint32_t* __restrict__ table, uint32_t n_old) {
+  __shared__ uint32_t s_table[IN_LDS ? REMAP_LDS_RANKS : 1];
+  if (IN_LDS) {
+    for (uint32_t i = threadIdx.x; i < n_old; i += BLOCK) s_table[i] = table[i];
+    __syncthreads();
+  }
+  auto rank = [&](uint32_t x) -> uint32_t {
+    if (x >= n_old) return x;   // (NONE32 of _root and whatever else is no rank)
+    if (IN_LDS) return s_table[x];
+    return table[x];
+  };
+  const uint32_t tid = gtid(), stride = gridDim.x * BLOCK;
+  for (uint32_t k = 0; k < r.n; k++) {
+    uint32_t* p = r.p[k];
+    const uint32_t n = r.count[k], step = r.stride[k];
+    if (step == 1) {
+      uint32_t head = (uint32_t)((16u - ((uintptr_t)p & 15u)) & 15u) / 4u;  // words up to the first 16-byte boundary
+      if (head > n) head = n;
+      const uint32_t n4 = (n - head) / 4;
+      uint4* q = (uint4*)(p + head);
+      for (uint32_t i = tid; i < n4; i += stride) {
+        const uint4 v = q[i];
+        uint4 w;
+        w.x = rank(v.x); w.y = rank(v.y); w.z = rank(v.z); w.w = rank(v.w);
+        if (w.x != v.x || w.y != v.y || w.z != v.z || w.w != v.w) q[i] = w;
+      }
+      if (tid < head) p[tid] = rank(p[tid]);
+      const uint32_t tail = head + 4 * n4;
+      if (tid < n - tail) p[tail + tid] = rank(p[tail + tid]);
+    } else {
+      const int32_t guard = r.guard[k];
+      const uint32_t skip = r.guard_skip[k];
+      for (uint32_t i = tid; i < n; i += stride) {
+        uint32_t* e = p + (size_t)i * step;
+        if (guard && e[guard] == skip) continue;
+        const uint32_t x = *e, y = rank(x);
+        if (y != x) *e = y;
+      }
+    }
+  }
+}
+
+void launch_remap_ranks(const RemapRanges& r, const uint32_t* d_table, uint32_t n_old, hipStream_t st) {
+  size_t most = 0;
+  for (uint32_t k = 0; k < r.n; k++) most = std::max<size_t>(most, r.count[k]);
+  if (!most || !n_old) return;
+  const uint32_t grid = (uint32_t)std::min<size_t>((most + REMAP_WG_ROWS - 1) / REMAP_WG_ROWS, 2048);
+  if (n_old <= REMAP_LDS_RANKS) hipLaunchKernelGGL(k_remap_ranks<true>, dim3(grid), dim3(BLOCK), 0, st, r, d_table, n_old);
+  else AM355_LAUNCH_INDEPENDENT(k_remap_ranks<false>, dim3(grid), dim3(BLOCK), st, r, d_table, n_old);
+}
+
 void launch_fill_ranges(const FillRanges& f, hipStream_t st) {
   if (!f.n) return;
   size_t words = 0;

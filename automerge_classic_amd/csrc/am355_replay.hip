@@ -994,7 +994,8 @@ int backend_load_impl(am355_ctx* c, const uint8_t* doc, size_t len) {
 // exactly the applied changes in HBM (am355_ctx.h resident_valid), only the BATCH is parsed (host: the device's parser compiled for
 // the host, am355_decode.hip parse_changes_host -- a launch, a copy back and the wait for them cost ~25 us, the walk a microsecond),
 // hashed (host: SHA extensions, ~2 us per 3 KB change against ~130 us of chain latency on the device), scheduled (host: the
-// in-order case of new.js:1550-1597 -- every dependency applied, next sequence number, known actors; anything else falls back to
+// in-order case of new.js:1550-1597 -- every dependency applied, next sequence number, known actors, or new authors inserted into
+// the actor table when am355_set_resident_new_actors is on; anything else falls back to
 // the full replay, which has the general scheduler), decoded (the batch's plans) and resolved (k_resolve over the new rows, onto
 // the kept accumulators). A batch of plain list edits is then merged into the stored order (am355_resorder.hip); for any other the
 // whole-document order / patch tables are rebuilt by the kernels of merge_run as in a full replay. What a call no longer pays is
@@ -1130,8 +1131,65 @@ static int replay_resident(am355_ctx* c) {
     }
     return NONE32;
   };
-  std::vector<uint64_t> clock(NA, 0);
-  for (size_t k = 0; k < c->clock_actor.size(); k++) clock[c->clock_actor[k]] = c->clock_seq[k];
+  // ---- authors the document does not know yet (am355_set_resident_new_actors; without it they take the full replay below): ranked among
+  //      c->actors in the byte order the full replay ranks by (rank_device_actors), on copies -- c->actors and every host table that is
+  //      indexed by a rank or holds one follow with the commit, the ranks the device holds by launch_remap_ranks in front of the decode.
+  //      From here on every rank of the schedule is a rank AFTER the insertion. (What the reference does here: it appends the actor to
+  //      the document's table, new.js:1434-1451 -- its stored ops carry indexes in order of first appearance, not ranks.) ----
+  struct Newcomer { const uint8_t* id; uint32_t len, first_change, rank; };
+  std::vector<Newcomer> newcomers;       // the distinct new authors of the batch, sorted once ranked
+  std::vector<uint32_t> remap, old_of;   // old rank -> new rank | new rank -> old rank (NONE32: a newcomer)
+  if (c->resident_new_actors) {
+    const uint8_t* prev = nullptr;
+    uint32_t prev_len = 0;
+    for (uint32_t i = 0; i < nb; i++) {
+      const ChangeMeta& m = metas[i];
+      if (m.flags || (m.pad & 1)) break;   // (the schedule falls back at this change)
+      const uint8_t* a = raw + m.base + m.actor_off;
+      if (prev && prev_len == m.actor_len && memcmp(prev, a, m.actor_len) == 0) continue;
+      prev = a; prev_len = m.actor_len;
+      if (rank_of(a, m.actor_len) != NONE32) continue;
+      bool seen = false;
+      for (const Newcomer& w : newcomers) seen = seen || (w.len == m.actor_len && memcmp(w.id, a, m.actor_len) == 0);
+      if (!seen) newcomers.push_back(Newcomer{a, m.actor_len, i, 0});
+    }
+  }
+  const bool grow = !newcomers.empty();
+  const uint32_t NA2 = NA + (uint32_t)newcomers.size();   // actors once the batch is applied
+  if (grow) {
+    auto id_less = [](const uint8_t* x, size_t xl, const uint8_t* y, size_t yl) {
+      const size_t ml = std::min(xl, yl);
+      const int r = ml ? memcmp(x, y, ml) : 0;
+      return r ? r < 0 : xl < yl;
+    };
+    std::sort(newcomers.begin(), newcomers.end(), [&](const Newcomer& x, const Newcomer& y) { return id_less(x.id, x.len, y.id, y.len); });
+    remap.resize(NA);
+    old_of.reserve(NA2);
+    size_t w = 0;
+    for (uint32_t r = 0; r < NA; r++) {
+      const std::string& s = c->actors[r];
+      for (; w < newcomers.size() && id_less(newcomers[w].id, newcomers[w].len, (const uint8_t*)s.data(), s.size()); w++) {
+        newcomers[w].rank = (uint32_t)old_of.size();
+        old_of.push_back(NONE32);
+      }
+      remap[r] = (uint32_t)old_of.size();
+      old_of.push_back(r);
+    }
+    for (; w < newcomers.size(); w++) { newcomers[w].rank = (uint32_t)old_of.size(); old_of.push_back(NONE32); }
+  }
+  // (a monotone renumbering: some kept rank moved iff the last one did -- newcomers that all sort behind every kept actor move none)
+  const bool rank_moved = grow && NA && remap[NA - 1] != NA - 1;
+  // the rank an id has once the batch is applied; a newcomer counts from its first change on (a later change of the batch may name it
+  // among its other actors); NONE32: nobody in the document or so far in the batch authored a change under this id
+  auto rank_in_batch = [&](const uint8_t* a, size_t len, uint32_t change) -> uint32_t {
+    const uint32_t r = rank_of(a, len);
+    if (r != NONE32) return grow ? remap[r] : r;
+    for (const Newcomer& w : newcomers)
+      if (w.first_change <= change && w.len == len && memcmp(w.id, a, len) == 0) return w.rank;
+    return NONE32;
+  };
+  std::vector<uint64_t> clock(NA2, 0);
+  for (size_t k = 0; k < c->clock_actor.size(); k++) clock[grow ? remap[c->clock_actor[k]] : c->clock_actor[k]] = c->clock_seq[k];
   std::vector<uint32_t> new_clock_actors;
   // heads as a mark per change index: the document's heads now, minus what the batch depends on, plus the batch
   std::vector<uint8_t> is_head(n, 0);
@@ -1145,19 +1203,20 @@ static int replay_resident(am355_ctx* c) {
   std::vector<ChangePlan> plans;
   std::vector<uint32_t> amap, dep_first(1, 0), dep_index, op_base(nb);
   plans.reserve(nb); dep_first.reserve(nb + 1); dep_index.reserve(2 * (size_t)nb); amap.reserve(4 * (size_t)nb);
-  std::vector<std::vector<ActorSpan>> add_spans(NA);
+  std::vector<std::vector<ActorSpan>> add_spans(NA2);
   uint64_t ops = old_ops, preds = old_preds, max_op = c->max_op;
   for (uint32_t i = 0; i < nb; i++) {
     const ChangeMeta& m = metas[i];
     const uint32_t ci = K + i;
     if (m.flags || (m.pad & 1)) return fallback_dirty("a change the parser flags");
     const uint8_t* p = raw + m.base;
-    // actor table: author + the others, all known to the document (a new actor changes the ranks of the kept rows: full replay)
+    // actor table: author + the others, all known to the document (a new actor changes the ranks of the kept rows: full replay, unless
+    // the context inserts new authors -- `newcomers` above)
     // (a run of changes by one author -- a peer's backlog, a typing session -- looks its rank up once)
     uint32_t author;
     if (prev_author_bytes && prev_author_len == m.actor_len && memcmp(prev_author_bytes, p + m.actor_off, m.actor_len) == 0) author = prev_author;
     else {
-      author = rank_of(p + m.actor_off, m.actor_len);
+      author = rank_in_batch(p + m.actor_off, m.actor_len, i);
       if (author == NONE32) return fallback_dirty("new actor");
       prev_author_bytes = p + m.actor_off; prev_author_len = m.actor_len; prev_author = author;
     }
@@ -1166,7 +1225,8 @@ static int replay_resident(am355_ctx* c) {
     amap.push_back(author);
     {
       // the table of the other actors: the same bytes as in the author's last change -> the same ranks
-      am355_ctx::ActorMemo& memo = c->res_actor_memo[author];
+      // (the memo is indexed by the ranks of c->actors and holds such ranks: a batch that inserts actors goes without it, and the commit drops it)
+      am355_ctx::ActorMemo* memo = grow ? nullptr : &c->res_actor_memo[author];
       size_t off = m.others_off, end = off;
       for (uint32_t k = 0; k < m.n_other; k++) {
         // (actor ids are 16 bytes in practice: a one-byte length, no general LEB128 walk)
@@ -1176,8 +1236,8 @@ static int replay_resident(am355_ctx* c) {
         end += (size_t)l;
       }
       const size_t tlen = end - off;
-      if (memo.ranks.size() == m.n_other && memo.bytes.size() == tlen && (tlen == 0 || memcmp(memo.bytes.data(), p + off, tlen) == 0)) {
-        amap.insert(amap.end(), memo.ranks.begin(), memo.ranks.end());
+      if (memo && memo->ranks.size() == m.n_other && memo->bytes.size() == tlen && (tlen == 0 || memcmp(memo->bytes.data(), p + off, tlen) == 0)) {
+        amap.insert(amap.end(), memo->ranks.begin(), memo->ranks.end());
       } else {
         std::vector<uint32_t> ranks;
         ranks.reserve(m.n_other);
@@ -1185,14 +1245,16 @@ static int replay_resident(am355_ctx* c) {
         for (uint32_t k = 0; k < m.n_other; k++) {
           uint64_t l;
           (void)read_uleb_host(p, m.len, o, l);
-          const uint32_t rk = l <= m.len - o ? rank_of(p + o, (size_t)l) : NONE32;
+          const uint32_t rk = l <= m.len - o ? rank_in_batch(p + o, (size_t)l, i) : NONE32;
           if (rk == NONE32) return fallback_dirty("new actor");
           ranks.push_back(rk);
           o += (size_t)l;
         }
         amap.insert(amap.end(), ranks.begin(), ranks.end());
-        memo.bytes.assign(p + off, p + end);
-        memo.ranks.swap(ranks);
+        if (memo) {
+          memo->bytes.assign(p + off, p + end);
+          memo->ranks.swap(ranks);
+        }
       }
     }
     if (m.seq != clock[author] + 1) return fallback_dirty("sequence number");
@@ -1201,7 +1263,8 @@ static int replay_resident(am355_ctx* c) {
     op_base[i] = (uint32_t)ops;
     if (m.n_ops) {
       // the change's op ids lie behind every id of its author so far (ascending, disjoint spans: what plan_fast verifies)
-      const uint32_t a0 = c->actor_tab_off[author], a1 = c->actor_tab_off[author + 1];
+      const uint32_t kept = grow ? old_of[author] : author;   // (the context's span tables go by the ranks before the batch; a newcomer has no span yet)
+      const uint32_t a0 = kept == NONE32 ? 0 : c->actor_tab_off[kept], a1 = kept == NONE32 ? 0 : c->actor_tab_off[kept + 1];
       uint64_t last_end = a1 > a0 ? (uint64_t)c->spans[a1 - 1].start_op + c->spans[a1 - 1].n_ops : 0;
       if (!add_spans[author].empty()) last_end = (uint64_t)add_spans[author].back().start_op + add_spans[author].back().n_ops;
       if (m.start_op < last_end || m.start_op + m.n_ops > 0xfffffff0ull) return fallback_dirty("op id range");
@@ -1215,7 +1278,7 @@ static int replay_resident(am355_ctx* c) {
   }
   const uint32_t N = (uint32_t)ops, P = (uint32_t)preds;
   if (N > c->cols_cap_ops || P > c->cols_cap_preds || (size_t)N + 1 > c->mb.row_stride) return fallback_dirty("row capacity");
-  const int bits_ctr = bits_for64(max_op), bits_actor = bits_for64(NA ? NA - 1 : 0), bits_row = bits_for64(N);
+  const int bits_ctr = bits_for64(max_op), bits_actor = bits_for64(NA2 ? NA2 - 1 : 0), bits_row = bits_for64(N);
   if (1 + bits_row + bits_ctr + bits_actor > 64) return fallback_dirty("sort key width");
   lap("batch scheduled (host)");
 
@@ -1253,18 +1316,43 @@ static int replay_resident(am355_ctx* c) {
   };
   // the per-actor op-id spans with the batch's (what the device tables hold from this call on; the context's copy follows with the commit)
   std::vector<ActorSpan> spans_new;
-  std::vector<uint32_t> tab_new(NA + 1, 0);
+  std::vector<uint32_t> tab_new(NA2 + 1, 0);
   spans_new.reserve(c->spans.size() + plans.size());
-  for (uint32_t a = 0; a < NA; a++) {
+  for (uint32_t a = 0; a < NA2; a++) {
     tab_new[a] = (uint32_t)spans_new.size();
-    spans_new.insert(spans_new.end(), c->spans.begin() + c->actor_tab_off[a], c->spans.begin() + c->actor_tab_off[a + 1]);
+    const uint32_t kept = grow ? old_of[a] : a;   // (a newcomer: an empty slot, then its spans of the batch)
+    if (kept != NONE32) spans_new.insert(spans_new.end(), c->spans.begin() + c->actor_tab_off[kept], c->spans.begin() + c->actor_tab_off[kept + 1]);
     spans_new.insert(spans_new.end(), add_spans[a].begin(), add_spans[a].end());
   }
-  tab_new[NA] = (uint32_t)spans_new.size();
+  tab_new[NA2] = (uint32_t)spans_new.size();
+  std::vector<std::string> actors_new;
+  if (grow) {
+    actors_new.resize(NA2);
+    for (uint32_t r = 0; r < NA; r++) actors_new[remap[r]] = c->actors[r];
+    for (const Newcomer& w : newcomers) actors_new[w.rank].assign((const char*)w.id, w.len);
+  }
   std::vector<ChangePlan> plans_dev = plans;   // (in the decoder's class order below)
   // ---- commit the host state (once the batch has passed every check) ----
   auto commit_host_state = [&]() {
     c->hash_index_n = n;
+    if (grow) {
+      // every host table that is indexed by a rank or holds one: the actors, the clock's actors (below: the clock itself and the span
+      // tables, built by new rank above), the rank of a loaded document's actor indexes (read by am355_save / am355_doc_changes of a
+      // document context only, which never comes here: kept in step all the same), the id -> rank index and the per-author memo of
+      // this path (rebuilt by the next call). c->plans / c->amap are this batch's, by new rank; am355_save ranks and inverts per call.
+      c->actors.swap(actors_new);
+      for (uint32_t& a : c->clock_actor) a = remap[a];
+      if (c->doc_actor_rank.size() == NA)
+        for (uint32_t& r : c->doc_actor_rank) if (r < NA) r = remap[r];
+      c->res_rank_of.clear();
+      c->res_rank_n = 0;
+      c->res_actor_memo.clear();
+      if (rank_moved) {
+        // the host copies of the object and map tables hold the ranks from before: the in-place branch below must not take them for current
+        c->h_tables_current = c->h_tables_were_current = false;
+        c->ir_copy_enqueued = 0;
+      }
+    }
     for (uint32_t a : new_clock_actors) c->clock_actor.push_back(a);
     c->clock_seq.clear();
     for (uint32_t a : c->clock_actor) c->clock_seq.push_back(clock[a]);
@@ -1298,7 +1386,9 @@ static int replay_resident(am355_ctx* c) {
   const size_t np = plans.size();
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t b_plans = sizeof(ChangePlan) * np, b_spans = sizeof(ActorSpan) * spans_new.size(), b_tab = 4 * tab_new.size(), b_amap = 4 * amap.size();
-  const size_t o_spans = al(b_plans + 16), o_tab = o_spans + al(b_spans + 16), o_x = o_tab + al(b_tab + 16), tables_bytes = o_x + al(b_amap + 16);
+  const size_t b_remap = rank_moved ? 4 * (size_t)NA : 0;   // (old rank -> new rank, for launch_remap_ranks)
+  const size_t o_spans = al(b_plans + 16), o_tab = o_spans + al(b_spans + 16), o_x = o_tab + al(b_tab + 16), o_remap = o_x + al(b_amap + 16),
+               tables_bytes = o_remap + al(b_remap + 16);
   if (!c->d_tables.ensure(tables_bytes) || !c->h_stage.ensure(tables_bytes)) return fail(c, AM355_E_NOMEM, "device allocation failed");
   uint8_t* d_tables = c->d_tables.as<uint8_t>();
   c->p_spans = (ActorSpan*)(d_tables + o_spans);
@@ -1325,12 +1415,13 @@ static int replay_resident(am355_ctx* c) {
     if (b_spans) memcpy(h + o_spans, spans_new.data(), b_spans);
     memcpy(h + o_tab, tab_new.data(), b_tab);
     if (b_amap) memcpy(h + o_x, amap.data(), b_amap);
-    { int qrc = queue_upload(c, d_tables, h, o_x + b_amap); if (qrc) return qrc; }
+    if (b_remap) memcpy(h + o_remap, remap.data(), b_remap);
+    { int qrc = queue_upload(c, d_tables, h, b_remap ? o_remap + b_remap : o_x + b_amap); if (qrc) return qrc; }
   }
   MergeBufs& b = c->mb;
   b.arena = c->d_arena.as<uint8_t>();
   b.ops = c->cols;
-  b.n_ops = N; b.n_preds = P; b.n_actors = NA;
+  b.n_ops = N; b.n_preds = P; b.n_actors = NA2;
   b.sig = c->h_sig.as<HostSignals>(); b.sig_seq = c->sig_seq;
   b.actor_tab_off = c->p_tab_off; b.spans = c->p_spans;
   b.bits_ctr = (uint32_t)bits_ctr; b.bits_actor = (uint32_t)bits_actor;
@@ -1365,6 +1456,22 @@ static int replay_resident(am355_ctx* c) {
   }
   c->resident_valid = false;   // (from here on the kept arrays change: a failure leaves no state behind)
   { int frc = flush_uploads(c); if (frc) return frc; }   // (the batch's bytes, its records, the tables, the delta stage's breaks: one launch; its hashes follow)
+  if (rank_moved) {
+    // the ranks the kept state holds, renumbered in front of the batch's decode (whose rows come with ranks after the insertion): the
+    // actor columns of the kept rows and preds; the op id a counter's last increment left (last_inc: counter << 32 | rank, 0 where no
+    // increment came); the op ids in the object table (not _root's, which means nothing) and in the map records -- a batch merged in
+    // place keeps both tables. The edit table needs nothing: it is either rebuilt by this call (merge_run) or stale from here on
+    // (c->ir_stale: ensure_ir_fresh rebuilds it from the rows before anybody reads it). A batch that fails behind this (hashes,
+    // dependencies) takes the full replay, which ranks the actors and fills every one of these arrays anew from the staged bytes.
+    RemapRanges rr;
+    bool fits = rr.add(c->cols.obj_actor, old_ops) && rr.add(c->cols.key_actor, old_ops) && rr.add(c->cols.id_actor, old_ops) && rr.add(c->cols.pred_actor, old_preds);
+    fits = fits && rr.add((uint32_t*)b.last_inc, old_ops, 2, 1, 0);
+    fits = fits && rr.add(&c->ir.obj->id_actor, c->counts.n_objects, (uint32_t)(sizeof(am355_ir_object) / 4),
+                          (int32_t)(offsetof(am355_ir_object, make_row) / 4) - (int32_t)(offsetof(am355_ir_object, id_actor) / 4), NONE32);
+    fits = fits && rr.add(&c->ir.map->id_actor, c->counts.n_map_emit, (uint32_t)(sizeof(am355_ir_map) / 4));
+    if (!fits) return fail(c, AM355_E_DEVICE, "rank rewrite: more ranges than one launch takes");
+    launch_remap_ranks(rr, (const uint32_t*)(d_tables + o_remap), NA, st);
+  }
   {
     FillRanges extra;
     extra.add(c->d_counts.p, b.counts_bytes, 0);
@@ -1479,6 +1586,10 @@ static int replay_resident(am355_ctx* c) {
     c->ir_stale = false;
   }
   c->n_resident_calls++;
+  if (grow) {
+    c->n_new_actor_calls++;
+    if (rank_moved) c->n_rank_rewrites++;
+  }
   return AM355_OK;
 }
 

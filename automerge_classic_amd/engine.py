@@ -100,6 +100,11 @@ def _bind(path):
     if hasattr(L, "am355_resident_maps_only_calls"):
         L.am355_resident_maps_only_calls.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
         L.am355_resident_maps_only_calls.restype = ctypes.c_int
+    if hasattr(L, "am355_set_resident_new_actors"):
+        L.am355_set_resident_new_actors.argtypes = [vp, ctypes.c_int]
+        L.am355_set_resident_new_actors.restype = ctypes.c_int
+        L.am355_resident_new_actor_calls.argtypes = [vp, vp]
+        L.am355_resident_new_actor_calls.restype = ctypes.c_int
     L.am355_get_raw.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32)]
     L.am355_doc_changes.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_void_p)]
     L.am355_apply_changes.argtypes = [vp, vp, u64p, u32]
@@ -345,6 +350,17 @@ class Engine:
         out = ctypes.c_uint64()
         self._check(self._L.am355_resident_maps_only_calls(self._h, ctypes.byref(out)))
         return int(out.value)
+
+    def set_resident_new_actors(self, on):
+        """on: a batch whose authors the document does not know yet is served on the resident state (the actors are inserted into the sorted
+        table, one kernel renumbers the ranks the state holds) instead of by the full replay. Off by default."""
+        self._check(self._L.am355_set_resident_new_actors(self._h, 1 if on else 0))
+
+    def resident_new_actor_calls(self):
+        """(calls served on the resident state that inserted at least one actor, those of them that launched the rank rewrite)."""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self._L.am355_resident_new_actor_calls(self._h, out))
+        return int(out[0]), int(out[1])
 
     def raw(self):
         """(arena, offsets) as staged: the uncompressed change containers back to back (copies)."""

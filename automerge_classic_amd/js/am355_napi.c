@@ -309,6 +309,21 @@ static napi_value js_forget_call_history(napi_env env, napi_callback_info info) 
   return NULL;
 }
 
+/* setResidentNewActors(ctx, on): am355_set_resident_new_actors (the first changes of a new actor are merged into the state the context
+   holds instead of taking the full replay) */
+static napi_value js_set_resident_new_actors(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  bool on = true;
+  if (argc > 1) NAPI_CALL(env, napi_get_value_bool(env, argv[1], &on));
+  int rc = am355_set_resident_new_actors(ctx, on ? 1 : 0);
+  if (rc) return throw_engine(env, ctx, rc);
+  return NULL;
+}
+
 /* hashGraphKnown(ctx, set) -> boolean: am355_hash_graph_known (set: 1 / 0 / -1 = only ask) */
 static napi_value js_hash_graph_known(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -749,6 +764,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"forgetCallHistory", NULL, js_forget_call_history, NULL, NULL, NULL, napi_enumerable, NULL},
       {"hashGraphKnown", NULL, js_hash_graph_known, NULL, NULL, NULL, napi_enumerable, NULL},
       {"reset", NULL, js_reset, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"setResidentNewActors", NULL, js_set_resident_new_actors, NULL, NULL, NULL, napi_enumerable, NULL},
       {"depGraph", NULL, js_dep_graph, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomBuild", NULL, js_bloom_build, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomProbe", NULL, js_bloom_probe, NULL, NULL, NULL, napi_enumerable, NULL},

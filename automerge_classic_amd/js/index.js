@@ -81,6 +81,9 @@ function acquireContext() {
   let e
   if (contexts.length < MAX_CONTEXTS && contexts.every(x => x.generation !== 0)) {
     e = { ctx: addon.create(parseInt(process.env.MI355X_DEVICE || '0')), generation: 0, used: 0 }
+    // the first changes of a new collaborator are merged into the state the context holds (the reference appends the actor and touches
+    // no stored op, new.js:1434-1451; the engine renumbers the actor ranks it stores) instead of replaying the whole log
+    addon.setResidentNewActors(e.ctx, true)
     contexts.push(e)
   } else {
     e = contexts.reduce((a, b) => (b.used < a.used ? b : a))

@@ -352,6 +352,19 @@ int am355_resident_counters(const am355_ctx *ctx, uint64_t out[3]);
 /* ... and for how many of the first kind the map half of the merge ran on its own: batches of plain map rows only (`set` / `del` on
  * string keys: every list stayed as it was) and batches of such rows beside list edits (the list rows merged in place first) (*out) */
 int am355_resident_maps_only_calls(const am355_ctx *ctx, uint64_t *out);
+/* The first changes of a NEW actor on the resident state. The engine stores actor fields as lexicographic ranks, so an actor the
+ * document does not know yet renumbers the ranks of the kept rows: by default such a batch takes the full replay ("new actor" among the
+ * reasons of am355_resident_counters out[1]), whose cost grows with the document. on != 0: the new authors of the batch are inserted into
+ * the sorted actor table and one streaming kernel rewrites the rank words the kept state holds (the actor columns of the op rows and
+ * preds, the op ids in the object and map tables, the counters' last increments) in front of the batch's decode -- a monotone
+ * renumbering: no order between kept rows changes --; the rest of the call runs as for known actors. An actor id that a change names
+ * without anybody in the document or earlier in the batch having authored a change under it still takes the full replay. Off by default;
+ * no environment variable. What the reference has in this place: it appends the actor to the document's table and touches no stored op
+ * (new.js:1434-1451), because its op ids carry actor indexes in order of first appearance and compare through the id strings.
+ * am355_resident_new_actor_calls: calls served on the resident state that inserted at least one actor (out[0]), and how many of those
+ * launched the rank rewrite because some kept rank moved (out[1]: an actor that sorts behind every known one moves none). */
+int am355_set_resident_new_actors(am355_ctx *ctx, int on);
+int am355_resident_new_actor_calls(const am355_ctx *ctx, uint64_t out[2]);
 
 /* For bindings that mirror per-state tables of the context in their own memory (the N-API addon: BackendDoc.changes, their hashes and
  * the raw arena, backend/new.js:1847, 1855-1879) and must not copy all of them for every one-change Backend.applyChanges:
