@@ -498,7 +498,7 @@ struct am355_ctx {
   bool pos_valid = false;                          // d_pos describes c->mb.order
   bool ir_stale = false;                           // rows / order are current, the whole-document patch tables are not
   uint64_t n_resorder_calls = 0;
-  uint64_t n_maps_only_calls = 0;   // resident calls that ran merge_run_maps: plain map rows only, or beside list edits merged in place
+  uint64_t n_maps_only_calls = 0;   // resident calls that ran merge_run_maps (or, with resident_map_merge, the in-place merge of the stored map table): plain map rows only, or beside list edits merged in place
   HostBuf h_res_metas;                             // pinned: the batch's ChangeMetas on their way to the host
   uint32_t res_dep_base = 0;                       // changes >= this were applied by resident calls: their dependency indexes live in ...
   std::vector<uint32_t> res_dep_first, res_dep_index;   // ... CSR over (change - res_dep_base)
@@ -507,6 +507,12 @@ struct am355_ctx {
   // inserted into the sorted table and the ranks the state holds are renumbered (am355_prims.h RemapRanges) -- instead of by the full replay
   bool resident_new_actors = false;
   uint64_t n_new_actor_calls = 0, n_rank_rewrites = 0;   // resident calls that inserted actors | those of them that launched the rank rewrite
+  // am355_set_resident_map_merge: the plain map rows of a batch are merged into the stored map records (am355_merge.h MapMergeBufs) instead
+  // of every record being emitted and ordered again (merge_run_maps); a document without a list is served that way too
+  bool resident_map_merge = false;
+  uint64_t n_map_merge_calls = 0, n_map_merge_declined = 0;   // resident calls whose map rows were merged in place | that tried and went on with the path of before
+  DevBuf d_map_alt, d_mapmerge;                    // the other map table | the stage's scratch
+  am355_ir_map* map_alt_ptr = nullptr;             // whichever of the two map tables c->ir.map does NOT point to (null: not set up since the last carve)
   std::string resident_why;                        // why the last attempt fell back (diagnostics, AM355_TRACE)
 
   // objectId sharding (am355_set_shard): this context merges the objects rank `shard_rank` of `shard_world` owns

@@ -98,6 +98,8 @@ struct HostSignals {
   uint32_t delta_mid[16];        // DeltaCounts after the first half of the delta stage
   volatile uint32_t delta_end_seq; uint32_t pad6[15];
   uint32_t delta_end[16];        // DeltaCounts after the stage (behind the copies of its tables, when the caller enqueued them)
+  volatile uint32_t mapmerge_seq;  uint32_t pad7[15];
+  uint32_t mapmerge[16];         // MapMergeBufs.words [8] after the first half of the in-place map merge
 };
 
 // Per-actor lookup table entry for opId -> row resolution: the applied changes of one actor, ascending start_op

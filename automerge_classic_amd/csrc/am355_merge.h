@@ -138,6 +138,42 @@ void merge_run_maps(MergeBufs& b, PatchIR& ir, Counts* h_counts, hipStream_t st)
 // am355_resorder.hip, or merge_run(..., resolved = true) goes on from k_emit)
 void merge_resolve(MergeBufs& b, hipStream_t st);
 
+// ---- resident map table (am355_set_resident_map_merge; am355_merge.hip "resident map table") -------------------------------------------
+// A batch of plain map rows merged into the STORED map records: what mergeDocChangeOps does to the blocks it visits (new.js:1052-1290),
+// per touched key instead of per block. Rows [T0, T0 + n_new) are the batch (resolved: succ_cnt / inc_cnt / kind / obj_row final).
+// Coordinates: a "gap" is an index into the stored table -- the record a new one lands in front of; the k-th new record (in table
+// order) lands at gap - dead records in front of the gap + k, stored record i at i - dead in front of it + new records with gap <= i.
+struct MapMergeBufs {
+  uint32_t T0, n_new;            // the batch's rows
+  uint32_t n_map, n_obj;         // records of the stored table, objects (_root included)
+  const am355_ir_map* map;       // the stored table ...
+  am355_ir_map* map_new;         // ... and its ping-pong partner, which the merged table is written to
+  uint32_t *dead, *dead_ex;      // [n_map + 1] the record's row no longer emits (entry n_map stays 0) | its exclusive prefix sum
+  uint32_t *obj_base;            // [n_obj + 1] first record of every object in the stored table, also of objects without records (the ranges' lengths, scanned)
+  uint32_t *row_gap;             // [n_new] per batch row: the gap of its record (NONE32: no plain map row)
+  uint32_t *srt_gap, *srt_oi;    // [n_new] per new record in table order: gap, object index
+  uint32_t *words;               // [16] MapMergeWord
+  HostSignals* sig;
+  uint32_t sig_seq;
+};
+// words[]: what the first half tells the host (pinned HostSignals.mapmerge, or read from the device)
+enum MapMergeWord { MM_DECLINE = 0,     // a key holds more than MAP_GROUP_MAX stored records, or a row names an object the table does not hold
+                    MM_OTHER_ROWS = 1,  // some row of the batch is no plain map row
+                    MM_N_NEW = 2,       // plain map rows of the batch that are visible: new records (listed in b.em_row / b.em_trig)
+                    MM_MAX_KEY = 3,     // their longest key
+                    MM_N_DEAD = 4,      // stored records whose row no longer emits
+                    MM_FLAGS = 5,       // Counts.flags behind the resolution
+                    MM_WORDS = 8 };
+constexpr uint32_t MAPMERGE_ROWS_MAX = 16384;   // rows of one batch the stage takes: the caller declines a larger batch before it enqueues anything (a bulk load: merge_run_maps)
+size_t mapmerge_bytes(uint32_t n_new, uint32_t n_map, uint32_t n_obj);
+void mapmerge_bind(MapMergeBufs& m, void* block, uint32_t n_new, uint32_t n_map, uint32_t n_obj);
+// first half: per batch row the key's group in the stored table (binary search, a walk of at most MAP_GROUP_MAX records), the stored
+// records that died, the new records listed; m.words signalled to the host. Writes the stage's scratch only.
+void mapmerge_find(MergeBufs& b, const PatchIR& ir, MapMergeBufs& m, hipStream_t st);
+// second half, once the host has read the words and goes on (nothing in it can fail): the new records ordered, the merged table
+// streamed into m.map_new, the objects' map ranges rewritten. n_new_rec / max_key: words[MM_N_NEW] / words[MM_MAX_KEY].
+void mapmerge_write(MergeBufs& b, PatchIR& ir, MapMergeBufs& m, uint32_t n_new_rec, uint32_t max_key, hipStream_t st);
+
 // Document load: whole-document patch of rows already in canonical order (pred_* arrays = succ lists). `b.counts` must be
 // cleared by the caller before the decode kernels run.
 void doc_patch(MergeBufs& b, PatchIR& ir, Counts* h_counts, hipStream_t st);

@@ -184,6 +184,21 @@ __device__ __forceinline__ uint32_t block_append(uint32_t* counter, bool want, u
   return s[BLOCK / WAVE] + s[wv] + (uint32_t)__popcll(m & ((1ull << lane) - 1));
 }
 
+// Does a live K_MAP row (action a; vis: it has no successor) emit a map value, and under which trigger id: a visible `set` or make row
+// under its own id, a counter whose successors are all increments under its last increment's (new.js:937-965). The one rule for k_emit
+// and for the in-place merge of the stored map table (k_mm_rows), which judges the stored records of a touched key by it.
+__device__ __forceinline__ bool map_row_emits(const MergeBufs& b, uint32_t g, uint32_t a, bool vis, unsigned long long& trig) {
+  const OpCols& o = b.ops;
+  if (a == 1) {
+    if (vis) { trig = pack_id(o.id_ctr[g], o.id_actor[g]); return true; }
+    if ((o.val_tl[g] & 15) == 8 && b.inc_cnt[g] == b.succ_cnt[g]) { trig = b.last_inc[g]; return true; }  // every succ is an inc
+  } else if ((a & 1) == 0 && vis) {
+    trig = pack_id(o.id_ctr[g], o.id_actor[g]);
+    return true;
+  }
+  return false;
+}
+
 __global__ __launch_bounds__(BLOCK) void k_emit(MergeBufs b) {
   wave_priority_high();
   __shared__ uint32_t s_red[BLOCK / WAVE];
@@ -207,14 +222,7 @@ __global__ __launch_bounds__(BLOCK) void k_emit(MergeBufs b) {
   unsigned long long trig = 0;
   uint32_t el = NONE32;
   if (live && kind == K_MAP) {
-    uint32_t tl = o.val_tl[g];
-    if (a == 1) {
-      if (vis) { want_map = true; trig = pack_id(o.id_ctr[g], o.id_actor[g]); }
-      else if ((tl & 15) == 8 && b.inc_cnt[g] == b.succ_cnt[g]) { want_map = true; trig = b.last_inc[g]; }  // every succ is an inc
-    } else if ((a & 1) == 0 && vis) {
-      want_map = true;
-      trig = pack_id(o.id_ctr[g], o.id_actor[g]);
-    }
+    want_map = map_row_emits(b, g, a, vis, trig);
   } else if (live) {
     bool valued = (a == 1) || (a & 1) == 0;
     want_ins = kind == K_LIST_INS;
@@ -407,18 +415,23 @@ __global__ __launch_bounds__(BLOCK) void k_map_keys_hist(MergeBufs b, const uint
 // the multi-pass radix sort would spend ~16 passes of 5 launches on them. One workgroup ranks every emission against all
 // others instead. Order: (object, key bytes in UTF-16 order -- a prefix sorts first --, trigger op id).
 constexpr uint32_t MAP_SORT_SMALL = 512;  // n comparisons per lane: beyond a few hundred the radix passes win
+// two keys in the arena in the order of the map table: bytes in UTF-16 order, a prefix sorts first. < 0, 0, > 0.
+__device__ __forceinline__ int map_keys_order(const MergeBufs& b, uint32_t off_a, uint32_t la, uint32_t off_b, uint32_t lb) {
+  const uint8_t *p = b.arena + off_a, *q = b.arena + off_b;
+  const uint32_t n = la < lb ? la : lb;
+  for (uint32_t k = 0; k < n; k++) {
+    uint32_t x = utf16_order_byte(p[k]), y = utf16_order_byte(q[k]);
+    if (x != y) return x < y ? -1 : 1;
+  }
+  return la != lb ? (la < lb ? -1 : 1) : 0;
+}
 __device__ __forceinline__ bool map_emission_less(const MergeBufs& b, uint32_t ea, uint32_t eb, const uint32_t* __restrict__ obj_rank) {
   uint32_t ga = b.em_row[ea], gb = b.em_row[eb];
   uint32_t oa = obj_index_of(b, b.obj_row[ga]), ob = obj_index_of(b, b.obj_row[gb]);
   if (obj_rank) { oa = obj_rank[oa]; ob = obj_rank[ob]; }
   if (oa != ob) return oa < ob;
-  const uint8_t *p = b.arena + b.ops.key_off[ga], *q = b.arena + b.ops.key_off[gb];
-  uint32_t la = b.ops.key_len[ga], lb = b.ops.key_len[gb], n = la < lb ? la : lb;
-  for (uint32_t k = 0; k < n; k++) {
-    uint32_t x = utf16_order_byte(p[k]), y = utf16_order_byte(q[k]);
-    if (x != y) return x < y;
-  }
-  if (la != lb) return la < lb;
+  const int ko = map_keys_order(b, b.ops.key_off[ga], b.ops.key_len[ga], b.ops.key_off[gb], b.ops.key_len[gb]);
+  if (ko) return ko < 0;
   unsigned long long ta = b.em_trig[ea], tb = b.em_trig[eb];
   if (ta != tb) return ta < tb;
   return ea < eb;
@@ -508,9 +521,8 @@ __global__ __launch_bounds__(BLOCK) void k_iota(uint32_t* __restrict__ v, uint32
   if (i < n) v[i] = i;
 }
 
-// one map emission: its record at output position i (e = emission at i, e_prev / e_next = its neighbours in output order, NONE32 at the ends)
-__device__ __forceinline__ void map_finish_one(const MergeBufs& b, const PatchIR& ir, uint32_t i, uint32_t e, uint32_t e_prev, uint32_t e_next) {
-  uint32_t g = b.em_row[e];
+// the record of the map value row g emits
+__device__ __forceinline__ am355_ir_map map_record_of(const MergeBufs& b, uint32_t g) {
   const OpCols& o = b.ops;
   uint32_t a = o.action[g];
   uint32_t flags = 0;
@@ -523,8 +535,13 @@ __device__ __forceinline__ void map_finish_one(const MergeBufs& b, const PatchIR
   } else if ((a & 1) == 0) {
     flags |= AM355_MAP_CHILD;
   }
-  ir.map[i] = am355_ir_map{o.id_ctr[g], o.id_actor[g], o.key_off[g], o.key_len[g], o.val_tl[g], (flags & AM355_MAP_CHILD) ? b.obj_index[g] : o.val_off[g],
-                           flags, 0, counter};
+  return am355_ir_map{o.id_ctr[g], o.id_actor[g], o.key_off[g], o.key_len[g], o.val_tl[g], (flags & AM355_MAP_CHILD) ? b.obj_index[g] : o.val_off[g],
+                      flags, 0, counter};
+}
+// one map emission: its record at output position i (e = emission at i, e_prev / e_next = its neighbours in output order, NONE32 at the ends)
+__device__ __forceinline__ void map_finish_one(const MergeBufs& b, const PatchIR& ir, uint32_t i, uint32_t e, uint32_t e_prev, uint32_t e_next) {
+  uint32_t g = b.em_row[e];
+  ir.map[i] = map_record_of(b, g);
   uint32_t oi = obj_index_of(b, b.obj_row[g]);
   uint32_t prev = e_prev != NONE32 ? obj_index_of(b, b.obj_row[b.em_row[e_prev]]) : NONE32;
   uint32_t next = e_next != NONE32 ? obj_index_of(b, b.obj_row[b.em_row[e_next]]) : NONE32;
@@ -557,6 +574,128 @@ __device__ __forceinline__ void map_small_finish(const MergeBufs& b, uint32_t n,
 __global__ __launch_bounds__(BLOCK) void k_map_small_finish(MergeBufs b, uint32_t n, PatchIR ir) {
   wave_priority_high();
   map_small_finish(b, n, ir);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// resident map table: a batch of plain map rows merged into the STORED records (am355_merge.h MapMergeBufs; replay_resident).
+// The reference merges the batch into its stored op set and touches only the blocks it visits (new.js:1052-1290 mergeDocChangeOps);
+// here every batch row finds its key's records in the stored table by binary search, the records whose rows no longer emit go out,
+// the batch's visible rows come in -- ordered among themselves by the machinery above --, and one streaming pass writes the table.
+// ---------------------------------------------------------------------------------------------------------
+// the dead marks cleared, the words cleared, and per object the length of its range in the stored table: the records lie object by
+// object, so the exclusive scan of the lengths (mapmerge_find) is every object's first record -- also of an object without records,
+// whose range is (0, 0)
+__global__ __launch_bounds__(BLOCK) void k_mm_begin(PatchIR ir, MapMergeBufs m) {
+  const uint32_t i = gtid();
+  if (i <= m.n_map) m.dead[i] = 0;
+  if (i <= m.n_obj) m.obj_base[i] = i < m.n_obj ? ir.obj[i].map_end - ir.obj[i].map_begin : 0u;
+  if (i < MM_WORDS) m.words[i] = 0;
+}
+
+// the trigger id a stored record stands under: a counter's is its row's last increment, as in k_emit and kd_map_records
+__device__ __forceinline__ unsigned long long map_record_trigger(const MergeBufs& b, const am355_ir_map& rec, uint32_t row) {
+  return (rec.flags & AM355_MAP_COUNTER) ? b.last_inc[row] : pack_id(rec.id_ctr, rec.id_actor);
+}
+
+// one thread per batch row. A plain map row looks its key up in its object's stretch of the stored table, judges every stored record
+// of the key by k_emit's rule (several rows that name one pred mark it with the same plain store: dead once), and -- visible itself --
+// is listed as an emission with the gap its record lands in. Reads the stored table, writes scratch.
+__global__ __launch_bounds__(BLOCK) void k_mm_rows(MergeBufs b, MapMergeBufs m) {
+  __shared__ uint32_t s_app[BLOCK / WAVE + 2];
+  const OpCols& o = b.ops;
+  const uint32_t t = gtid();
+  const bool in_range = t < m.n_new;
+  const uint32_t g = m.T0 + t;
+  bool plain = false, want = false;
+  unsigned long long trig = 0;
+  uint32_t gap = NONE32;
+  if (in_range) {
+    const uint8_t kind = b.kind[g];
+    const uint32_t a = o.action[g];
+    plain = plain_map_row(kind, a, o.key_len[g]);
+    const uint32_t orow = b.obj_row[g];
+    if (!plain) m.words[MM_OTHER_ROWS] = 1;
+    else if (orow != NONE32 && orow >= m.T0) m.words[MM_DECLINE] = 1;   // (an object of this batch: its make row is no plain row anyway)
+    else {
+      const uint32_t oi = obj_index_of(b, orow);
+      if (oi >= m.n_obj) m.words[MM_DECLINE] = 1;   // (never expected: the table holds every kept object)
+      else {
+        const uint32_t koff = o.key_off[g], klen = o.key_len[g];
+        uint32_t lo = m.obj_base[oi];
+        const uint32_t end = m.obj_base[oi + 1];
+        uint32_t hi = end;
+        while (lo < hi) {   // the first record of the object whose key is not in front of this row's
+          const uint32_t mid = (lo + hi) >> 1;
+          if (map_keys_order(b, m.map[mid].key_off, m.map[mid].key_len, koff, klen) < 0) lo = mid + 1; else hi = mid;
+        }
+        want = kind == K_MAP && map_row_emits(b, g, a, b.succ_cnt[g] == 0, trig);
+        uint32_t below = 0, steps = 0;
+        for (uint32_t j = lo; j < end; j++, steps++) {
+          const am355_ir_map rec = m.map[j];
+          if (map_keys_order(b, rec.key_off, rec.key_len, koff, klen) != 0) break;
+          if (steps >= MAP_GROUP_MAX) { m.words[MM_DECLINE] = 1; break; }
+          const uint32_t r = row_of(b, rec.id_actor, rec.id_ctr);
+          if (r == NONE32 || r >= m.T0) { m.words[MM_DECLINE] = 1; break; }   // (never expected: a record's row is a kept row)
+          unsigned long long unused;
+          const uint8_t rk = b.kind[r];
+          if (!(rk == K_MAP && map_row_emits(b, r, o.action[r], b.succ_cnt[r] == 0, unused))) m.dead[j] = 1;
+          below += map_record_trigger(b, rec, r) < trig ? 1u : 0u;
+        }
+        gap = lo + below;
+      }
+    }
+  }
+  const uint32_t slot = block_append(&m.words[MM_N_NEW], want, s_app);
+  if (want) {
+    b.em_row[slot] = g;
+    b.em_trig[slot] = trig;
+    if (o.key_len[g] > *(volatile uint32_t*)&m.words[MM_MAX_KEY]) atomicMax(&m.words[MM_MAX_KEY], o.key_len[g]);
+  }
+  if (in_range) m.row_gap[t] = want ? gap : NONE32;
+}
+
+// behind the scan of the dead marks: the words to the host
+__global__ __launch_bounds__(WAVE) void k_mm_signal(MergeBufs b, MapMergeBufs m) {
+  if (threadIdx.x) return;
+  m.words[MM_N_DEAD] = m.dead_ex[m.n_map];
+  m.words[MM_FLAGS] = b.counts->flags;
+  if (m.sig) signal_host(m.sig->mapmerge, m.words, MM_WORDS, &m.sig->mapmerge_seq, m.sig_seq);
+}
+
+// the new records in table order (perm: their emissions ordered): gap and object of the k-th, and its record at its place
+__global__ __launch_bounds__(BLOCK) void k_mm_place(MergeBufs b, MapMergeBufs m, const uint32_t* __restrict__ perm, uint32_t n_rec) {
+  const uint32_t k = gtid();
+  if (k >= n_rec) return;
+  const uint32_t g = b.em_row[perm[k]], gap = m.row_gap[g - m.T0];
+  m.srt_gap[k] = gap;
+  m.srt_oi[k] = obj_index_of(b, b.obj_row[g]);
+  m.map_new[gap - m.dead_ex[gap] + k] = map_record_of(b, g);
+}
+
+// the streaming pass. Workgroups [0, rec_blocks): stored record i, when its row still emits, to i - dead in front + new records with
+// gap <= i (a new record stands in FRONT of the stored record at its gap). The rest: the objects' ranges -- survivors in front of the
+// object's first stored record + new records of the objects in front; an object left without records gets (0, 0), as k_compact_rows
+// and k_map_finish leave it. Every object thread reads and writes its own entry only.
+__global__ __launch_bounds__(BLOCK) void k_mm_write(PatchIR ir, MapMergeBufs m, uint32_t n_rec, uint32_t rec_blocks) {
+  if (blockIdx.x < rec_blocks) {
+    const uint32_t i = gtid();
+    if (i >= m.n_map || m.dead[i]) return;
+    uint32_t lo = 0, hi = n_rec;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (m.srt_gap[mid] <= i) lo = mid + 1; else hi = mid; }
+    m.map_new[i - m.dead_ex[i] + lo] = m.map[i];
+    return;
+  }
+  const uint32_t oi = (blockIdx.x - rec_blocks) * BLOCK + threadIdx.x;
+  if (oi >= m.n_obj) return;
+  const uint32_t first = m.obj_base[oi], end = m.obj_base[oi + 1];
+  uint32_t lo = 0, hi = n_rec;
+  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (m.srt_oi[mid] < oi) lo = mid + 1; else hi = mid; }
+  const uint32_t in_front = lo;
+  hi = n_rec;
+  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (m.srt_oi[mid] <= oi) lo = mid + 1; else hi = mid; }
+  const uint32_t begin_new = first - m.dead_ex[first] + in_front, end_new = end - m.dead_ex[end] + lo;
+  ir.obj[oi].map_begin = end_new > begin_new ? begin_new : 0u;
+  ir.obj[oi].map_end = end_new > begin_new ? end_new : 0u;
 }
 
 static int bits_for(uint64_t max_value) {
@@ -1584,8 +1723,9 @@ bool merge_prepare(MergeBufs& b, hipStream_t aux, int what, const FillRanges* ex
 }
 
 // map emissions: LSD over (trigger id | key length | key chunks last..first | object)
+// (perm_only: the order alone -- *perm_only = the emission indexes in table order, in the sort scratch; no record is written)
 static void order_map_emissions(MergeBufs& b, PatchIR& ir, const Counts* hc, hipStream_t st, uint32_t* ride_with_list_order = nullptr,
-                                const MapKeyStats* ks = nullptr, bool trigger_passes = false) {
+                                const MapKeyStats* ks = nullptr, bool trigger_passes = false, const uint32_t** perm_only = nullptr) {
   uint32_t ne = hc->n_map_emit;
   if (!ne) return;
   uint32_t* perm_a = b.val_a;
@@ -1610,7 +1750,7 @@ static void order_map_emissions(MergeBufs& b, PatchIR& ir, const Counts* hc, hip
   // (measured in round 5 and not adopted: all passes of all key fields in ONE launch of one workgroup, 8-16 wavefronts each owning a
   // contiguous stretch of the pairs -- 400 us for the map workload's 17 k emissions against 150 us for the 22 tiled launches: a
   // wavefront's 64-item steps each wait a memory round trip, and keeping a lane's 24-48 pairs in registers spilled; profiles/r05_c3_*)
-  if (ne <= BLOCK) {
+  if (ne <= BLOCK && !perm_only) {
     if (ride_with_list_order) *ride_with_list_order = ne;  // (an extra workgroup of k_list_order_objs: merge_run)
     else hipLaunchKernelGGL(k_map_small_finish, dim3(1), dim3(BLOCK), 0, st, b, ne, ir);
     return;
@@ -1658,6 +1798,7 @@ static void order_map_emissions(MergeBufs& b, PatchIR& ir, const Counts* hc, hip
                              last_is_chunk0 ? (const uint64_t*)(cur ? b.key_b : b.key_a) : (const uint64_t*)nullptr);
     cur ^= 1;
   }
+  if (perm_only) { *perm_only = cur ? perm_b : perm_a; return; }
   AM355_LAUNCH_INDEPENDENT(k_map_finish, grid_for(ne), dim3(BLOCK), st, b, (const uint32_t*)(cur ? perm_b : perm_a), ne, ir);
 }
 
@@ -1844,6 +1985,49 @@ void merge_run_maps(MergeBufs& b, PatchIR& ir, Counts* hc, hipStream_t st) {
     (void)hipStreamSynchronize(st);
     hc->map_group_big = 0;
   }
+}
+
+// ---- resident map table: host side (am355_merge.h) ----
+static size_t mm_al(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+size_t mapmerge_bytes(uint32_t n_new, uint32_t n_map, uint32_t n_obj) {
+  return 2 * mm_al(4 * ((size_t)n_map + 1)) + mm_al(4 * ((size_t)n_obj + 1)) + 3 * mm_al(4 * ((size_t)n_new + 1)) + mm_al(64) + 256;
+}
+void mapmerge_bind(MapMergeBufs& m, void* block, uint32_t n_new, uint32_t n_map, uint32_t n_obj) {
+  uint8_t* p = (uint8_t*)block;
+  auto take = [&](size_t bytes) { void* q = p; p += mm_al(bytes); return (uint32_t*)q; };
+  m.dead = take(4 * ((size_t)n_map + 1));
+  m.dead_ex = take(4 * ((size_t)n_map + 1));
+  m.obj_base = take(4 * ((size_t)n_obj + 1));
+  m.row_gap = take(4 * ((size_t)n_new + 1));
+  m.srt_gap = take(4 * ((size_t)n_new + 1));
+  m.srt_oi = take(4 * ((size_t)n_new + 1));
+  m.words = take(64);
+  m.n_new = n_new; m.n_map = n_map; m.n_obj = n_obj;
+}
+
+void mapmerge_find(MergeBufs& b, const PatchIR& ir, MapMergeBufs& m, hipStream_t st) {
+  // (n_map + 1 marks, n_obj + 1 lengths, n_new >= 1 rows, one thread to signal: no grid is empty)
+  AM355_LAUNCH_INDEPENDENT(k_mm_begin, grid_for(std::max(std::max(m.n_map, m.n_obj) + 1, (uint32_t)MM_WORDS)), dim3(BLOCK), st, ir, m);
+  exclusive_scan_u32(m.obj_base, m.obj_base, m.n_obj + 1, nullptr, b.scan_ws, st);
+  hipLaunchKernelGGL(k_mm_rows, grid_for(std::max(m.n_new, 1u)), dim3(BLOCK), 0, st, b, m);
+  exclusive_scan_u32(m.dead, m.dead_ex, m.n_map + 1, nullptr, b.scan_ws, st);
+  hipLaunchKernelGGL(k_mm_signal, dim3(1), dim3(WAVE), 0, st, b, m);
+}
+
+void mapmerge_write(MergeBufs& b, PatchIR& ir, MapMergeBufs& m, uint32_t n_new_rec, uint32_t max_key, hipStream_t st) {
+  if (n_new_rec) {
+    // the new records among themselves: up to MAP_SORT_SMALL ranked from LDS, beyond by the key passes -- the values of a key by
+    // passes over their trigger ids, which no count of values on one key can fail
+    Counts hc{};
+    hc.n_map_emit = n_new_rec;
+    hc.max_key_len = max_key;
+    hc.n_objects = m.n_obj - 1;
+    const uint32_t* perm = nullptr;
+    order_map_emissions(b, ir, &hc, st, nullptr, nullptr, true, &perm);
+    AM355_LAUNCH_INDEPENDENT(k_mm_place, grid_for(n_new_rec), dim3(BLOCK), st, b, m, perm, n_new_rec);
+  }
+  const uint32_t rec_blocks = grid_for(m.n_map).x;
+  AM355_LAUNCH_INDEPENDENT(k_mm_write, dim3(rec_blocks + grid_for(m.n_obj).x), dim3(BLOCK), st, ir, m, n_new_rec, rec_blocks);
 }
 
 // Whole-document patch of canonical rows (document load). Synchronises the stream twice (counts).

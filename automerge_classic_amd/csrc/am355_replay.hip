@@ -533,6 +533,7 @@ int setup_buffers(am355_ctx* c, uint32_t NA) {
   size_t Nc = (size_t)N + 1;
   c->resident_valid = false;
   c->order_alt_ptr = nullptr;
+  c->map_alt_ptr = nullptr;
   c->pos_valid = false;
   c->ir_stale = false;
   canary_scope("replay buffers (setup_buffers: op rows, preds, merge scratch, sort scratch, patch IR)");
@@ -1500,6 +1501,89 @@ static int replay_resident(am355_ctx* c) {
     if (!c->pos_valid) resorder_positions(b, NL_old, ro.pos_of, st);
     resorder_run(b, ro, st, &final_in_new);
   }
+  // ---- map table: with am355_set_resident_map_merge the batch's plain map rows are merged into the STORED records (am355_merge.h
+  //      MapMergeBufs) where merge_run_maps would emit and order every record of the document again. Its first half reads the stored
+  //      table and writes scratch; the host reads its words and only then lets the second half write the other table buffer and the
+  //      objects' ranges -- a batch it declines goes on with the path of before on state nobody touched. A document without a list has
+  //      no list stage whose verdict says "plain map rows only": the first half's own look at the rows decides, and it is enqueued
+  //      here, in front of the host's hashing. ----
+  const bool map_merge_on = c->resident_map_merge && NN && c->mb.row_stride;
+  const bool map_merge_fits = NN <= MAPMERGE_ROWS_MAX;   // (a larger batch is declined here, before anything is enqueued for it)
+  const bool map_merge_alone = map_merge_on && !try_resorder && NL_old == 0;
+  MapMergeBufs mm{};
+  auto map_merge_find = [&]() -> int {
+    const uint32_t n_map = c->counts.n_map_emit, n_obj = c->counts.n_objects;
+    if (!c->map_alt_ptr) {
+      if (!c->d_map_alt.ensure(sizeof(am355_ir_map) * (size_t)c->mb.row_stride)) return fail(c, AM355_E_NOMEM, "device allocation failed (resident map table)");
+      c->map_alt_ptr = c->d_map_alt.as<am355_ir_map>();
+    }
+    if (!c->d_mapmerge.ensure(mapmerge_bytes(NN, n_map, n_obj))) return fail(c, AM355_E_NOMEM, "device allocation failed (resident map table)");
+    mapmerge_bind(mm, c->d_mapmerge.p, NN, n_map, n_obj);
+    mm.T0 = (uint32_t)old_ops;
+    mm.map = c->ir.map; mm.map_new = c->map_alt_ptr;
+    mm.sig = b.sig; mm.sig_seq = b.sig_seq;
+    mapmerge_find(b, c->ir, mm, st);
+    return AM355_OK;
+  };
+  // The batch's map rows into the stored table: the first half (own_look: no list stage judged the batch -- the first half was enqueued
+  // in front of the host's hashing and says itself whether every row is a plain map row; a batch with other rows is no attempt), its
+  // words, and -- unless it declines -- the second half. served: the stored table is the merged one.
+  auto map_rows_in_place = [&](bool own_look, bool& served) -> int {
+    uint32_t w[MM_WORDS];
+    served = false;
+    if (!map_merge_on) return AM355_OK;
+    if (!map_merge_fits) {
+      c->n_map_merge_declined++;
+      lap("map table: batch beyond the stage's rows, left to the map half of the merge");
+      return AM355_OK;
+    }
+    if (!own_look) { const int frc = map_merge_find(); if (frc) return frc; }
+    if (wait_host_signal(&b.sig->mapmerge_seq, b.sig_seq, st)) {
+      memcpy(w, (const void*)b.sig->mapmerge, sizeof w);
+      c->staging_in_flight = false;   // (the kernel that signalled ran behind everything that read the pinned arena)
+    } else {
+      HIPCHK(c, hipStreamSynchronize(st));
+      HIPCHK(c, hipMemcpy(w, mm.words, sizeof w, hipMemcpyDeviceToHost));
+    }
+    if (w[MM_FLAGS]) return error_for_flags(c, w[MM_FLAGS], "op set rejected");
+    if (own_look && w[MM_OTHER_ROWS]) return AM355_OK;
+    const uint32_t n_after = mm.n_map - w[MM_N_DEAD] + w[MM_N_NEW];
+    if (w[MM_DECLINE] || n_after > c->mb.row_stride) {
+      c->n_map_merge_declined++;
+      lap("map table: left to the map half of the merge");
+      return AM355_OK;
+    }
+    mapmerge_write(b, c->ir, mm, w[MM_N_NEW], w[MM_MAX_KEY], st);
+    am355_ir_map* const was = c->ir.map;
+    c->ir.map = c->map_alt_ptr;
+    c->map_alt_ptr = was;   // (the previous table is what the next in-place merge writes)
+    c->counts.n_map_emit = n_after;
+    c->counts.max_key_len = std::max(c->counts.max_key_len, w[MM_MAX_KEY]);   // (an upper bound: read to size the key passes of the map order only)
+    c->n_map_merge_calls++;
+    served = true;
+    lap("map table merged in place");
+    if (getenv("AM355_MAPMERGE_VERIFY")) {   // (tests; read per call)
+      std::vector<am355_ir_map> got(n_after), want(n_after);
+      std::vector<am355_ir_object> got_obj(mm.n_obj), want_obj(mm.n_obj);
+      HIPCHK(c, hipStreamSynchronize(st));
+      if (n_after) HIPCHK(c, hipMemcpy(got.data(), c->ir.map, sizeof(am355_ir_map) * (size_t)n_after, hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(got_obj.data(), c->ir.obj, sizeof(am355_ir_object) * (size_t)mm.n_obj, hipMemcpyDeviceToHost));
+      merge_run_maps(b, c->ir, hc, st);
+      HIPCHK(c, hipStreamSynchronize(st));
+      if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
+      bool same = hc->n_map_emit == n_after;
+      if (same) {
+        if (n_after) HIPCHK(c, hipMemcpy(want.data(), c->ir.map, sizeof(am355_ir_map) * (size_t)n_after, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(want_obj.data(), c->ir.obj, sizeof(am355_ir_object) * (size_t)mm.n_obj, hipMemcpyDeviceToHost));
+        same = !n_after || memcmp(got.data(), want.data(), sizeof(am355_ir_map) * (size_t)n_after) == 0;
+        for (uint32_t k = 0; same && k < mm.n_obj; k++) same = got_obj[k].map_begin == want_obj[k].map_begin && got_obj[k].map_end == want_obj[k].map_end;
+      }
+      if (trace && !same) fprintf(stderr, "resident: map table verify: %u records in place, %u from scratch\n", n_after, hc->n_map_emit);
+      if (!same) return fail(c, AM355_E_DEVICE, "internal: the map table merged in place differs from the table computed from scratch");
+    }
+    return AM355_OK;
+  };
+  if (map_merge_alone && map_merge_fits) { const int mrc = map_merge_find(); if (mrc) return mrc; }
   lap("resolution / list order enqueued");
   // ---- host, while the device works on the batch: hashes, duplicates, dependencies; then the commit ----
   if (const char* why = hashes_and_dependencies()) {
@@ -1546,11 +1630,15 @@ static int replay_resident(am355_ctx* c) {
       if (hw[4]) {
         // plain map rows beside the list edits (text typed and a key assigned in one change): the map half of the merge behind the
         // in-place list merge -- the map records and the object table's map ranges change, the delta stage runs its map kernels
-        merge_run_maps(b, c->ir, hc, st);
-        lap("map half of the merge done");
-        if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
-        c->counts.n_map_emit = hc->n_map_emit;
-        c->counts.max_key_len = hc->max_key_len;
+        bool in_place = false;
+        { const int mrc = map_rows_in_place(false, in_place); if (mrc) return mrc; }
+        if (!in_place) {
+          merge_run_maps(b, c->ir, hc, st);
+          lap("map half of the merge done");
+          if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
+          c->counts.n_map_emit = hc->n_map_emit;
+          c->counts.max_key_len = hc->max_key_len;
+        }
         c->h_tables_current = false;
         c->ir_copy_enqueued = 0;
         c->batch_list_only = false;
@@ -1560,11 +1648,15 @@ static int replay_resident(am355_ctx* c) {
       // a batch of plain map rows (`set` / `del` on string keys): no list changes -- the stored order, positions and element counts stay,
       // the map half of the merge runs alone (visibility, object table, map records in patch order); the whole-document edit tables are
       // stale from here on, as after an in-place list merge
-      merge_run_maps(b, c->ir, hc, st);
-      lap("map half of the merge done");
-      if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
-      c->counts.n_map_emit = hc->n_map_emit;
-      c->counts.max_key_len = hc->max_key_len;
+      bool in_place = false;
+      { const int mrc = map_rows_in_place(false, in_place); if (mrc) return mrc; }
+      if (!in_place) {
+        merge_run_maps(b, c->ir, hc, st);
+        lap("map half of the merge done");
+        if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
+        c->counts.n_map_emit = hc->n_map_emit;
+        c->counts.max_key_len = hc->max_key_len;
+      }
       c->ir_stale = true;
       c->ir_fetched = false;
       c->n_maps_only_calls++;
@@ -1573,6 +1665,22 @@ static int replay_resident(am355_ctx* c) {
     } else {
       c->pos_valid = false;
       lap("list order: not a batch for the in-place merge");
+    }
+  }
+  if (map_merge_alone) {
+    // a document without a list: plain map rows only -> the stored map table merged in place is all the call changes (the edit tables
+    // are stale from here on, as behind the map half alone); anything else goes on with merge_run below, as without the switch
+    bool in_place = false;
+    const int mrc = map_rows_in_place(true, in_place);
+    if (mrc) return mrc;
+    if (in_place) {
+      c->ir_stale = true;
+      c->ir_fetched = false;
+      c->h_tables_current = false;
+      c->ir_copy_enqueued = 0;
+      c->n_maps_only_calls++;
+      c->pos_valid = false;   // (no list, no positions: the first list rows take merge_run)
+      maps_only = true;
     }
   }
   if (!merged_in_place && !maps_only) {

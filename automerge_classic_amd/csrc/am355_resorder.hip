@@ -65,7 +65,7 @@ __global__ __launch_bounds__(WAVE) void kr_gaps(MergeBufs b, ResOrderBufs r) {
   // every list as it is: the caller then runs the map half of the merge alone (merge_run_maps). Every chunk's rows are looked at.
   // words[4]: some row IS a plain map row: it takes no part in the list order (a row like a deletion here), and the caller runs the map
   // half of the merge behind the in-place list merge.
-  const bool plain_map = (kind == K_MAP && a == 1) || (kind == K_DEL && o.key_len[g] != NONE32);
+  const bool plain_map = plain_map_row(kind, a, o.key_len[g]);
   if (lane == 0) r.words[plain_map ? 4 : 3] = 1;
   // (a chunk behind one that was refused: the order it would scan was never written)
   if (r.chunk && r.words[0]) return;

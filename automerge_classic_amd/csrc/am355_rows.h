@@ -47,6 +47,12 @@ __device__ __forceinline__ bool same_key(const MergeBufs& b, uint32_t r1, uint32
   return true;
 }
 
+// a plain map row: `set` of a value / `del` on a string key -- no object made, no increment (what a resident call merges without a
+// look at the lists: am355_resorder.hip kr_gaps, am355_merge.hip k_mm_rows)
+__device__ __forceinline__ bool plain_map_row(uint8_t kind, uint32_t action, uint32_t key_len) {
+  return (kind == K_MAP && action == 1) || (kind == K_DEL && key_len != NONE32);
+}
+
 __device__ __forceinline__ uint32_t obj_index_of(const MergeBufs& b, uint32_t make_row) { return make_row == NONE32 ? 0 : b.obj_index[make_row]; }
 
 // JS compares strings by UTF-16 code units (new.js:84). On valid UTF-8 that equals byte order except that

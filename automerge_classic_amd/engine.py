@@ -105,6 +105,11 @@ def _bind(path):
         L.am355_set_resident_new_actors.restype = ctypes.c_int
         L.am355_resident_new_actor_calls.argtypes = [vp, vp]
         L.am355_resident_new_actor_calls.restype = ctypes.c_int
+    if hasattr(L, "am355_set_resident_map_merge"):
+        L.am355_set_resident_map_merge.argtypes = [vp, ctypes.c_int]
+        L.am355_set_resident_map_merge.restype = ctypes.c_int
+        L.am355_resident_map_merge_calls.argtypes = [vp, vp]
+        L.am355_resident_map_merge_calls.restype = ctypes.c_int
     L.am355_get_raw.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32)]
     L.am355_doc_changes.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_void_p)]
     L.am355_apply_changes.argtypes = [vp, vp, u64p, u32]
@@ -360,6 +365,18 @@ class Engine:
         """(calls served on the resident state that inserted at least one actor, those of them that launched the rank rewrite)."""
         out = (ctypes.c_uint64 * 2)()
         self._check(self._L.am355_resident_new_actor_calls(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def set_resident_map_merge(self, on):
+        """on: the plain map rows of a batch (`set` / `del` on string keys) are merged into the stored map records of the resident state
+        instead of every record being emitted and ordered again; a document without a list is served that way too. Off by default."""
+        self._check(self._L.am355_set_resident_map_merge(self._h, 1 if on else 0))
+
+    def resident_map_merge_calls(self):
+        """(resident calls whose map rows were merged into the stored map table in place, calls that tried, declined and were served by
+        the path of before)."""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self._L.am355_resident_map_merge_calls(self._h, out))
         return int(out[0]), int(out[1])
 
     def raw(self):

@@ -20,6 +20,7 @@ const path = require('path')
 
 const JS_ONLY = process.env.MI355X_BACKEND_JS_ONLY === '1'
 const HYDRATE_FROM_DOC = process.env.MI355X_HYDRATE === 'doc'
+const MAP_MERGE = process.env.MI355X_MAP_MERGE === '1'   // am355_set_resident_map_merge for every context of this module
 const PATCH_VIA_JSON = process.env.MI355X_PATCH_VIA_JSON === '1'   // A/B: JSON text rendered by the engine + JSON.parse
 const { materialize } = require('./materialize.js')
 let addon = null, ctx = null
@@ -32,6 +33,7 @@ let tick = 0
 if (!JS_ONLY) {
   addon = require(path.join(__dirname, 'am355_napi.node'))
   ctx = addon.create(parseInt(process.env.MI355X_DEVICE || '0'))   // throws without an MI355X
+  if (MAP_MERGE) addon.setResidentMapMerge(ctx, true)   // (as for every context acquireContext makes, see there)
   contexts.push({ ctx, generation: 0, used: 0 })
 }
 
@@ -84,6 +86,10 @@ function acquireContext() {
     // the first changes of a new collaborator are merged into the state the context holds (the reference appends the actor and touches
     // no stored op, new.js:1434-1451; the engine renumbers the actor ranks it stores) instead of replaying the whole log
     addon.setResidentNewActors(e.ctx, true)
+    // key assignments are merged into the map records the context holds (the reference merges a batch into its stored op set and
+    // touches only the blocks it visits, new.js:1052-1290) instead of every map value of the document being ordered again
+    // (MI355X_MAP_MERGE=1: measured, the path gains nothing on one-change calls and is slower on 40-change calls, profiles/map_merge_timings.txt -- not the default here)
+    if (MAP_MERGE) addon.setResidentMapMerge(e.ctx, true)
     contexts.push(e)
   } else {
     e = contexts.reduce((a, b) => (b.used < a.used ? b : a))
@@ -741,6 +747,8 @@ module.exports = {
   // engine statistics of the last GPU replay (not part of the reference surface)
   _engineStats: () => (addon ? addon.stats(ctx) : null),
   _counters: counters,
+  // [calls whose map rows were merged into the stored map table in place, calls that tried and declined], over all contexts
+  _residentMapMergeCalls: () => contexts.reduce((s, e) => { const w = addon.residentMapMergeCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),
   _applyProfile: profile,
   _hydrate: hydrate   // (tests: the reference handle of an engine state, made the way the state came to be)
 }

@@ -365,6 +365,21 @@ int am355_resident_maps_only_calls(const am355_ctx *ctx, uint64_t *out);
  * launched the rank rewrite because some kept rank moved (out[1]: an actor that sorts behind every known one moves none). */
 int am355_set_resident_new_actors(am355_ctx *ctx, int on);
 int am355_resident_new_actor_calls(const am355_ctx *ctx, uint64_t out[2]);
+/* Plain map rows (`set` of a value / `del` on a string key: no object made, no increment) merged into the STORED map records. By default
+ * a resident call with such rows runs the map half of the merge over the whole document (am355_resident_maps_only_calls: every op row
+ * judged again, every map value ordered again), and a document without any list takes all of merge_run: both grow with the document.
+ * on != 0: every map row of the batch finds its key's records in the stored table by binary search; the records whose rows the batch
+ * overwrote or deleted go out, the batch's visible rows come in -- ordered among themselves --, and one streaming pass writes the merged
+ * table beside the stored one and rewrites the objects' map ranges. No pass over the document's op rows, no sort of the stored values.
+ * The patch tables are byte for byte what the path of before writes (AM355_MAPMERGE_VERIFY=1 in the environment: every such call
+ * rebuilds them that way and compares). Left to the path of before, on state the attempt did not touch: a key that holds more than 256
+ * stored values, a batch of more than 16384 rows, declined before anything is enqueued for it (both counted in out[1]); and, as before, batches that increment counters or make
+ * objects, which this path does not look at. Off by default; no environment variable. What the reference has in this place:
+ * mergeDocChangeOps merges the batch into the stored op set and touches only the blocks it visits (new.js:1052-1290).
+ * am355_resident_map_merge_calls: resident calls whose map rows were merged into the stored table in place (out[0]); calls that tried
+ * and declined, and were served by the path of before (out[1]). */
+int am355_set_resident_map_merge(am355_ctx *ctx, int on);
+int am355_resident_map_merge_calls(const am355_ctx *ctx, uint64_t out[2]);
 
 /* For bindings that mirror per-state tables of the context in their own memory (the N-API addon: BackendDoc.changes, their hashes and
  * the raw arena, backend/new.js:1847, 1855-1879) and must not copy all of them for every one-change Backend.applyChanges:

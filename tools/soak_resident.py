@@ -2,7 +2,9 @@
 CPU emulation): text typed by one author, concurrent text with deletions over one or more objects, maps with conflicts; batches of
 random sizes (1 .. 40 changes), the in-place list merge in random chunk sizes, AM355_RESORDER_VERIFY on. Every incremental patch, the
 whole-document patch every few calls and at the end, and Backend.save against a bulk replay are compared.
-  python tools/soak_resident.py <first seed> <sessions>"""
+  python tools/soak_resident.py <first seed> <sessions> [big | campaigns | mapmerge]
+  mapmerge: the map and mixed session kinds only, with am355_set_resident_map_merge on and AM355_MAPMERGE_VERIFY=1 (every in-place merge of
+  the stored map table is rebuilt from scratch and compared)."""
 import os
 import random
 import sys
@@ -20,12 +22,17 @@ from test_apply_vectors import same_patch  # noqa: E402
 LIB = os.environ.get("AM355_TOOL_LIB")
 first, count = int(sys.argv[1]), int(sys.argv[2])
 BIG = len(sys.argv) > 3 and sys.argv[3] == "big"   # long concurrent-text logs delivered in batches of up to 144 changes: several chunks of the in-place merge, tens of thousands of edit items
-totals = {"sessions": 0, "calls": 0, "served": 0, "fell_back": 0, "in_place": 0, "maps_only": 0, "refused": 0}
+MAPMERGE = len(sys.argv) > 3 and sys.argv[3] == "mapmerge"
+if MAPMERGE:
+    os.environ["AM355_MAPMERGE_VERIFY"] = "1"
+totals = {"sessions": 0, "calls": 0, "served": 0, "fell_back": 0, "in_place": 0, "maps_only": 0, "refused": 0, "map_merged": 0, "map_declined": 0}
 for seed in range(first, first + count):
     rnd = random.Random(seed)
     kind = rnd.choice(["typing", "concurrent", "concurrent", "concurrent_small", "map", "mixed", "mixed"])
     if BIG:
         kind = "big"
+    if MAPMERGE:
+        kind = rnd.choice(["map", "mixed"])
     if kind == "big":
         log = loggen.generate(loggen.KIND_TEXT_CONCURRENT, n_actors=rnd.randint(8, 24), n_rounds=rnd.randint(6, 14), ins_per_change=rnd.randint(40, 320),
                               del_per_change=rnd.randint(0, 60), n_objects=rnd.randint(1, 3), seed=seed)
@@ -84,6 +91,8 @@ for seed in range(first, first + count):
         j = rnd.randint(1, len(batches) - 2)
         batches[j], batches[j + 1] = batches[j + 1], batches[j]
     eng = engine.Engine(0, LIB) if LIB else engine.Engine(0)
+    if MAPMERGE:
+        eng.set_resident_map_merge(True)
     session = oracle_lib.OracleSession()
     try:
         for i, batch in enumerate(batches):
@@ -114,6 +123,9 @@ for seed in range(first, first + count):
         s, f, p = eng.resident_counters()
         totals["served"] += s; totals["fell_back"] += f; totals["in_place"] += p
         totals["maps_only"] += eng.resident_maps_only_calls()
+        if MAPMERGE:
+            m, d = eng.resident_map_merge_calls()
+            totals["map_merged"] += m; totals["map_declined"] += d
         totals["sessions"] += 1
     finally:
         eng.close()
