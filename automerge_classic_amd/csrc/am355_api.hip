@@ -8,6 +8,7 @@
 //                                  additionally ranks actors lexicographically for numeric op-id comparison)
 //   envelope                       backend/new.js:1870-1873, 2064-2067 (maxOp, clock, deps, pendingChanges)
 #include "am355_ctx.h"
+#include "am355_scan.h"
 
 // the context's host threads, streams, events and signal words; false: something could not be made (the caller deletes the context,
 // which destroys what was)
@@ -218,6 +219,316 @@ extern "C" int am355_test_scan(am355_ctx* c, const uint32_t* in, uint32_t* out, 
   (void)hipMemcpyAsync(total, dt.p, 4, hipMemcpyDeviceToHost, st);
   HIPCHK(c, hipStreamSynchronize(st));
   return AM355_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The device primitives of am355_prims.h and the workgroup / carried scans of am355_scan.h, each driven by itself
+// (tests/test_primitives.py). A hook uploads the caller's buffer images WHOLE, hands the primitive a pointer some words (bytes) into
+// them, and downloads them whole: the caller sees what was written around a range as well as in it. Offsets and ranges that would
+// leave an image are refused with AM355_E_ARG before anything is launched.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+// device image of a host buffer, 16-byte aligned whatever the allocator gives
+struct TestImage {
+  DevBuf d;
+  uint8_t* p = nullptr;
+  size_t bytes = 0;
+  bool up(const void* host, size_t n, hipStream_t st) {
+    if (!d.ensure(n + 16)) return false;
+    p = (uint8_t*)(((uintptr_t)d.p + 15) & ~(uintptr_t)15);
+    bytes = n;
+    if (n) (void)hipMemcpyAsync(p, host, n, hipMemcpyHostToDevice, st);
+    return true;
+  }
+  void down(void* host, hipStream_t st) const {
+    if (bytes) (void)hipMemcpyAsync(host, p, bytes, hipMemcpyDeviceToHost, st);
+  }
+  uint32_t* words(size_t off = 0) const { return (uint32_t*)p + off; }
+};
+int test_finish(am355_ctx* c) {
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  return AM355_OK;
+}
+
+// carried scan: the producer / consumer pair of the replay kernels, one value per thread (am355_scan.h)
+__global__ __launch_bounds__(BLOCK) void k_test_carry_produce(const uint32_t* __restrict__ v, uint32_t n, CarryScan cs) {
+  __shared__ uint32_t s[BLOCK / WAVE];
+  const uint32_t i = gtid();
+  (void)carry_publish(cs, i < n ? v[i] : 0u, s);
+}
+// out: the exclusive prefix over the grid (carry_prefix); out_wg / wg_total: over the workgroup alone (block_exclusive_scan_u32)
+__global__ __launch_bounds__(BLOCK) void k_test_carry_consume(const uint32_t* __restrict__ v, uint32_t n, CarryScan cs, uint32_t* __restrict__ out,
+                                                              uint32_t* __restrict__ out_wg, uint32_t* __restrict__ wg_total) {
+  __shared__ uint32_t s[BLOCK / WAVE];
+  const uint32_t i = gtid();
+  const uint32_t x = i < n ? v[i] : 0u;
+  uint32_t total;
+  const uint32_t in_wg = block_exclusive_scan_u32(x, s, &total);
+  const uint32_t pre = carry_prefix(cs, x, s);
+  if (i < n) { out[i] = pre; out_wg[i] = in_wg; }
+  if (threadIdx.x == 0) wg_total[blockIdx.x] = total;
+}
+}  // namespace
+
+extern "C" int am355_test_scan_at(am355_ctx* c, uint32_t* in_buf, uint32_t in_words, uint32_t in_off, uint32_t* out_buf, uint32_t out_words, uint32_t out_off, uint32_t n,
+                                  uint32_t* total) {
+  if (!c || !in_buf) return AM355_E_ARG;
+  return guarded(c, [&]() -> int {
+    const bool in_place = !out_buf;
+    if (in_off > 3 || out_off > 3 || (size_t)in_off + n > in_words || (in_place ? out_off != in_off : (size_t)out_off + n > out_words))
+      return fail(c, AM355_E_ARG, "am355_test_scan_at: the range leaves its buffer");
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    TestImage di, dout, dt;
+    DevBuf ws;
+    uint32_t none = 0;
+    if (!di.up(in_buf, 4 * (size_t)in_words, st) || !dout.up(out_buf, in_place ? 0 : 4 * (size_t)out_words, st) || !dt.up(total ? total : &none, 4, st) ||
+        !ws.ensure(scan_workspace_bytes(n)))
+      return fail(c, AM355_E_NOMEM, "alloc");
+    exclusive_scan_u32(di.words(in_off), in_place ? di.words(in_off) : dout.words(out_off), n, total ? dt.words() : nullptr, ws.p, st);
+    di.down(in_buf, st);
+    dout.down(out_buf, st);
+    if (total) dt.down(total, st);
+    return test_finish(c);
+  });
+}
+
+extern "C" int am355_test_scan2(am355_ctx* c, uint32_t* in_a, uint32_t* in_b, uint32_t in_words, uint32_t in_off, uint32_t* out_a, uint32_t* out_b, uint32_t out_words,
+                                uint32_t out_off, uint32_t n, uint32_t* total_a, uint32_t* total_b) {
+  if (!c || !in_a || !in_b || !out_a != !out_b) return AM355_E_ARG;
+  return guarded(c, [&]() -> int {
+    const bool in_place = !out_a;
+    if (in_off > 3 || out_off > 3 || (size_t)in_off + n > in_words || (in_place ? out_off != in_off : (size_t)out_off + n > out_words))
+      return fail(c, AM355_E_ARG, "am355_test_scan2: the range leaves its buffer");
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    TestImage da, db, oa, ob, dt;
+    DevBuf ws;
+    uint32_t t2[2] = {total_a ? *total_a : 0u, total_b ? *total_b : 0u};
+    const size_t ob_bytes = in_place ? 0 : 4 * (size_t)out_words;
+    if (!da.up(in_a, 4 * (size_t)in_words, st) || !db.up(in_b, 4 * (size_t)in_words, st) || !oa.up(out_a, ob_bytes, st) || !ob.up(out_b, ob_bytes, st) || !dt.up(t2, 8, st) ||
+        !ws.ensure(scan_workspace_bytes(n)))
+      return fail(c, AM355_E_NOMEM, "alloc");
+    exclusive_scan2_u32(da.words(in_off), in_place ? da.words(in_off) : oa.words(out_off), total_a ? dt.words(0) : nullptr, db.words(in_off),
+                        in_place ? db.words(in_off) : ob.words(out_off), total_b ? dt.words(1) : nullptr, n, ws.p, st);
+    da.down(in_a, st);
+    db.down(in_b, st);
+    oa.down(out_a, st);
+    ob.down(out_b, st);
+    dt.down(t2, st);
+    int rc = test_finish(c);
+    if (rc != AM355_OK) return rc;
+    if (total_a) *total_a = t2[0];
+    if (total_b) *total_b = t2[1];
+    return AM355_OK;
+  });
+}
+
+extern "C" int am355_test_scan_terminators(am355_ctx* c, const uint8_t* bytes_buf, size_t bytes_len, uint32_t byte_off, uint32_t L, uint32_t* out_buf, uint32_t out_words,
+                                           uint32_t out_off, uint32_t* total) {
+  if (!c || !bytes_buf || !out_buf) return AM355_E_ARG;
+  return guarded(c, [&]() -> int {
+    if (byte_off > 7 || out_off > 3 || L == 0xffffffffu || (size_t)byte_off + L > bytes_len || (size_t)out_off + L + 1 > out_words)
+      return fail(c, AM355_E_ARG, "am355_test_scan_terminators: the range leaves its buffer");
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    TestImage db, dout, dt;
+    DevBuf ws;
+    uint32_t none = 0;
+    if (!db.up(bytes_buf, bytes_len, st) || !dout.up(out_buf, 4 * (size_t)out_words, st) || !dt.up(total ? total : &none, 4, st) || !ws.ensure(scan_workspace_bytes(L + 1)))
+      return fail(c, AM355_E_NOMEM, "alloc");
+    exclusive_scan_terminators(db.p + byte_off, L, dout.words(out_off), total ? dt.words() : nullptr, ws.p, st);
+    dout.down(out_buf, st);
+    if (total) dt.down(total, st);
+    return test_finish(c);
+  });
+}
+
+// *inout: what *d_out holds before the call, and after it
+extern "C" int am355_test_max(am355_ctx* c, const uint32_t* v, uint32_t n, uint32_t* inout) {
+  if (!c || (!v && n) || !inout) return AM355_E_ARG;
+  return guarded(c, [&]() -> int {
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    TestImage dv, dm;
+    if (!dv.up(v, 4 * (size_t)n, st) || !dm.up(inout, 4, st)) return fail(c, AM355_E_NOMEM, "alloc");
+    max_u32(dv.words(), n, dm.words(), st);
+    dm.down(inout, st);
+    return test_finish(c);
+  });
+}
+
+// first_table: null, or the histogram of the first digit as the caller computed it ([digit x sort_tiles(n) + tile], am355_prims.h): uploaded
+// to sort_first_table(ws) and the sort called with first_hist_done. *result_buffer: what radix_sort_pairs returned; keys / vals come
+// back from that buffer.
+extern "C" int am355_test_sort_bits(am355_ctx* c, uint64_t* keys, uint32_t* vals, uint32_t n, int begin_bit, int end_bit, const uint32_t* first_table, int* result_buffer) {
+  if (!c || ((!keys || !vals) && n) || !result_buffer) return AM355_E_ARG;
+  return guarded(c, [&]() -> int {
+    if (begin_bit < 0 || end_bit > 64 || begin_bit > end_bit) return fail(c, AM355_E_ARG, "am355_test_sort_bits: bits [%d, %d)", begin_bit, end_bit);
+    if (first_table && !sort_is_fused(n)) return fail(c, AM355_E_ARG, "am355_test_sort_bits: first_hist_done is for fused sorts only (%u elements are %u tiles)", n, sort_tiles(n));
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    TestImage ka, va;
+    DevBuf kb, vb, ws;
+    if (!ka.up(keys, 8 * (size_t)n, st) || !kb.ensure(8 * (size_t)n + 8) || !va.up(vals, 4 * (size_t)n, st) || !vb.ensure(4 * (size_t)n + 4) || !ws.ensure(sort_workspace_bytes(n)))
+      return fail(c, AM355_E_NOMEM, "alloc");
+    if (first_table && n) (void)hipMemcpyAsync(sort_first_table(ws.p), first_table, 4 * (size_t)256 * sort_tiles(n), hipMemcpyHostToDevice, st);
+    const int res = radix_sort_pairs((uint64_t*)ka.p, va.words(), kb.as<uint64_t>(), vb.as<uint32_t>(), n, begin_bit, end_bit, ws.p, st, first_table != nullptr);
+    if (n) {
+      (void)hipMemcpyAsync(keys, res ? kb.p : (void*)ka.p, 8 * (size_t)n, hipMemcpyDeviceToHost, st);
+      (void)hipMemcpyAsync(vals, res ? vb.p : (void*)va.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st);
+    }
+    *result_buffer = res;
+    return test_finish(c);
+  });
+}
+
+// mark: [mark_words >= n] words, the first n are the marks
+extern "C" int am355_test_chain_mark(am355_ctx* c, const uint32_t* next, uint32_t* mark, uint32_t mark_words, uint32_t n) {
+  if (!c || ((!next || !mark) && n) || mark_words < n) return AM355_E_ARG;
+  return guarded(c, [&]() -> int {
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    TestImage dn, dm;
+    DevBuf work;
+    if (!dn.up(next, 4 * (size_t)n, st) || !dm.up(mark, 4 * (size_t)mark_words, st) || !work.ensure(chain_work_bytes(n))) return fail(c, AM355_E_NOMEM, "alloc");
+    chain_mark(dn.words(), n, dm.words(), work.p, st);
+    dm.down(mark, st);
+    return test_finish(c);
+  });
+}
+
+// ranges: n_ranges x {first word (an offset into buf, base_off is added), count, stride, guard (int32), guard_skip}. *n_added: the ranges
+// the table held at the launch. AM355_E_ARG: RemapRanges::add() refused one (nothing is launched then).
+extern "C" int am355_test_remap(am355_ctx* c, uint32_t* buf, uint32_t words, uint32_t base_off, const uint32_t* ranges, uint32_t n_ranges, const uint32_t* table,
+                                uint32_t n_old, uint32_t* n_added) {
+  if (!c || !buf || (!ranges && n_ranges) || (!table && n_old)) return AM355_E_ARG;
+  return guarded(c, [&]() -> int {
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    TestImage db, dt;
+    if (!db.up(buf, 4 * (size_t)words, st) || !dt.up(table, 4 * (size_t)n_old, st)) return fail(c, AM355_E_NOMEM, "alloc");
+    RemapRanges r;
+    for (uint32_t k = 0; k < n_ranges; k++) {
+      const uint32_t* q = ranges + 5 * (size_t)k;
+      const int64_t first = (int64_t)base_off + q[0], count = q[1], stride = q[2], guard = (int32_t)q[3];
+      if (count && stride) {
+        const int64_t last = first + (count - 1) * stride;
+        if (base_off > 3 || last >= (int64_t)words || first + guard < 0 || last + guard >= (int64_t)words || (guard && (guard <= -stride || guard >= stride)))
+          return fail(c, AM355_E_ARG, "am355_test_remap: range %u leaves the buffer (or its guard the record)", k);
+      }
+      if (!r.add(db.words((size_t)first), (size_t)count, (uint32_t)stride, (int32_t)guard, q[4])) return fail(c, AM355_E_ARG, "am355_test_remap: add() refused range %u", k);
+    }
+    if (n_added) *n_added = r.n;
+    launch_remap_ranks(r, dt.words(), n_old, st);
+    db.down(buf, st);
+    return test_finish(c);
+  });
+}
+
+// ranges: n_ranges x {first word (+ base_off), BYTES, value}
+extern "C" int am355_test_fill(am355_ctx* c, uint32_t* buf, uint32_t words, uint32_t base_off, const uint32_t* ranges, uint32_t n_ranges, uint32_t* n_added) {
+  if (!c || !buf || (!ranges && n_ranges)) return AM355_E_ARG;
+  return guarded(c, [&]() -> int {
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    TestImage db;
+    if (!db.up(buf, 4 * (size_t)words, st)) return fail(c, AM355_E_NOMEM, "alloc");
+    FillRanges f;
+    for (uint32_t k = 0; k < n_ranges; k++) {
+      const uint32_t* q = ranges + 3 * (size_t)k;
+      const size_t first = (size_t)base_off + q[0];
+      if (base_off > 3 || first + ((size_t)q[1] + 3) / 4 > words) return fail(c, AM355_E_ARG, "am355_test_fill: range %u leaves the buffer", k);
+      if (!f.add(db.words(first), q[1], q[2])) return fail(c, AM355_E_ARG, "am355_test_fill: add() refused range %u", k);
+    }
+    if (n_added) *n_added = f.n;
+    launch_fill_ranges(f, st);
+    db.down(buf, st);
+    return test_finish(c);
+  });
+}
+
+// ranges: n_ranges x {byte offset into dst, byte offset into src, bytes}. src_pinned: the source lies in pinned host memory and the kernel
+// reads it over the link (the product's case); else in device memory.
+extern "C" int am355_test_copy(am355_ctx* c, uint8_t* dst, size_t dst_bytes, const uint8_t* src, size_t src_bytes, int src_pinned, const uint32_t* ranges, uint32_t n_ranges,
+                               uint32_t* n_added) {
+  if (!c || !dst || !src || (!ranges && n_ranges)) return AM355_E_ARG;
+  return guarded(c, [&]() -> int {
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    TestImage dd, ds;
+    HostBuf hs;
+    const uint8_t* s0;
+    if (!dd.up(dst, dst_bytes, st)) return fail(c, AM355_E_NOMEM, "alloc");
+    if (src_pinned) {
+      if (!hs.ensure(src_bytes + 16)) return fail(c, AM355_E_NOMEM, "alloc");
+      uint8_t* h = (uint8_t*)(((uintptr_t)hs.p + 15) & ~(uintptr_t)15);
+      memcpy(h, src, src_bytes);
+      s0 = h;
+    } else {
+      if (!ds.up(src, src_bytes, st)) return fail(c, AM355_E_NOMEM, "alloc");
+      s0 = ds.p;
+    }
+    CopyRanges r;
+    for (uint32_t k = 0; k < n_ranges; k++) {
+      const uint32_t* q = ranges + 3 * (size_t)k;
+      if ((size_t)q[0] + q[2] > dst_bytes || (size_t)q[1] + q[2] > src_bytes) return fail(c, AM355_E_ARG, "am355_test_copy: range %u leaves its buffer", k);
+      if (!r.add(dd.p + q[0], s0 + q[1], q[2])) return fail(c, AM355_E_ARG, "am355_test_copy: add() refused range %u", k);
+    }
+    if (n_added) *n_added = r.n;
+    launch_copy_ranges(r, st);
+    dd.down(dst, st);
+    return test_finish(c);   // (the pinned source lives until here: the kernel has run)
+  });
+}
+
+// host_words: [host_words_n >= n_a + n_b] words as pinned memory holds them before the launch, and after it; *seq_word likewise
+extern "C" int am355_test_signal_words(am355_ctx* c, const uint32_t* a, uint32_t n_a, const uint32_t* b, uint32_t n_b, uint32_t seq, uint32_t* host_words,
+                                       uint32_t host_words_n, uint32_t* seq_word) {
+  if (!c || (!a && n_a) || (!b && n_b) || !host_words || !seq_word || (size_t)n_a + n_b > host_words_n) return AM355_E_ARG;
+  return guarded(c, [&]() -> int {
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    TestImage da, db;
+    HostBuf h;
+    if (!da.up(a, 4 * (size_t)n_a, st) || !db.up(b, 4 * (size_t)n_b, st) || !h.ensure(4 * ((size_t)host_words_n + 1))) return fail(c, AM355_E_NOMEM, "alloc");
+    uint32_t* hw = h.as<uint32_t>();
+    memcpy(hw, host_words, 4 * (size_t)host_words_n);
+    hw[host_words_n] = *seq_word;
+    launch_signal_words(da.words(), n_a, db.words(), n_b, hw, (volatile uint32_t*)(hw + host_words_n), seq, st);
+    int rc = test_finish(c);
+    if (rc != AM355_OK) return rc;
+    memcpy(host_words, hw, 4 * (size_t)host_words_n);
+    *seq_word = hw[host_words_n];
+    return AM355_OK;
+  });
+}
+
+// out: carry_prefix of v over the grid; out_wg / wg_total ([(n + 255) / 256]): block_exclusive_scan_u32 of v over each workgroup and its sum
+extern "C" int am355_test_carried_scan(am355_ctx* c, const uint32_t* v, uint32_t n, uint32_t* out, uint32_t* out_wg, uint32_t* wg_total) {
+  if (!c || !v || !out || !out_wg || !wg_total || !n || n > 0xffffff00u) return AM355_E_ARG;
+  return guarded(c, [&]() -> int {
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    const uint32_t wgs = (n + BLOCK - 1) / BLOCK;
+    const size_t group_words = ((size_t)(wgs >> CARRY_GROUP_SHIFT) + 1) * CARRY_GROUP_STRIDE;
+    TestImage dv;
+    DevBuf d_out, d_wg, d_tot, d_carry;
+    if (!dv.up(v, 4 * (size_t)n, st) || !d_out.ensure(4 * (size_t)n) || !d_wg.ensure(4 * (size_t)n) || !d_tot.ensure(4 * (size_t)wgs) ||
+        !d_carry.ensure(4 * (wgs + group_words)))
+      return fail(c, AM355_E_NOMEM, "alloc");
+    CarryScan cs;
+    cs.wg_sum = d_carry.as<uint32_t>();
+    cs.group_sum = cs.wg_sum + wgs;
+    (void)hipMemsetAsync(cs.group_sum, 0, 4 * group_words, st);
+    hipLaunchKernelGGL(k_test_carry_produce, dim3(wgs), dim3(BLOCK), 0, st, (const uint32_t*)dv.words(), n, cs);
+    hipLaunchKernelGGL(k_test_carry_consume, dim3(wgs), dim3(BLOCK), 0, st, (const uint32_t*)dv.words(), n, cs, d_out.as<uint32_t>(), d_wg.as<uint32_t>(), d_tot.as<uint32_t>());
+    (void)hipMemcpyAsync(out, d_out.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st);
+    (void)hipMemcpyAsync(out_wg, d_wg.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st);
+    (void)hipMemcpyAsync(wg_total, d_tot.p, 4 * (size_t)wgs, hipMemcpyDeviceToHost, st);
+    return test_finish(c);
+  });
 }
 
 extern "C" int am355_get_rows(am355_ctx* c, uint32_t* obj_actor, uint32_t* obj_ctr, uint32_t* key_actor, uint32_t* key_ctr, uint32_t* key_off,

@@ -75,6 +75,14 @@ void exclusive_scan2_u32(const uint32_t* in_a, uint32_t* out_a, uint32_t* d_tota
 // *d_out = max(*d_out, max(v[0..n)))
 void max_u32(const uint32_t* v, uint32_t n, uint32_t* d_out, hipStream_t st);
 size_t sort_workspace_bytes(uint32_t n);
+// Stable LSD sort of (key, value) pairs, ascending, by WHOLE 8-bit digits from begin_bit up: ceil((end_bit - begin_bit) / 8) passes
+// (none when end_bit <= begin_bit: the pairs stay where they are), pass k by bits [begin_bit + 8 k, begin_bit + 8 k + 8) (a digit that
+// reaches past bit 63 is filled with zeros). So every key bit in [begin_bit, begin_bit + 8 * passes) takes part -- also the ones between
+// end_bit and the top of the last digit, which the CONTRACT wants zero in every key (or equal in all of them): callers build their keys
+// from fields that add up to end_bit bits and leave everything above zero, or pass whole bytes (order_map_emissions). Bits below begin_bit
+// and above the last digit are carried along and never looked at. Pairs whose looked-at bits are equal keep their input order.
+// Returns where the result lies: 0 = (keys_a, vals_a), 1 = (keys_b, vals_b) -- the parity of the number of passes (0 when n == 0: nothing is launched);
+// the other pair of buffers holds the state before the last pass.
 // first_hist_done: the caller's own kernel (the one that produced keys_a) has already left the histogram of the FIRST digit (bits
 // [begin_bit, begin_bit + 8)) in sort_first_table(ws), laid out [digit x sort_tiles(n) + tile] over tiles of SORT_TILE_ELEMS elements --
 // only for sorts with sort_is_fused(n)

@@ -79,6 +79,17 @@ def _bind(path):
     L.am355_get_hashes.argtypes = [vp, vp]
     L.am355_test_sort.argtypes = [vp, vp, vp, u32, ctypes.c_int]
     L.am355_test_scan.argtypes = [vp, vp, vp, u32, vp]
+    sz, ci = ctypes.c_size_t, ctypes.c_int
+    for f, args in (("am355_test_scan_at", [vp, vp, u32, u32, vp, u32, u32, u32, vp]), ("am355_test_scan2", [vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, vp]),
+                    ("am355_test_scan_terminators", [vp, vp, sz, u32, u32, vp, u32, u32, vp]), ("am355_test_max", [vp, vp, u32, vp]),
+                    ("am355_test_sort_bits", [vp, vp, vp, u32, ci, ci, vp, ctypes.POINTER(ci)]), ("am355_test_chain_mark", [vp, vp, vp, u32, u32]),
+                    ("am355_test_remap", [vp, vp, u32, u32, vp, u32, vp, u32, ctypes.POINTER(u32)]), ("am355_test_fill", [vp, vp, u32, u32, vp, u32, ctypes.POINTER(u32)]),
+                    ("am355_test_copy", [vp, vp, sz, vp, sz, ci, vp, u32, ctypes.POINTER(u32)]), ("am355_test_signal_words", [vp, vp, u32, vp, u32, u32, vp, u32, vp]),
+                    ("am355_test_carried_scan", [vp, vp, u32, vp, vp, vp])):
+        if not hasattr(L, f):   # (a library of an earlier commit, loaded for an A/B run)
+            continue
+        getattr(L, f).argtypes = args
+        getattr(L, f).restype = ci
     L.am355_get_rows.argtypes = [vp] * 15
     L.am355_save.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
     L.am355_get_applied.argtypes = [vp, vp, ctypes.POINTER(u32)]
@@ -417,6 +428,92 @@ class Engine:
         total = np.zeros(1, dtype=np.uint32)
         self._check(self._L.am355_test_scan(self._h, a.ctypes.data, out.ctypes.data, a.size, total.ctypes.data))
         return out, int(total[0])
+
+    # The primitives one by one (am355_test_* of include/am355.h). Buffers are images: copies go to the device whole and come back whole,
+    # so the words around a range can be compared as well. `total` arguments: None = not asked for, else the word's value before the call.
+    @staticmethod
+    def _img(a, dtype=np.uint32):
+        return None if a is None else np.ascontiguousarray(a, dtype=dtype).copy()
+
+    @staticmethod
+    def _ptr(a):
+        return None if a is None else a.ctypes.data
+
+    def prim_scan(self, in_buf, in_off, n, out_buf=None, out_off=0, total=None):
+        """exclusive_scan_u32 from in_buf[in_off:] into out_buf[out_off:] (None: in place). Returns (in_buf, out_buf, total) afterwards."""
+        a, o = self._img(in_buf), self._img(out_buf)
+        t = None if total is None else np.array([total], dtype=np.uint32)
+        self._check(self._L.am355_test_scan_at(self._h, a.ctypes.data, a.size, in_off, self._ptr(o), 0 if o is None else o.size, in_off if o is None else out_off, n, self._ptr(t)))
+        return a, o, None if t is None else int(t[0])
+
+    def prim_scan2(self, in_a, in_b, in_off, n, out_a=None, out_b=None, out_off=0, total_a=None, total_b=None):
+        a, b, oa, ob = self._img(in_a), self._img(in_b), self._img(out_a), self._img(out_b)
+        ta = None if total_a is None else np.array([total_a], dtype=np.uint32)
+        tb = None if total_b is None else np.array([total_b], dtype=np.uint32)
+        self._check(self._L.am355_test_scan2(self._h, a.ctypes.data, b.ctypes.data, a.size, in_off, self._ptr(oa), self._ptr(ob), 0 if oa is None else oa.size,
+                                             in_off if oa is None else out_off, n, self._ptr(ta), self._ptr(tb)))
+        return a, b, oa, ob, None if ta is None else int(ta[0]), None if tb is None else int(tb[0])
+
+    def prim_scan_terminators(self, bytes_buf, byte_off, L, out_buf, out_off, total=None):
+        b, o = self._img(bytes_buf, np.uint8), self._img(out_buf)
+        t = None if total is None else np.array([total], dtype=np.uint32)
+        self._check(self._L.am355_test_scan_terminators(self._h, b.ctypes.data, b.size, byte_off, L, o.ctypes.data, o.size, out_off, self._ptr(t)))
+        return o, None if t is None else int(t[0])
+
+    def prim_max(self, values, before):
+        v = self._img(values)
+        t = np.array([before], dtype=np.uint32)
+        self._check(self._L.am355_test_max(self._h, v.ctypes.data, v.size, t.ctypes.data))
+        return int(t[0])
+
+    def prim_sort(self, keys, vals, begin_bit, end_bit, first_table=None):
+        """radix_sort_pairs. Returns (keys, vals, the buffer the sort said holds them)."""
+        k, v, tab = self._img(keys, np.uint64), self._img(vals), self._img(first_table)
+        res = ctypes.c_int(-1)
+        self._check(self._L.am355_test_sort_bits(self._h, k.ctypes.data, v.ctypes.data, k.size, begin_bit, end_bit, self._ptr(tab), ctypes.byref(res)))
+        return k, v, res.value
+
+    def prim_chain_mark(self, nxt, mark, n):
+        nx, m = self._img(nxt), self._img(mark)
+        self._check(self._L.am355_test_chain_mark(self._h, nx.ctypes.data, m.ctypes.data, m.size, n))
+        return m
+
+    def prim_remap(self, buf, base_off, ranges, table):
+        """ranges: [(first word, count, stride, guard, guard_skip)]. Returns (buf, ranges the table held)."""
+        b, tab = self._img(buf), self._img(table)
+        r = np.array([[f, c, s, g & 0xFFFFFFFF, k] for f, c, s, g, k in ranges], dtype=np.uint32).reshape(-1, 5)
+        added = ctypes.c_uint32(0)
+        self._check(self._L.am355_test_remap(self._h, b.ctypes.data, b.size, base_off, r.ctypes.data, len(ranges), tab.ctypes.data, tab.size, ctypes.byref(added)))
+        return b, added.value
+
+    def prim_fill(self, buf, base_off, ranges):
+        """ranges: [(first word, bytes, value)]."""
+        b = self._img(buf)
+        r = np.array(ranges, dtype=np.uint32).reshape(-1, 3)
+        added = ctypes.c_uint32(0)
+        self._check(self._L.am355_test_fill(self._h, b.ctypes.data, b.size, base_off, r.ctypes.data, len(ranges), ctypes.byref(added)))
+        return b, added.value
+
+    def prim_copy(self, dst, src, ranges, src_pinned):
+        """ranges: [(dst byte offset, src byte offset, bytes)]."""
+        d, s = self._img(dst, np.uint8), self._img(src, np.uint8)
+        r = np.array(ranges, dtype=np.uint32).reshape(-1, 3)
+        added = ctypes.c_uint32(0)
+        self._check(self._L.am355_test_copy(self._h, d.ctypes.data, d.size, s.ctypes.data, s.size, 1 if src_pinned else 0, r.ctypes.data, len(ranges), ctypes.byref(added)))
+        return d, added.value
+
+    def prim_signal_words(self, a, b, seq, host_words, seq_word):
+        wa, wb, h = self._img(a), self._img(b), self._img(host_words)
+        s = np.array([seq_word], dtype=np.uint32)
+        self._check(self._L.am355_test_signal_words(self._h, wa.ctypes.data, wa.size, wb.ctypes.data, wb.size, seq, h.ctypes.data, h.size, s.ctypes.data))
+        return h, int(s[0])
+
+    def prim_carried_scan(self, values):
+        """Returns (carry_prefix over the grid, block_exclusive_scan_u32 within each workgroup, the workgroups' sums)."""
+        v = self._img(values)
+        out, out_wg, tot = np.empty_like(v), np.empty_like(v), np.empty((v.size + 255) // 256, dtype=np.uint32)
+        self._check(self._L.am355_test_carried_scan(self._h, v.ctypes.data, v.size, out.ctypes.data, out_wg.ctypes.data, tot.ctypes.data))
+        return out, out_wg, tot
 
     def rows(self):
         n = int(self.stats().n_ops)

@@ -396,6 +396,37 @@ int am355_applied_in_input_order(const am355_ctx *ctx, int *yes);
 /* ---- diagnostics: device primitives exposed for kernel-level tests ---- */
 int am355_test_sort(am355_ctx *ctx, uint64_t *keys, uint32_t *vals, uint32_t n, int key_bits);
 int am355_test_scan(am355_ctx *ctx, const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *total);
+/* The primitives one by one (tests/test_primitives.py). Every buffer is an IMAGE: uploaded whole, handed to the primitive at the given
+ * offset (scans: 0..3 words, so that the pointer is deliberately not 16-byte aligned; terminators: 0..7 bytes), downloaded whole -- the
+ * caller sees the words around a range too. A range that would leave its image is refused with AM355_E_ARG, nothing is launched.
+ *   scan_at / scan2: out_buf (out_a and out_b) NULL = in place (out_off == in_off); a NULL total is not asked for, else it holds the
+ *     word's value before the call and after it.  scan_terminators: out has L + 1 entries.  max: *inout = *d_out before and after.
+ *   sort_bits: first_table NULL, or the first digit's histogram computed by the caller ([digit * tiles + tile], tiles of 2048 pairs;
+ *     AM355_E_ARG for sorts of more than 64 tiles); *result_buffer = 0 / 1, the buffer the sort named -- keys / vals come from there.
+ *   remap: ranges = n_ranges x {first word, count, stride, guard (int32), guard_skip}; fill: x {first word, BYTES, value}; both with
+ *     base_off (0..3 words) added to every first word.  copy: x {dst byte offset, src byte offset, bytes}, the source in pinned host
+ *     memory (src_pinned) or in device memory.  AM355_E_ARG also when the range table's add() refuses a range; *n_added = ranges the
+ *     table held at the launch.
+ *   signal_words: host_words / *seq_word = the pinned words before and after the launch.
+ *   carried_scan: out = exclusive prefix of v over the grid (carry_publish in one kernel, carry_prefix in the next); out_wg, wg_total
+ *     [(n + 255) / 256] = exclusive prefix within each 256-thread workgroup and its sum (block_exclusive_scan_u32). */
+int am355_test_scan_at(am355_ctx *ctx, uint32_t *in_buf, uint32_t in_words, uint32_t in_off, uint32_t *out_buf, uint32_t out_words, uint32_t out_off,
+                       uint32_t n, uint32_t *total);
+int am355_test_scan2(am355_ctx *ctx, uint32_t *in_a, uint32_t *in_b, uint32_t in_words, uint32_t in_off, uint32_t *out_a, uint32_t *out_b, uint32_t out_words,
+                     uint32_t out_off, uint32_t n, uint32_t *total_a, uint32_t *total_b);
+int am355_test_scan_terminators(am355_ctx *ctx, const uint8_t *bytes_buf, size_t bytes_len, uint32_t byte_off, uint32_t L, uint32_t *out_buf, uint32_t out_words,
+                                uint32_t out_off, uint32_t *total);
+int am355_test_max(am355_ctx *ctx, const uint32_t *v, uint32_t n, uint32_t *inout);
+int am355_test_sort_bits(am355_ctx *ctx, uint64_t *keys, uint32_t *vals, uint32_t n, int begin_bit, int end_bit, const uint32_t *first_table, int *result_buffer);
+int am355_test_chain_mark(am355_ctx *ctx, const uint32_t *next, uint32_t *mark, uint32_t mark_words, uint32_t n);
+int am355_test_remap(am355_ctx *ctx, uint32_t *buf, uint32_t words, uint32_t base_off, const uint32_t *ranges, uint32_t n_ranges, const uint32_t *table, uint32_t n_old,
+                     uint32_t *n_added);
+int am355_test_fill(am355_ctx *ctx, uint32_t *buf, uint32_t words, uint32_t base_off, const uint32_t *ranges, uint32_t n_ranges, uint32_t *n_added);
+int am355_test_copy(am355_ctx *ctx, uint8_t *dst, size_t dst_bytes, const uint8_t *src, size_t src_bytes, int src_pinned, const uint32_t *ranges, uint32_t n_ranges,
+                    uint32_t *n_added);
+int am355_test_signal_words(am355_ctx *ctx, const uint32_t *a, uint32_t n_a, const uint32_t *b, uint32_t n_b, uint32_t seq, uint32_t *host_words, uint32_t host_words_n,
+                            uint32_t *seq_word);
+int am355_test_carried_scan(am355_ctx *ctx, const uint32_t *v, uint32_t n, uint32_t *out, uint32_t *out_wg, uint32_t *wg_total);
 /* decoded op rows of the last replay, copied to caller arrays of length n_ops (any pointer may be NULL) */
 int am355_get_rows(am355_ctx *ctx, uint32_t *obj_actor, uint32_t *obj_ctr, uint32_t *key_actor, uint32_t *key_ctr, uint32_t *key_off,
                    uint32_t *key_len, uint32_t *action, uint32_t *val_tl, uint32_t *val_off, uint32_t *pred_num, uint32_t *id_ctr,

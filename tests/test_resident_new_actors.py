@@ -456,3 +456,40 @@ def test_recorded_sessions_emulated(emu_lib):
 @pytest.mark.gpu
 def test_recorded_sessions_gpu():
     check_recorded_sessions(_gpu, 2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 8. the rank inside a counter's stored last-increment id
+# ---------------------------------------------------------------------------------------------------------------------------
+def check_last_increment_rank(make_engine):
+    """tests/golden/resident/last_inc_rank.json (oracle/js/make_last_inc_rank.js, hand-built with the reference's encodeChange). Actors
+    X < A < N1 < N2 < B by id. First call: X makes the counter `cnt`, A and B increment it concurrently, both under op counter 5 -- the
+    kept state stores 5@B, B of rank 2, as the id under which the completed counter is emitted (MergeBufs.last_inc). Second call: N1 and
+    N2 arrive, N2 assigns `cnt` concurrently under 5@N2. The key now has two values, emitted in the order of (5@N2, 5@B): equal
+    counters, so B's rank -- 4 now -- against N2's 3 decides. With the rank left at 2 the counter comes first, with the rewrite of that
+    range (am355_replay.hip replay_resident) the string, as in the reference: in the patch of the call, in the whole-document patch behind
+    it, and in the patch of a third call by A that leaves the key alone."""
+    import base64
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "resident", "last_inc_rank.json")) as f:
+        fx = json.load(f)
+    batches = [[base64.b64decode(c) for c in b] for b in fx["batches"]]
+    ids = fx["actors"]
+    assert ids["A"] < ids["N1"] < ids["N2"] < ids["B"]
+    assert [author_of(c).hex() for c in batches[1]] == [ids["N1"], ids["N2"]]
+    make = Switched(make_engine)
+    seen = drive(make, batches, {0: NOT_ATTEMPTED}, whole_after=(1,), saved_log=ChangeLog.from_changes([c for b in batches for c in b]))
+    assert all(s[:3] in (IN_PLACE, MERGE_RUN) for s in seen[1:]), seen
+    assert make.calls == [(0, 0, 3), (1, 1, 5), (0, 0, 5)], make.calls   # the second call inserted actors (two at once) and rewrote the kept ranks
+
+
+def test_last_increment_rank_emulated(emu_lib, monkeypatch):
+    monkeypatch.setenv("AM355_RESORDER_VERIFY", "1")
+    check_last_increment_rank(_emulated(emu_lib))
+
+
+@pytest.mark.gpu
+def test_last_increment_rank_gpu(monkeypatch):
+    monkeypatch.setenv("AM355_RESORDER_VERIFY", "1")
+    check_last_increment_rank(_gpu)
