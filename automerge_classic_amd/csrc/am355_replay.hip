@@ -1007,457 +1007,464 @@ int backend_load_impl(am355_ctx* c, const uint8_t* doc, size_t len) {
 // ---------------------------------------------------------------------------------------------------------
 enum { RESIDENT_FALLBACK = 1 };
 
+// the `lost` counters of the buffers the kept state lives in: what the resident mark remembers and compares
+static void resident_lost(const am355_ctx* c, uint32_t lost[8]) {
+  const uint32_t now[8] = {c->d_cols.lost, c->d_pred.lost, c->d_merge.lost, c->d_metas.lost, c->d_hashes.lost, c->d_ir.lost, c->d_sort.lost, c->h_hashes.lost};
+  memcpy(lost, now, sizeof now);
+}
+
 static void resident_mark(am355_ctx* c) {
   am355_ctx::ResidentMark& m = c->res_mark;
-  const uint32_t lost[8] = {c->d_cols.lost, c->d_pred.lost, c->d_merge.lost, c->d_metas.lost, c->d_hashes.lost, c->d_ir.lost, c->d_sort.lost, c->h_hashes.lost};
-  for (int k = 0; k < 8; k++) m.lost[k] = lost[k];
+  resident_lost(c, m.lost);
   m.n_changes = c->n_changes; m.n_ops = c->n_ops; m.n_preds = c->n_preds;
 }
 
 // none of the buffers the kept state lives in has given its content up since the mark (growing WITH the content -- ensure_keep -- is fine)
 static bool resident_mark_holds(const am355_ctx* c) {
-  const am355_ctx::ResidentMark& m = c->res_mark;
-  const uint32_t lost[8] = {c->d_cols.lost, c->d_pred.lost, c->d_merge.lost, c->d_metas.lost, c->d_hashes.lost, c->d_ir.lost, c->d_sort.lost, c->h_hashes.lost};
-  for (int k = 0; k < 8; k++)
-    if (m.lost[k] != lost[k]) return false;
+  uint32_t lost[8];
+  resident_lost(c, lost);
+  if (memcmp(c->res_mark.lost, lost, sizeof lost) != 0) return false;
   return c->d_cols.p && c->d_merge.p && c->d_metas.p && c->d_hashes.p && c->h_hashes.p;
 }
 
-// hash -> change index over c->h_hashes (open addressing, change index + 1; keyed by eight bytes of the hash, verified by full comparison)
-static inline size_t hash_slot(const uint8_t* h, size_t mask) { uint64_t v; memcpy(&v, h, 8); return (size_t)((v * 0x9e3779b97f4a7c15ull) >> 20) & mask; }
-static void hash_index_add(am355_ctx* c, uint32_t ci) {
-  const uint8_t* hs = c->h_hashes.as<uint8_t>();
-  const size_t mask = c->hash_index.size() - 1;
-  size_t i = hash_slot(hs + 32 * (size_t)ci, mask);
-  while (c->hash_index[i]) i = (i + 1) & mask;
-  c->hash_index[i] = ci + 1;
+// The two host indexes of this path are one kind of table: open addressing over a power of two of words that hold index + 1 (0:
+// empty), probed linearly from the key's hash. Each index brings its own hash (key_of_*: the shifts differ) and its own equality.
+static void table_reset(std::vector<uint32_t>& t, size_t min_cap) {
+  size_t cap = 64;
+  while (cap < min_cap) cap <<= 1;
+  t.assign(cap, 0);
 }
-static uint32_t hash_index_find(const am355_ctx* c, const uint8_t* h) {
-  const uint8_t* hs = (const uint8_t*)c->h_hashes.p;
-  const size_t mask = c->hash_index.size() - 1;
-  for (size_t i = hash_slot(h, mask); c->hash_index[i]; i = (i + 1) & mask)
-    if (memcmp(hs + 32 * (size_t)(c->hash_index[i] - 1), h, 32) == 0) return c->hash_index[i] - 1;
+static void table_add(std::vector<uint32_t>& t, uint64_t key, uint32_t index) {
+  const size_t mask = t.size() - 1;
+  size_t i = (size_t)key & mask;
+  while (t[i]) i = (i + 1) & mask;
+  t[i] = index + 1;
+}
+template <class Same>
+static uint32_t table_find(const std::vector<uint32_t>& t, uint64_t key, Same same) {
+  const size_t mask = t.size() - 1;
+  for (size_t i = (size_t)key & mask; t[i]; i = (i + 1) & mask)
+    if (same(t[i] - 1)) return t[i] - 1;
   return NONE32;
 }
+// hash -> change index over c->h_hashes (keyed by eight bytes of the hash, verified by full comparison)
+static inline uint64_t key_of_hash(const uint8_t* h) { uint64_t v; memcpy(&v, h, 8); return (v * 0x9e3779b97f4a7c15ull) >> 20; }
+static void hash_index_add(am355_ctx* c, uint32_t ci) { table_add(c->hash_index, key_of_hash(c->h_hashes.as<uint8_t>() + 32 * (size_t)ci), ci); }
+static uint32_t hash_index_find(const am355_ctx* c, const uint8_t* h) {
+  const uint8_t* hs = (const uint8_t*)c->h_hashes.p;
+  return table_find(c->hash_index, key_of_hash(h), [&](uint32_t ci) { return memcmp(hs + 32 * (size_t)ci, h, 32) == 0; });
+}
+// actor id -> rank over c->actors, without building a std::string per lookup (a change names dozens of other actors: their table is a lookup each)
+static inline uint64_t key_of_actor(const uint8_t* a, size_t len) {
+  uint64_t v = 0;
+  memcpy(&v, a, len < 8 ? len : 8);
+  return ((v ^ len) * 0x9e3779b97f4a7c15ull) >> 24;
+}
+static uint32_t rank_of(const am355_ctx* c, const uint8_t* a, size_t len) {
+  return table_find(c->res_rank_of, key_of_actor(a, len), [&](uint32_t r) { return c->actors[r].size() == len && memcmp(c->actors[r].data(), a, len) == 0; });
+}
 
-static int replay_resident(am355_ctx* c) {
-  const bool trace = getenv("AM355_TRACE") != nullptr;
-  auto t_begin = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (trace) fprintf(stderr, "resident: %-30s +%8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-  };
-  auto fallback = [&](const char* why) {
-    c->resident_why = why;
-    c->n_resident_fallbacks++;
-    if (trace) fprintf(stderr, "resident: full replay instead (%s)\n", why);
-    return (int)RESIDENT_FALLBACK;
-  };
-  // (once changes of the batch have entered the hash index it no longer describes the applied changes: dropped, rebuilt by the next attempt)
-  auto fallback_dirty = [&](const char* why) { c->hash_index_n = 0; c->hash_index.clear(); return fallback(why); };
-  const uint32_t K = c->keep.n_changes, n = c->n_changes;
-  const uint64_t old_ops = c->keep.n_ops, old_preds = c->keep.n_preds;
-  if (n <= K) return fallback("empty batch");
-  const uint32_t nb = n - K;
-  if (!c->resident_valid || !resident_mark_holds(c) || c->res_mark.n_changes != K || c->res_mark.n_ops != old_ops || c->res_mark.n_preds != old_preds)
-    return fallback("the context's arrays are not the kept state");
-  if (c->shard_world != 1 || c->phase_events || c->graph_mode != 0 || !c->mb.sig) return fallback("mode");
-  if (c->d_metas.cap < sizeof(ChangeMeta) * (size_t)n) return fallback("per-change tables full");   // (am355_load_changes grows it with its content)
+struct ResidentLap {   // AM355_TRACE: the call's milestones on stderr
+  bool on;
+  std::chrono::steady_clock::time_point t0;
+  void operator()(const char* what) const {
+    if (on) fprintf(stderr, "resident: %-30s +%8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  }
+};
+
+// The batch goes to the full replay instead. `fallback` leaves the hash index as it is -- for the sites in front of the first
+// hash_index_add --; `fallback_dirty` drops it: once changes of the batch have entered the hash index it no longer describes the
+// applied changes (rebuilt by the next attempt). Every site keeps the one it has always used.
+static int resident_fallback(am355_ctx* c, const char* why, bool trace) {
+  c->resident_why = why;
+  c->n_resident_fallbacks++;
+  if (trace) fprintf(stderr, "resident: full replay instead (%s)\n", why);
+  return (int)RESIDENT_FALLBACK;
+}
+static int resident_fallback_dirty(am355_ctx* c, const char* why, bool trace) {
+  c->hash_index_n = 0;
+  c->hash_index.clear();
+  return resident_fallback(c, why, trace);
+}
+
+struct Newcomer { const uint8_t* id; uint32_t len, first_change, rank; };   // (id: into c->raw, which no phase touches)
+
+// What the host decides about one batch: lives on the stack of replay_resident, filled phase by phase and handed on by reference;
+// nothing keeps a pointer into it past the call, and it points into no context state that a phase may reallocate (metas: the pinned
+// h_res_metas, sized by resident_parse and left alone behind it). Each group is written by the phase named above it and only read later.
+struct ResidentBatch {
+  // resident_preconditions
+  uint32_t K = 0, n = 0, nb = 0, NA = 0;      // applied changes | staged changes | the batch | actors of the document
+  uint64_t old_ops = 0, old_preds = 0;
+  // resident_parse
+  const ChangeMeta* metas = nullptr;
+  // resident_rank_newcomers
+  std::vector<Newcomer> newcomers;       // the distinct new authors of the batch, sorted once ranked
+  std::vector<uint32_t> remap, old_of;   // old rank -> new rank | new rank -> old rank (NONE32: a newcomer)
+  bool grow = false, rank_moved = false;
+  uint32_t NA2 = 0;                      // actors once the batch is applied
+  // resident_clock_and_heads (sized, seeded from the context), resident_schedule (the batch's part)
+  std::vector<uint64_t> clock;
+  std::vector<uint32_t> new_clock_actors;
+  std::vector<uint8_t> is_head;          // a mark per change index (completed by resident_hashes_and_dependencies)
+  std::vector<ChangePlan> plans;
+  std::vector<uint32_t> amap, op_base;
+  std::vector<std::vector<ActorSpan>> add_spans;
+  uint64_t max_op = 0;
+  uint32_t N = 0, P = 0;
+  int bits_ctr = 0, bits_actor = 0;
+  // resident_build_tables
+  std::vector<ActorSpan> spans_new;
+  std::vector<uint32_t> tab_new;
+  std::vector<std::string> actors_new;
+  std::vector<ChangePlan> plans_dev;     // plans in the decoder's class order: n_small, n_large, then the lane-serial ones
+  uint32_t n_small = 0, n_large = 0;
+  // resident_upload_tables: offsets into c->d_tables
+  size_t o_spans = 0, o_tab = 0, o_x = 0, o_remap = 0;
+  // resident_hashes_and_dependencies
+  std::vector<uint32_t> dep_first, dep_index;
+
+  // the rank an id has once the batch is applied; a newcomer counts from its first change on (a later change of the batch may name it
+  // among its other actors); NONE32: nobody in the document or so far in the batch authored a change under this id
+  uint32_t rank_in_batch(const am355_ctx* c, const uint8_t* a, size_t len, uint32_t change) const {
+    const uint32_t r = rank_of(c, a, len);
+    if (r != NONE32) return grow ? remap[r] : r;
+    for (const Newcomer& w : newcomers)
+      if (w.first_change <= change && w.len == len && memcmp(w.id, a, len) == 0) return w.rank;
+    return NONE32;
+  }
+};
+
+// What the device part binds for the list-order and map-table stages, and what the verdicts behind the commit read of it.
+struct ResidentStages {
+  ResOrderBufs ro{};
+  MapMergeBufs mm{};
+  uint32_t NN = 0, NL_old = 0, NO = 0;   // the batch's rows | list elements, objects of the kept state
+  bool try_resorder = false, final_in_new = true;
+  bool map_merge_on = false, map_merge_fits = false, map_merge_alone = false;
+  bool no_maps_only = false;             // AM355_NO_MAPS_ONLY (tests, A/B: read once per call)
+};
+
+// Phase 1, preconditions. Reads the context; writes the sizes of `rb`, nothing of the context. Returns why the kept state or the mode
+// does not admit the path (-> fallback), nullptr when it does.
+static const char* resident_preconditions(const am355_ctx* c, ResidentBatch& rb) {
+  rb.K = c->keep.n_changes; rb.n = c->n_changes;
+  rb.old_ops = c->keep.n_ops; rb.old_preds = c->keep.n_preds;
+  rb.NA = (uint32_t)c->actors.size();
+  if (rb.n <= rb.K) return "empty batch";
+  rb.nb = rb.n - rb.K;
+  if (!c->resident_valid || !resident_mark_holds(c) || c->res_mark.n_changes != rb.K || c->res_mark.n_ops != rb.old_ops || c->res_mark.n_preds != rb.old_preds)
+    return "the context's arrays are not the kept state";
+  if (c->shard_world != 1 || c->phase_events || c->graph_mode != 0 || !c->mb.sig) return "mode";
+  if (c->d_metas.cap < sizeof(ChangeMeta) * (size_t)rb.n) return "per-change tables full";   // (am355_load_changes grows it with its content)
+  return nullptr;
+}
+
+// Phase 2, the batch parsed on the host: header / column directory / row counts of its changes (the device's own parser,
+// am355_decode.hip parse_change, compiled for the host: no launch, no copy back, no wait). Grows the hash tables with their content
+// and the pinned metas (allocation growth only), writes h_res_metas and rb.metas, queues the metas' upload. AM355_OK or an error.
+static int resident_parse(am355_ctx* c, ResidentBatch& rb) {
+  const uint32_t K = rb.K, n = rb.n, nb = rb.nb;
   if (!c->d_hashes.ensure_keep(32 * (size_t)n, 32 * (size_t)K) || !c->h_hashes.ensure_keep(32 * (size_t)n, 32 * (size_t)K))
     return fail(c, AM355_E_NOMEM, "allocation failed (per-change tables)");
   if (!c->h_res_metas.ensure(sizeof(ChangeMeta) * (size_t)nb)) return fail(c, AM355_E_NOMEM, "host allocation failed");
-  hipStream_t st = c->stream;
-  const uint8_t* raw = c->raw.data();
+  std::vector<uint32_t> ne(nb);
+  parse_changes_host(c->raw.data(), c->raw_off.data() + K, nb, c->h_res_metas.as<ChangeMeta>(), ne.data());
+  rb.metas = c->h_res_metas.as<ChangeMeta>();
+  return queue_upload(c, c->d_metas.as<ChangeMeta>() + K, c->h_res_metas.p, sizeof(ChangeMeta) * (size_t)nb);
+}
 
-  // ---- host: header / column directory / row counts of the batch's changes (the device's own parser, am355_decode.hip parse_change,
-  //      compiled for the host: no launch, no copy back, no wait), and their hashes ----
-  {
-    std::vector<uint32_t> ne(nb);
-    parse_changes_host(raw, c->raw_off.data() + K, nb, c->h_res_metas.as<ChangeMeta>(), ne.data());
-    { int qrc = queue_upload(c, c->d_metas.as<ChangeMeta>() + K, c->h_res_metas.p, sizeof(ChangeMeta) * (size_t)nb); if (qrc) return qrc; }
+// Phase 3, the indexes: the hash index of the applied changes and the id -> rank index with the per-author memo, rebuilt when they
+// do not describe exactly the applied state (after a full replay, a reset, a fallback, an insertion of actors). Reads rb's sizes;
+// writes these three members of the context, which are caches of its state, not state.
+static void resident_indexes(am355_ctx* c, const ResidentBatch& rb) {
+  if (c->hash_index_n != rb.K || c->hash_index.empty() || c->hash_index.size() < 4 * (size_t)rb.n) {
+    table_reset(c->hash_index, 4 * (size_t)rb.n + 64);
+    for (uint32_t i = 0; i < rb.K; i++) hash_index_add(c, i);
+    c->hash_index_n = rb.K;
   }
-  uint8_t* hs = c->h_hashes.as<uint8_t>();
-  std::atomic<int> bad_sum{0};
-  auto hash_one = [&](uint32_t i) {
-    const uint64_t off = c->raw_off[K + i], len = c->raw_off[K + i + 1] - off;
-    if (len < 9) { bad_sum.store(1); return; }
-    sha256_digest(raw + off + 8, (size_t)len - 8, hs + 32 * (size_t)(K + i));     // columnar.js:693-705: over the chunk without magic + checksum
-    if (memcmp(hs + 32 * (size_t)(K + i), raw + off + 4, 4) != 0) bad_sum.store(1);
-  };
-  // (run BEHIND the enqueue of the batch's device work, see below: ~1 us per change of the calling thread's time that the device spends decoding)
-  auto hash_batch = [&]() {
-    if (nb >= 32 && c->pool->size() >= 2) {
-      const unsigned parts = std::min<unsigned>(c->pool->size() + 1, 16u);
-      c->pool->run(parts, [&](unsigned t) { for (uint32_t i = t; i < nb; i += parts) hash_one(i); });
-    } else {
-      for (uint32_t i = 0; i < nb; i++) hash_one(i);
-    }
-    return bad_sum.load() == 0;
-  };
-  lap("batch parsed (host)");
-  // the hash index of the applied changes (rebuilt when it does not describe exactly them: after a full replay, a reset, a fallback)
-  if (c->hash_index_n != K || c->hash_index.empty() || c->hash_index.size() < 4 * (size_t)n) {
-    size_t cap = 64;
-    while (cap < 4 * (size_t)n + 64) cap <<= 1;
-    c->hash_index.assign(cap, 0);
-    for (uint32_t i = 0; i < K; i++) hash_index_add(c, i);
-    c->hash_index_n = K;
+  if (c->res_rank_n != rb.NA || c->res_rank_of.empty()) {
+    table_reset(c->res_rank_of, 4 * (size_t)rb.NA + 16);
+    for (uint32_t r = 0; r < rb.NA; r++) table_add(c->res_rank_of, key_of_actor((const uint8_t*)c->actors[r].data(), c->actors[r].size()), r);
+    c->res_rank_n = rb.NA;
+    c->res_actor_memo.assign(rb.NA, am355_ctx::ActorMemo{});
   }
-  const ChangeMeta* metas = c->h_res_metas.as<ChangeMeta>();
+}
 
-  // ---- host: the in-order schedule of the batch, on copies (committed only when every change passes) ----
-  const uint32_t NA = (uint32_t)c->actors.size();
-  // actor id -> rank without building a std::string per lookup (a change names dozens of other actors: their table is a lookup each)
-  auto actor_slot = [](const uint8_t* a, size_t len, size_t mask) {
-    uint64_t v = 0;
-    memcpy(&v, a, len < 8 ? len : 8);
-    return (size_t)(((v ^ len) * 0x9e3779b97f4a7c15ull) >> 24) & mask;
-  };
-  if (c->res_rank_n != NA || c->res_rank_of.empty()) {
-    size_t cap = 64;
-    while (cap < 4 * (size_t)NA + 16) cap <<= 1;
-    c->res_rank_of.assign(cap, 0);
-    for (uint32_t r = 0; r < NA; r++) {
-      size_t i = actor_slot((const uint8_t*)c->actors[r].data(), c->actors[r].size(), cap - 1);
-      while (c->res_rank_of[i]) i = (i + 1) & (cap - 1);
-      c->res_rank_of[i] = r + 1;
-    }
-    c->res_rank_n = NA;
-    c->res_actor_memo.assign(NA, am355_ctx::ActorMemo{});
-  }
-  auto rank_of = [&](const uint8_t* a, size_t len) -> uint32_t {
-    const size_t mask = c->res_rank_of.size() - 1;
-    for (size_t i = actor_slot(a, len, mask); c->res_rank_of[i]; i = (i + 1) & mask) {
-      const std::string& s = c->actors[c->res_rank_of[i] - 1];
-      if (s.size() == len && memcmp(s.data(), a, len) == 0) return c->res_rank_of[i] - 1;
-    }
-    return NONE32;
-  };
-  // ---- authors the document does not know yet (am355_set_resident_new_actors; without it they take the full replay below): ranked among
-  //      c->actors in the byte order the full replay ranks by (rank_device_actors), on copies -- c->actors and every host table that is
-  //      indexed by a rank or holds one follow with the commit, the ranks the device holds by launch_remap_ranks in front of the decode.
-  //      From here on every rank of the schedule is a rank AFTER the insertion. (What the reference does here: it appends the actor to
-  //      the document's table, new.js:1434-1451 -- its stored ops carry indexes in order of first appearance, not ranks.) ----
-  struct Newcomer { const uint8_t* id; uint32_t len, first_change, rank; };
-  std::vector<Newcomer> newcomers;       // the distinct new authors of the batch, sorted once ranked
-  std::vector<uint32_t> remap, old_of;   // old rank -> new rank | new rank -> old rank (NONE32: a newcomer)
+// Phase 4, authors the document does not know yet (am355_set_resident_new_actors; without it they take the full replay): ranked among
+// c->actors in the byte order the full replay ranks by (rank_device_actors), on copies -- c->actors and every host table that is
+// indexed by a rank or holds one follow with the commit, the ranks the device holds by launch_remap_ranks in front of the decode.
+// From here on every rank of the schedule is a rank AFTER the insertion. (What the reference does here: it appends the actor to
+// the document's table, new.js:1434-1451 -- its stored ops carry indexes in order of first appearance, not ranks.)
+// Reads the context (actors, rank index) and rb.metas; writes rb's insertion group only.
+static void resident_rank_newcomers(const am355_ctx* c, ResidentBatch& rb) {
+  std::vector<Newcomer>& newcomers = rb.newcomers;
+  const uint32_t NA = rb.NA;
   if (c->resident_new_actors) {
     const uint8_t* prev = nullptr;
     uint32_t prev_len = 0;
-    for (uint32_t i = 0; i < nb; i++) {
-      const ChangeMeta& m = metas[i];
+    for (uint32_t i = 0; i < rb.nb; i++) {
+      const ChangeMeta& m = rb.metas[i];
       if (m.flags || (m.pad & 1)) break;   // (the schedule falls back at this change)
-      const uint8_t* a = raw + m.base + m.actor_off;
+      const uint8_t* a = c->raw.data() + m.base + m.actor_off;
       if (prev && prev_len == m.actor_len && memcmp(prev, a, m.actor_len) == 0) continue;
       prev = a; prev_len = m.actor_len;
-      if (rank_of(a, m.actor_len) != NONE32) continue;
+      if (rank_of(c, a, m.actor_len) != NONE32) continue;
       bool seen = false;
       for (const Newcomer& w : newcomers) seen = seen || (w.len == m.actor_len && memcmp(w.id, a, m.actor_len) == 0);
       if (!seen) newcomers.push_back(Newcomer{a, m.actor_len, i, 0});
     }
   }
-  const bool grow = !newcomers.empty();
-  const uint32_t NA2 = NA + (uint32_t)newcomers.size();   // actors once the batch is applied
-  if (grow) {
+  rb.grow = !newcomers.empty();
+  rb.NA2 = NA + (uint32_t)newcomers.size();
+  if (rb.grow) {
     auto id_less = [](const uint8_t* x, size_t xl, const uint8_t* y, size_t yl) {
       const size_t ml = std::min(xl, yl);
       const int r = ml ? memcmp(x, y, ml) : 0;
       return r ? r < 0 : xl < yl;
     };
     std::sort(newcomers.begin(), newcomers.end(), [&](const Newcomer& x, const Newcomer& y) { return id_less(x.id, x.len, y.id, y.len); });
-    remap.resize(NA);
-    old_of.reserve(NA2);
+    rb.remap.resize(NA);
+    rb.old_of.reserve(rb.NA2);
     size_t w = 0;
     for (uint32_t r = 0; r < NA; r++) {
       const std::string& s = c->actors[r];
       for (; w < newcomers.size() && id_less(newcomers[w].id, newcomers[w].len, (const uint8_t*)s.data(), s.size()); w++) {
-        newcomers[w].rank = (uint32_t)old_of.size();
-        old_of.push_back(NONE32);
+        newcomers[w].rank = (uint32_t)rb.old_of.size();
+        rb.old_of.push_back(NONE32);
       }
-      remap[r] = (uint32_t)old_of.size();
-      old_of.push_back(r);
+      rb.remap[r] = (uint32_t)rb.old_of.size();
+      rb.old_of.push_back(r);
     }
-    for (; w < newcomers.size(); w++) { newcomers[w].rank = (uint32_t)old_of.size(); old_of.push_back(NONE32); }
+    for (; w < newcomers.size(); w++) { newcomers[w].rank = (uint32_t)rb.old_of.size(); rb.old_of.push_back(NONE32); }
   }
   // (a monotone renumbering: some kept rank moved iff the last one did -- newcomers that all sort behind every kept actor move none)
-  const bool rank_moved = grow && NA && remap[NA - 1] != NA - 1;
-  // the rank an id has once the batch is applied; a newcomer counts from its first change on (a later change of the batch may name it
-  // among its other actors); NONE32: nobody in the document or so far in the batch authored a change under this id
-  auto rank_in_batch = [&](const uint8_t* a, size_t len, uint32_t change) -> uint32_t {
-    const uint32_t r = rank_of(a, len);
-    if (r != NONE32) return grow ? remap[r] : r;
-    for (const Newcomer& w : newcomers)
-      if (w.first_change <= change && w.len == len && memcmp(w.id, a, len) == 0) return w.rank;
-    return NONE32;
-  };
-  std::vector<uint64_t> clock(NA2, 0);
-  for (size_t k = 0; k < c->clock_actor.size(); k++) clock[grow ? remap[c->clock_actor[k]] : c->clock_actor[k]] = c->clock_seq[k];
-  std::vector<uint32_t> new_clock_actors;
-  // heads as a mark per change index: the document's heads now, minus what the batch depends on, plus the batch
-  std::vector<uint8_t> is_head(n, 0);
+  rb.rank_moved = rb.grow && NA && rb.remap[NA - 1] != NA - 1;
+}
+
+// The document's clock by new rank and its heads as marks, the copies the schedule works on (heads: the document's heads now, minus
+// what the batch depends on, plus the batch). Reads the context, writes rb only. Returns the reason when a head is no applied change:
+// nothing of the batch has entered the hash index yet, so this one is a plain fallback.
+static const char* resident_clock_and_heads(const am355_ctx* c, ResidentBatch& rb) {
+  rb.clock.assign(rb.NA2, 0);
+  for (size_t k = 0; k < c->clock_actor.size(); k++) rb.clock[rb.grow ? rb.remap[c->clock_actor[k]] : c->clock_actor[k]] = c->clock_seq[k];
+  rb.is_head.assign(rb.n, 0);
   for (size_t k = 0; k + 32 <= c->heads.size(); k += 32) {
     const uint32_t hi = hash_index_find(c, &c->heads[k]);
-    if (hi == NONE32) return fallback("a head that is not an applied change");
-    is_head[hi] = 1;
+    if (hi == NONE32) return "a head that is not an applied change";
+    rb.is_head[hi] = 1;
   }
+  return nullptr;
+}
+
+// The table of the other actors of change `i` (meta m, bytes p), as ranks onto rb.amap: the same bytes as in the author's last change
+// -> the same ranks. Reads the context's actors through the rank index; writes rb.amap and the author's memo. Returns the reason or nullptr.
+static const char* resident_other_actors(am355_ctx* c, ResidentBatch& rb, const ChangeMeta& m, const uint8_t* p, uint32_t i, uint32_t author) {
+  // (the memo is indexed by the ranks of c->actors and holds such ranks: a batch that inserts actors goes without it, and the commit drops it)
+  am355_ctx::ActorMemo* memo = rb.grow ? nullptr : &c->res_actor_memo[author];
+  size_t off = m.others_off, end = off;
+  for (uint32_t k = 0; k < m.n_other; k++) {
+    // (actor ids are 16 bytes in practice: a one-byte length, no general LEB128 walk)
+    if (end < m.len && p[end] < 0x80 && (size_t)p[end] < m.len - end) { end += 1 + (size_t)p[end]; continue; }
+    uint64_t l;
+    if (!read_uleb_host(p, m.len, end, l) || l > m.len - end) return "actor table";
+    end += (size_t)l;
+  }
+  const size_t tlen = end - off;
+  if (memo && memo->ranks.size() == m.n_other && memo->bytes.size() == tlen && (tlen == 0 || memcmp(memo->bytes.data(), p + off, tlen) == 0)) {
+    rb.amap.insert(rb.amap.end(), memo->ranks.begin(), memo->ranks.end());
+    return nullptr;
+  }
+  std::vector<uint32_t> ranks;
+  ranks.reserve(m.n_other);
+  size_t o = off;
+  for (uint32_t k = 0; k < m.n_other; k++) {
+    uint64_t l;
+    (void)read_uleb_host(p, m.len, o, l);
+    const uint32_t rk = l <= m.len - o ? rb.rank_in_batch(c, p + o, (size_t)l, i) : NONE32;
+    if (rk == NONE32) return "new actor";
+    ranks.push_back(rk);
+    o += (size_t)l;
+  }
+  rb.amap.insert(rb.amap.end(), ranks.begin(), ranks.end());
+  if (memo) {
+    memo->bytes.assign(p + off, p + end);
+    memo->ranks.swap(ranks);
+  }
+  return nullptr;
+}
+
+// Phase 5, the in-order schedule of the batch (the in-order case of new.js:1550-1597), on copies: committed only when every change
+// passes. Reads the context's actors, spans, capacities; writes rb's schedule group and -- the ONE piece of context state touched
+// before the commit -- the per-author actor memo (a cache: a stale entry costs a memcmp, never a wrong rank, because it is compared
+// by bytes). Returns the reason (-> fallback_dirty, as the loop has always used, although nothing has entered the index yet) or nullptr.
+static const char* resident_schedule(am355_ctx* c, ResidentBatch& rb) {
+  const uint32_t nb = rb.nb;
+  const uint8_t* raw = c->raw.data();
   const uint8_t* prev_author_bytes = nullptr;
   uint32_t prev_author_len = 0, prev_author = 0;
-  std::vector<ChangePlan> plans;
-  std::vector<uint32_t> amap, dep_first(1, 0), dep_index, op_base(nb);
-  plans.reserve(nb); dep_first.reserve(nb + 1); dep_index.reserve(2 * (size_t)nb); amap.reserve(4 * (size_t)nb);
-  std::vector<std::vector<ActorSpan>> add_spans(NA2);
-  uint64_t ops = old_ops, preds = old_preds, max_op = c->max_op;
+  rb.op_base.resize(nb);
+  rb.plans.reserve(nb); rb.amap.reserve(4 * (size_t)nb);
+  rb.add_spans.resize(rb.NA2);
+  uint64_t ops = rb.old_ops, preds = rb.old_preds, max_op = c->max_op;
   for (uint32_t i = 0; i < nb; i++) {
-    const ChangeMeta& m = metas[i];
-    const uint32_t ci = K + i;
-    if (m.flags || (m.pad & 1)) return fallback_dirty("a change the parser flags");
+    const ChangeMeta& m = rb.metas[i];
+    const uint32_t ci = rb.K + i;
+    if (m.flags || (m.pad & 1)) return "a change the parser flags";
     const uint8_t* p = raw + m.base;
     // actor table: author + the others, all known to the document (a new actor changes the ranks of the kept rows: full replay, unless
-    // the context inserts new authors -- `newcomers` above)
+    // the context inserts new authors -- rb.newcomers)
     // (a run of changes by one author -- a peer's backlog, a typing session -- looks its rank up once)
     uint32_t author;
     if (prev_author_bytes && prev_author_len == m.actor_len && memcmp(prev_author_bytes, p + m.actor_off, m.actor_len) == 0) author = prev_author;
     else {
-      author = rank_in_batch(p + m.actor_off, m.actor_len, i);
-      if (author == NONE32) return fallback_dirty("new actor");
+      author = rb.rank_in_batch(c, p + m.actor_off, m.actor_len, i);
+      if (author == NONE32) return "new actor";
       prev_author_bytes = p + m.actor_off; prev_author_len = m.actor_len; prev_author = author;
     }
-    ChangePlan pl{ci, (uint32_t)ops, (uint32_t)preds, (uint32_t)amap.size(), author, 1 + m.n_other};
-    if (pl.n_actors != m.n_entries) return fallback_dirty("actor table");
-    amap.push_back(author);
-    {
-      // the table of the other actors: the same bytes as in the author's last change -> the same ranks
-      // (the memo is indexed by the ranks of c->actors and holds such ranks: a batch that inserts actors goes without it, and the commit drops it)
-      am355_ctx::ActorMemo* memo = grow ? nullptr : &c->res_actor_memo[author];
-      size_t off = m.others_off, end = off;
-      for (uint32_t k = 0; k < m.n_other; k++) {
-        // (actor ids are 16 bytes in practice: a one-byte length, no general LEB128 walk)
-        if (end < m.len && p[end] < 0x80 && (size_t)p[end] < m.len - end) { end += 1 + (size_t)p[end]; continue; }
-        uint64_t l;
-        if (!read_uleb_host(p, m.len, end, l) || l > m.len - end) return fallback_dirty("actor table");
-        end += (size_t)l;
-      }
-      const size_t tlen = end - off;
-      if (memo && memo->ranks.size() == m.n_other && memo->bytes.size() == tlen && (tlen == 0 || memcmp(memo->bytes.data(), p + off, tlen) == 0)) {
-        amap.insert(amap.end(), memo->ranks.begin(), memo->ranks.end());
-      } else {
-        std::vector<uint32_t> ranks;
-        ranks.reserve(m.n_other);
-        size_t o = off;
-        for (uint32_t k = 0; k < m.n_other; k++) {
-          uint64_t l;
-          (void)read_uleb_host(p, m.len, o, l);
-          const uint32_t rk = l <= m.len - o ? rank_in_batch(p + o, (size_t)l, i) : NONE32;
-          if (rk == NONE32) return fallback_dirty("new actor");
-          ranks.push_back(rk);
-          o += (size_t)l;
-        }
-        amap.insert(amap.end(), ranks.begin(), ranks.end());
-        if (memo) {
-          memo->bytes.assign(p + off, p + end);
-          memo->ranks.swap(ranks);
-        }
-      }
-    }
-    if (m.seq != clock[author] + 1) return fallback_dirty("sequence number");
-    if (clock[author] == 0) new_clock_actors.push_back(author);
-    clock[author] = m.seq;
-    op_base[i] = (uint32_t)ops;
+    ChangePlan pl{ci, (uint32_t)ops, (uint32_t)preds, (uint32_t)rb.amap.size(), author, 1 + m.n_other};
+    if (pl.n_actors != m.n_entries) return "actor table";
+    rb.amap.push_back(author);
+    if (const char* why = resident_other_actors(c, rb, m, p, i, author)) return why;
+    if (m.seq != rb.clock[author] + 1) return "sequence number";
+    if (rb.clock[author] == 0) rb.new_clock_actors.push_back(author);
+    rb.clock[author] = m.seq;
+    rb.op_base[i] = (uint32_t)ops;
     if (m.n_ops) {
       // the change's op ids lie behind every id of its author so far (ascending, disjoint spans: what plan_fast verifies)
-      const uint32_t kept = grow ? old_of[author] : author;   // (the context's span tables go by the ranks before the batch; a newcomer has no span yet)
+      const uint32_t kept = rb.grow ? rb.old_of[author] : author;   // (the context's span tables go by the ranks before the batch; a newcomer has no span yet)
       const uint32_t a0 = kept == NONE32 ? 0 : c->actor_tab_off[kept], a1 = kept == NONE32 ? 0 : c->actor_tab_off[kept + 1];
       uint64_t last_end = a1 > a0 ? (uint64_t)c->spans[a1 - 1].start_op + c->spans[a1 - 1].n_ops : 0;
-      if (!add_spans[author].empty()) last_end = (uint64_t)add_spans[author].back().start_op + add_spans[author].back().n_ops;
-      if (m.start_op < last_end || m.start_op + m.n_ops > 0xfffffff0ull) return fallback_dirty("op id range");
-      add_spans[author].push_back(ActorSpan{(uint32_t)m.start_op, m.n_ops, (uint32_t)ops});
+      std::vector<ActorSpan>& mine = rb.add_spans[author];
+      if (!mine.empty()) last_end = (uint64_t)mine.back().start_op + mine.back().n_ops;
+      if (m.start_op < last_end || m.start_op + m.n_ops > 0xfffffff0ull) return "op id range";
+      mine.push_back(ActorSpan{(uint32_t)m.start_op, m.n_ops, (uint32_t)ops});
       max_op = std::max<uint64_t>(max_op, m.start_op + m.n_ops - 1);
-      plans.push_back(pl);
+      rb.plans.push_back(pl);
     }
     ops += m.n_ops;
     preds += m.n_preds;
-    if (ops >= 0x7ffffff0ull || preds >= 0xfffffff0ull) return fallback_dirty("size");
+    if (ops >= 0x7ffffff0ull || preds >= 0xfffffff0ull) return "size";
   }
-  const uint32_t N = (uint32_t)ops, P = (uint32_t)preds;
-  if (N > c->cols_cap_ops || P > c->cols_cap_preds || (size_t)N + 1 > c->mb.row_stride) return fallback_dirty("row capacity");
-  const int bits_ctr = bits_for64(max_op), bits_actor = bits_for64(NA2 ? NA2 - 1 : 0), bits_row = bits_for64(N);
-  if (1 + bits_row + bits_ctr + bits_actor > 64) return fallback_dirty("sort key width");
-  lap("batch scheduled (host)");
+  rb.N = (uint32_t)ops; rb.P = (uint32_t)preds; rb.max_op = max_op;
+  if (rb.N > c->cols_cap_ops || rb.P > c->cols_cap_preds || (size_t)rb.N + 1 > c->mb.row_stride) return "row capacity";
+  rb.bits_ctr = bits_for64(max_op); rb.bits_actor = bits_for64(rb.NA2 ? rb.NA2 - 1 : 0);
+  if (1 + bits_for64(rb.N) + rb.bits_ctr + rb.bits_actor > 64) return "sort key width";
+  return nullptr;
+}
 
-  // ---- the batch's hashes, and what depends on them: not a duplicate, every dependency an applied change (a change of this batch in
-  //      front counts), the heads. Run BEHIND the enqueue of the batch's device work (decode, resolution, list order): SHA-256 of a
-  //      3 KB change is ~1.5 us of the calling thread -- 40 changes 60 us with the lookups -- which the device spends on the batch anyway.
-  //      A batch that fails here has changed the kept arrays: the full replay that follows starts from the staged bytes, as it does
-  //      after any failure. Returns the reason, nullptr when the batch passes. ----
-  auto hashes_and_dependencies = [&]() -> const char* {
-    if (!hash_batch()) return "checksum";
-    const uint8_t* prev_deps = nullptr;   // the dependency block of the change in front (a round of synced peers shares it): resolved once
-    uint32_t prev_n_deps = 0, prev_first = 0;
-    for (uint32_t i = 0; i < nb; i++) {
-      const ChangeMeta& m = metas[i];
-      const uint32_t ci = K + i;
-      const uint8_t* p = raw + m.base;
-      if (hash_index_find(c, hs + 32 * (size_t)ci) != NONE32) return "duplicate change";
-      const uint8_t* deps = p + m.deps_off;
-      if (prev_deps && prev_n_deps == m.n_deps && m.n_deps && memcmp(prev_deps, deps, 32 * (size_t)m.n_deps) == 0) {
-        for (uint32_t k = 0; k < m.n_deps; k++) dep_index.push_back(dep_index[prev_first + k]);   // (their head marks are already down)
-      } else {
-        for (uint32_t k = 0; k < m.n_deps; k++) {
-          const uint32_t di = hash_index_find(c, deps + 32 * (size_t)k);
-          if (di == NONE32) return "dependency not applied yet";
-          dep_index.push_back(di);
-          is_head[di] = 0;
-        }
-      }
-      prev_deps = deps; prev_n_deps = m.n_deps; prev_first = dep_first.back();
-      dep_first.push_back((uint32_t)dep_index.size());
-      is_head[ci] = 1;
-      hash_index_add(c, ci);   // (undone by dropping the index when a later change fails)
-    }
-    return nullptr;
-  };
-  // the per-actor op-id spans with the batch's (what the device tables hold from this call on; the context's copy follows with the commit)
-  std::vector<ActorSpan> spans_new;
-  std::vector<uint32_t> tab_new(NA2 + 1, 0);
-  spans_new.reserve(c->spans.size() + plans.size());
-  for (uint32_t a = 0; a < NA2; a++) {
-    tab_new[a] = (uint32_t)spans_new.size();
-    const uint32_t kept = grow ? old_of[a] : a;   // (a newcomer: an empty slot, then its spans of the batch)
-    if (kept != NONE32) spans_new.insert(spans_new.end(), c->spans.begin() + c->actor_tab_off[kept], c->spans.begin() + c->actor_tab_off[kept + 1]);
-    spans_new.insert(spans_new.end(), add_spans[a].begin(), add_spans[a].end());
+// Phase 6, the new tables, on the host: the per-actor op-id spans with the batch's (what the device tables hold from this call on; the
+// context's copy follows with the commit), the actor table after the insertion, and the plans in the decoder's class order. Reads
+// the context's spans and actors; writes rb's table group only.
+static void resident_build_tables(const am355_ctx* c, ResidentBatch& rb) {
+  rb.tab_new.assign(rb.NA2 + 1, 0);
+  rb.spans_new.reserve(c->spans.size() + rb.plans.size());
+  for (uint32_t a = 0; a < rb.NA2; a++) {
+    rb.tab_new[a] = (uint32_t)rb.spans_new.size();
+    const uint32_t kept = rb.grow ? rb.old_of[a] : a;   // (a newcomer: an empty slot, then its spans of the batch)
+    if (kept != NONE32) rb.spans_new.insert(rb.spans_new.end(), c->spans.begin() + c->actor_tab_off[kept], c->spans.begin() + c->actor_tab_off[kept + 1]);
+    rb.spans_new.insert(rb.spans_new.end(), rb.add_spans[a].begin(), rb.add_spans[a].end());
   }
-  tab_new[NA2] = (uint32_t)spans_new.size();
-  std::vector<std::string> actors_new;
-  if (grow) {
-    actors_new.resize(NA2);
-    for (uint32_t r = 0; r < NA; r++) actors_new[remap[r]] = c->actors[r];
-    for (const Newcomer& w : newcomers) actors_new[w.rank].assign((const char*)w.id, w.len);
+  rb.tab_new[rb.NA2] = (uint32_t)rb.spans_new.size();
+  if (rb.grow) {
+    rb.actors_new.resize(rb.NA2);
+    for (uint32_t r = 0; r < rb.NA; r++) rb.actors_new[rb.remap[r]] = c->actors[r];
+    for (const Newcomer& w : rb.newcomers) rb.actors_new[w.rank].assign((const char*)w.id, w.len);
   }
-  std::vector<ChangePlan> plans_dev = plans;   // (in the decoder's class order below)
-  // ---- commit the host state (once the batch has passed every check) ----
-  auto commit_host_state = [&]() {
-    c->hash_index_n = n;
-    if (grow) {
-      // every host table that is indexed by a rank or holds one: the actors, the clock's actors (below: the clock itself and the span
-      // tables, built by new rank above), the rank of a loaded document's actor indexes (read by am355_save / am355_doc_changes of a
-      // document context only, which never comes here: kept in step all the same), the id -> rank index and the per-author memo of
-      // this path (rebuilt by the next call). c->plans / c->amap are this batch's, by new rank; am355_save ranks and inverts per call.
-      c->actors.swap(actors_new);
-      for (uint32_t& a : c->clock_actor) a = remap[a];
-      if (c->doc_actor_rank.size() == NA)
-        for (uint32_t& r : c->doc_actor_rank) if (r < NA) r = remap[r];
-      c->res_rank_of.clear();
-      c->res_rank_n = 0;
-      c->res_actor_memo.clear();
-      if (rank_moved) {
-        // the host copies of the object and map tables hold the ranks from before: the in-place branch below must not take them for current
-        c->h_tables_current = c->h_tables_were_current = false;
-        c->ir_copy_enqueued = 0;
-      }
-    }
-    for (uint32_t a : new_clock_actors) c->clock_actor.push_back(a);
-    c->clock_seq.clear();
-    for (uint32_t a : c->clock_actor) c->clock_seq.push_back(clock[a]);
-    {
-      std::vector<const uint8_t*> hv;
-      for (uint32_t i = 0; i < n; i++)
-        if (is_head[i]) hv.push_back(hs + 32 * (size_t)i);
-      std::sort(hv.begin(), hv.end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; });
-      std::vector<uint8_t> heads_new(hv.size() * 32);
-      for (size_t k = 0; k < hv.size(); k++) memcpy(&heads_new[32 * k], hv[k], 32);
-      c->heads.swap(heads_new);
-    }
-    c->spans.swap(spans_new);
-    c->actor_tab_off.swap(tab_new);
-    for (uint32_t i = 0; i < nb; i++) { c->applied_change.push_back(K + i); c->applied_op_base.push_back(op_base[i]); }
-    if (c->res_dep_first.empty()) c->res_dep_first.assign(1, 0);
-    for (uint32_t i = 0; i < nb; i++) {
-      c->res_dep_index.insert(c->res_dep_index.end(), dep_index.begin() + dep_first[i], dep_index.begin() + dep_first[i + 1]);
-      c->res_dep_first.push_back((uint32_t)c->res_dep_index.size());
-    }
-    c->n_applied = n; c->n_pending = 0;
-    c->pending_change.clear();
-    c->pass_first_row.clear();
-    c->n_ops = N; c->n_preds = P; c->max_op = max_op;
-    c->has_unknown_cols = false;
-    c->plans.swap(plans_dev);
-    c->amap = amap;
-  };
+  std::vector<ChangePlan>& pd = rb.plans_dev;
+  pd = rb.plans;
+  std::vector<ChangePlan> large, serial;
+  size_t w = 0;
+  for (size_t i = 0; i < pd.size(); i++) {
+    const int wc = change_wave_class(rb.metas[pd[i].change - rb.K]);
+    if (wc == 2) pd[w++] = pd[i];
+    else if (wc == 1) large.push_back(pd[i]);
+    else serial.push_back(pd[i]);
+  }
+  rb.n_small = (uint32_t)w;
+  rb.n_large = (uint32_t)large.size();
+  for (auto& pl : large) pd[w++] = pl;
+  for (auto& pl : serial) pd[w++] = pl;
+}
 
-  // ---- device: tables, the batch's rows, their resolution, then the whole-document order / patch tables ----
-  const size_t np = plans.size();
+// Phase 7, the tables staged in pinned memory and queued for the upload: plans | spans | span offsets | actor map | (old rank -> new
+// rank, for launch_remap_ranks). Reads rb; writes rb's offsets, grows d_tables / h_stage, points p_spans / p_tab_off into d_tables
+// and takes the call's signal sequence number. AM355_OK or an error.
+static int resident_upload_tables(am355_ctx* c, ResidentBatch& rb) {
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_plans = sizeof(ChangePlan) * np, b_spans = sizeof(ActorSpan) * spans_new.size(), b_tab = 4 * tab_new.size(), b_amap = 4 * amap.size();
-  const size_t b_remap = rank_moved ? 4 * (size_t)NA : 0;   // (old rank -> new rank, for launch_remap_ranks)
-  const size_t o_spans = al(b_plans + 16), o_tab = o_spans + al(b_spans + 16), o_x = o_tab + al(b_tab + 16), o_remap = o_x + al(b_amap + 16),
-               tables_bytes = o_remap + al(b_remap + 16);
+  const size_t b_plans = sizeof(ChangePlan) * rb.plans_dev.size(), b_spans = sizeof(ActorSpan) * rb.spans_new.size(), b_tab = 4 * rb.tab_new.size(),
+               b_amap = 4 * rb.amap.size(), b_remap = rb.rank_moved ? 4 * (size_t)rb.NA : 0;
+  rb.o_spans = al(b_plans + 16); rb.o_tab = rb.o_spans + al(b_spans + 16); rb.o_x = rb.o_tab + al(b_tab + 16); rb.o_remap = rb.o_x + al(b_amap + 16);
+  const size_t tables_bytes = rb.o_remap + al(b_remap + 16);
   if (!c->d_tables.ensure(tables_bytes) || !c->h_stage.ensure(tables_bytes)) return fail(c, AM355_E_NOMEM, "device allocation failed");
   uint8_t* d_tables = c->d_tables.as<uint8_t>();
-  c->p_spans = (ActorSpan*)(d_tables + o_spans);
-  c->p_tab_off = (uint32_t*)(d_tables + o_tab);
+  c->p_spans = (ActorSpan*)(d_tables + rb.o_spans);
+  c->p_tab_off = (uint32_t*)(d_tables + rb.o_tab);
   c->sig_seq++;
-  uint32_t n_small = 0, n_large = 0;
-  {
-    std::vector<ChangePlan> large, serial;
-    size_t w = 0;
-    for (size_t i = 0; i < np; i++) {
-      const int wc = change_wave_class(metas[plans_dev[i].change - K]);
-      if (wc == 2) plans_dev[w++] = plans_dev[i];
-      else if (wc == 1) large.push_back(plans_dev[i]);
-      else serial.push_back(plans_dev[i]);
-    }
-    n_small = (uint32_t)w;
-    n_large = (uint32_t)large.size();
-    for (auto& pl : large) plans_dev[w++] = pl;
-    for (auto& pl : serial) plans_dev[w++] = pl;
-  }
-  {
-    uint8_t* h = c->h_stage.as<uint8_t>();
-    if (b_plans) memcpy(h, plans_dev.data(), b_plans);
-    if (b_spans) memcpy(h + o_spans, spans_new.data(), b_spans);
-    memcpy(h + o_tab, tab_new.data(), b_tab);
-    if (b_amap) memcpy(h + o_x, amap.data(), b_amap);
-    if (b_remap) memcpy(h + o_remap, remap.data(), b_remap);
-    { int qrc = queue_upload(c, d_tables, h, b_remap ? o_remap + b_remap : o_x + b_amap); if (qrc) return qrc; }
-  }
+  uint8_t* h = c->h_stage.as<uint8_t>();
+  if (b_plans) memcpy(h, rb.plans_dev.data(), b_plans);
+  if (b_spans) memcpy(h + rb.o_spans, rb.spans_new.data(), b_spans);
+  memcpy(h + rb.o_tab, rb.tab_new.data(), b_tab);
+  if (b_amap) memcpy(h + rb.o_x, rb.amap.data(), b_amap);
+  if (b_remap) memcpy(h + rb.o_remap, rb.remap.data(), b_remap);
+  return queue_upload(c, d_tables, h, b_remap ? rb.o_remap + b_remap : rb.o_x + b_amap);
+}
+
+// Phase 8, the merge buffers bound to the state with the batch (c->mb; row_stride stays as the last full replay carved the arrays).
+// Reads rb; writes c->mb and grows d_counts. AM355_OK or an error.
+static int resident_bind_merge(am355_ctx* c, const ResidentBatch& rb) {
   MergeBufs& b = c->mb;
   b.arena = c->d_arena.as<uint8_t>();
   b.ops = c->cols;
-  b.n_ops = N; b.n_preds = P; b.n_actors = NA2;
+  b.n_ops = rb.N; b.n_preds = rb.P; b.n_actors = rb.NA2;
   b.sig = c->h_sig.as<HostSignals>(); b.sig_seq = c->sig_seq;
   b.actor_tab_off = c->p_tab_off; b.spans = c->p_spans;
-  b.bits_ctr = (uint32_t)bits_ctr; b.bits_actor = (uint32_t)bits_actor;
-  b.first_row = (uint32_t)old_ops; b.seed_list_inc = c->seed_list_inc;   // (b.row_stride: as the last full replay carved the arrays)
-  if (!c->d_counts.ensure(merge_counts_bytes(N))) return fail(c, AM355_E_NOMEM, "device allocation failed (merge)");
+  b.bits_ctr = (uint32_t)rb.bits_ctr; b.bits_actor = (uint32_t)rb.bits_actor;
+  b.first_row = (uint32_t)rb.old_ops; b.seed_list_inc = c->seed_list_inc;
+  if (!c->d_counts.ensure(merge_counts_bytes(rb.N))) return fail(c, AM355_E_NOMEM, "device allocation failed (merge)");
   merge_bind_counts(b, c->d_counts.p);
-  // ---- list order: a batch of plain list edits is merged into the STORED order (am355_resorder.hip); anything else -- map rows, new
-  //      objects, a new element with two new children -- orders every list anew with the kernels of merge_run. Its buffers are bound here:
-  //      their clears ride with the fill of the new rows' accumulators ----
+  return AM355_OK;
+}
+
+// Phase 9, list order: a batch of plain list edits is merged into the STORED order (am355_resorder.hip); anything else -- map rows, new
+// objects, a new element with two new children -- orders every list anew with the kernels of merge_run. Its buffers are bound here:
+// their clears ride with the fill of the new rows' accumulators. Reads rb and the context's counts; writes rs and grows / sets up
+// the stage's buffers (d_order_alt, d_pos, d_resorder, h_resorder). AM355_OK or an error.
+static int resident_bind_list_order(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs) {
   static const bool no_resorder = getenv("AM355_NO_RESORDER") != nullptr;
-  const uint32_t NN = N - (uint32_t)old_ops, NL_old = c->counts.n_list_ins, NO = c->counts.n_objects;
-  const bool try_resorder = !no_resorder && NN && NN <= resorder_chunk_rows() * (resorder_chunk_rows() < RESORDER_ROWS_MAX ? 64u : RESORDER_CHUNKS_MAX) &&   // (tests' small chunks: many of them)
-                             NL_old && c->mb.row_stride;
-  ResOrderBufs ro{};
-  if (try_resorder) {
-    const size_t cap_rows = c->mb.row_stride;
-    // (the order lives in one of two arrays of row_stride + 2 words -- the one carved with the merge arrays and c->d_order_alt --, and
-    // every in-place merge writes the other one; a new carve, setup_buffers, starts over)
-    if (!c->order_alt_ptr) {
-      if (!c->d_order_alt.ensure(4 * (cap_rows + 2))) return fail(c, AM355_E_NOMEM, "device allocation failed (resident list order)");
-      c->order_alt_ptr = c->d_order_alt.as<uint32_t>();
-    }
-    if (!c->d_pos.ensure_keep(4 * cap_rows, c->pos_valid ? 4 * (size_t)old_ops : 0) || !c->d_resorder.ensure(resorder_bytes(NN, NO)) || !c->h_resorder.ensure(64))
-      return fail(c, AM355_E_NOMEM, "device allocation failed (resident list order)");
-    resorder_bind(ro, c->d_resorder.p, NN, NO);
-    canary_arm();   // (AM355_CANARY=1 only)
-    ro.T0 = (uint32_t)old_ops; ro.n_new = NN; ro.n_list = NL_old; ro.n_obj = NO;
-    ro.pos_of = c->d_pos.as<uint32_t>();
-    ro.order_new = c->order_alt_ptr;
-    ro.sig = b.sig; ro.sig_seq = b.sig_seq;
-    ro.allow_maps = getenv("AM355_NO_MAPS_ONLY") ? 0u : 1u;   // (tests, A/B: read per call)
+  const uint32_t NN = rs.NN = rb.N - (uint32_t)rb.old_ops;
+  rs.NL_old = c->counts.n_list_ins; rs.NO = c->counts.n_objects;
+  rs.try_resorder = !no_resorder && NN && NN <= resorder_chunk_rows() * (resorder_chunk_rows() < RESORDER_ROWS_MAX ? 64u : RESORDER_CHUNKS_MAX) &&   // (tests' small chunks: many of them)
+                    rs.NL_old && c->mb.row_stride;
+  if (!rs.try_resorder) return AM355_OK;
+  ResOrderBufs& ro = rs.ro;
+  const size_t cap_rows = c->mb.row_stride;
+  // (the order lives in one of two arrays of row_stride + 2 words -- the one carved with the merge arrays and c->d_order_alt --, and
+  // every in-place merge writes the other one; a new carve, setup_buffers, starts over)
+  if (!c->order_alt_ptr) {
+    if (!c->d_order_alt.ensure(4 * (cap_rows + 2))) return fail(c, AM355_E_NOMEM, "device allocation failed (resident list order)");
+    c->order_alt_ptr = c->d_order_alt.as<uint32_t>();
   }
-  c->resident_valid = false;   // (from here on the kept arrays change: a failure leaves no state behind)
-  { int frc = flush_uploads(c); if (frc) return frc; }   // (the batch's bytes, its records, the tables, the delta stage's breaks: one launch; its hashes follow)
-  if (rank_moved) {
+  if (!c->d_pos.ensure_keep(4 * cap_rows, c->pos_valid ? 4 * (size_t)rb.old_ops : 0) || !c->d_resorder.ensure(resorder_bytes(NN, rs.NO)) || !c->h_resorder.ensure(64))
+    return fail(c, AM355_E_NOMEM, "device allocation failed (resident list order)");
+  resorder_bind(ro, c->d_resorder.p, NN, rs.NO);
+  canary_arm();   // (AM355_CANARY=1 only)
+  ro.T0 = (uint32_t)rb.old_ops; ro.n_new = NN; ro.n_list = rs.NL_old; ro.n_obj = rs.NO;
+  ro.pos_of = c->d_pos.as<uint32_t>();
+  ro.order_new = c->order_alt_ptr;
+  ro.sig = c->mb.sig; ro.sig_seq = c->mb.sig_seq;
+  ro.allow_maps = rs.no_maps_only ? 0u : 1u;
+  return AM355_OK;
+}
+
+// Phases 11-13, the first launches that write kept arrays (the caller has dropped resident_valid and flushed the uploads): the ranks
+// the kept state holds rewritten, the fills, the batch's decode -- forked onto the third stream and joined where that pays. Reads rb,
+// rs; writes device memory only. AM355_OK or an error.
+static int resident_decode(am355_ctx* c, const ResidentBatch& rb, const ResidentStages& rs) {
+  hipStream_t st = c->stream;
+  MergeBufs& b = c->mb;
+  const uint8_t* d_tables = c->d_tables.as<uint8_t>();
+  if (rb.rank_moved) {
     // the ranks the kept state holds, renumbered in front of the batch's decode (whose rows come with ranks after the insertion): the
     // actor columns of the kept rows and preds; the op id a counter's last increment left (last_inc: counter << 32 | rank, 0 where no
     // increment came); the op ids in the object table (not _root's, which means nothing) and in the map records -- a batch merged in
@@ -1465,41 +1472,350 @@ static int replay_resident(am355_ctx* c) {
     // (c->ir_stale: ensure_ir_fresh rebuilds it from the rows before anybody reads it). A batch that fails behind this (hashes,
     // dependencies) takes the full replay, which ranks the actors and fills every one of these arrays anew from the staged bytes.
     RemapRanges rr;
-    bool fits = rr.add(c->cols.obj_actor, old_ops) && rr.add(c->cols.key_actor, old_ops) && rr.add(c->cols.id_actor, old_ops) && rr.add(c->cols.pred_actor, old_preds);
-    fits = fits && rr.add((uint32_t*)b.last_inc, old_ops, 2, 1, 0);
+    bool fits = rr.add(c->cols.obj_actor, rb.old_ops) && rr.add(c->cols.key_actor, rb.old_ops) && rr.add(c->cols.id_actor, rb.old_ops) && rr.add(c->cols.pred_actor, rb.old_preds);
+    fits = fits && rr.add((uint32_t*)b.last_inc, rb.old_ops, 2, 1, 0);
     fits = fits && rr.add(&c->ir.obj->id_actor, c->counts.n_objects, (uint32_t)(sizeof(am355_ir_object) / 4),
                           (int32_t)(offsetof(am355_ir_object, make_row) / 4) - (int32_t)(offsetof(am355_ir_object, id_actor) / 4), NONE32);
     fits = fits && rr.add(&c->ir.map->id_actor, c->counts.n_map_emit, (uint32_t)(sizeof(am355_ir_map) / 4));
     if (!fits) return fail(c, AM355_E_DEVICE, "rank rewrite: more ranges than one launch takes");
-    launch_remap_ranks(rr, (const uint32_t*)(d_tables + o_remap), NA, st);
+    launch_remap_ranks(rr, (const uint32_t*)(d_tables + rb.o_remap), rb.NA, st);
   }
-  {
-    FillRanges extra;
-    extra.add(c->d_counts.p, b.counts_bytes, 0);
-    if (try_resorder) extra.add(ro.obj_add, (size_t)((uint8_t*)(ro.words + 8) - (uint8_t*)ro.obj_add), 0);   // obj_add | words (neighbours in the block, resorder_bind)
-    if (!merge_prepare(b, st, MERGE_FILL_ROWS, &extra)) return fail(c, AM355_E_DEVICE, "merge fills: more ranges than one launch takes");   // (the new rows' accumulators; in this stream: the decode of a small batch is too short to hide a second stream's join)
-  }
+  FillRanges extra;
+  extra.add(c->d_counts.p, b.counts_bytes, 0);
+  if (rs.try_resorder) extra.add(rs.ro.obj_add, (size_t)((uint8_t*)(rs.ro.words + 8) - (uint8_t*)rs.ro.obj_add), 0);   // obj_add | words (neighbours in the block, resorder_bind)
+  if (!merge_prepare(b, st, MERGE_FILL_ROWS, &extra)) return fail(c, AM355_E_DEVICE, "merge fills: more ranges than one launch takes");   // (the new rows' accumulators; in this stream: the decode of a small batch is too short to hide a second stream's join)
   // (launch_decode_columns puts a class on the second stream only when the small class and the lane-serial one are both there and no
   // large one: a handful of changes otherwise decode in ONE launch on `st`, and the fork / join would be four runtime calls for nothing)
-  const uint32_t n_serial = (uint32_t)np - n_small - n_large;
+  const uint32_t n_small = rb.n_small, n_large = rb.n_large, n_serial = (uint32_t)rb.plans_dev.size() - n_small - n_large;
   const bool second_stream = n_small && n_serial && !(n_large && n_small + n_large <= 1024);
   if (second_stream) {
     HIPCHK(c, hipEventRecord(c->ev_fork, st));
     HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_fork, 0));
   }
   launch_decode_columns(c->d_arena.as<uint8_t>(), c->d_metas.as<ChangeMeta>(), (const ChangePlan*)d_tables, n_small, n_large, n_serial,
-                        (const uint32_t*)(d_tables + o_x), nullptr, c->cols, &c->d_counts.as<Counts>()->flags, st, second_stream ? c->stream3.h : nullptr, 0, 1);
+                        (const uint32_t*)(d_tables + rb.o_x), nullptr, c->cols, &c->d_counts.as<Counts>()->flags, st, second_stream ? c->stream3.h : nullptr, 0, 1);
   if (second_stream) {
     HIPCHK(c, hipEventRecord(c->ev_join, c->stream3));
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_join, 0));
   }
-  lap("decode enqueued");
+  return AM355_OK;
+}
+
+// The first half of the map merge (am355_merge.h MapMergeBufs): binds rs.mm to the stored table and its scratch and enqueues
+// mapmerge_find, which reads the stored table and writes scratch only. Sets the other map table up on first use. AM355_OK or an error.
+static int resident_map_find(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs) {
+  MapMergeBufs& mm = rs.mm;
+  const uint32_t n_map = c->counts.n_map_emit, n_obj = c->counts.n_objects;
+  if (!c->map_alt_ptr) {
+    if (!c->d_map_alt.ensure(sizeof(am355_ir_map) * (size_t)c->mb.row_stride)) return fail(c, AM355_E_NOMEM, "device allocation failed (resident map table)");
+    c->map_alt_ptr = c->d_map_alt.as<am355_ir_map>();
+  }
+  if (!c->d_mapmerge.ensure(mapmerge_bytes(rs.NN, n_map, n_obj))) return fail(c, AM355_E_NOMEM, "device allocation failed (resident map table)");
+  mapmerge_bind(mm, c->d_mapmerge.p, rs.NN, n_map, n_obj);
+  mm.T0 = (uint32_t)rb.old_ops;
+  mm.map = c->ir.map; mm.map_new = c->map_alt_ptr;
+  mm.sig = c->mb.sig; mm.sig_seq = c->mb.sig_seq;
+  mapmerge_find(c->mb, c->ir, mm, c->stream);
+  return AM355_OK;
+}
+
+// AM355_MAPMERGE_VERIFY (tests): the table just merged in place against merge_run_maps' table of the same rows, record by record,
+// and the objects' map ranges. Leaves the table from scratch in place (the same, or the call fails).
+static int resident_map_verify(am355_ctx* c, const MapMergeBufs& mm, uint32_t n_after, bool trace) {
+  hipStream_t st = c->stream;
   Counts* hc = c->h_counts.as<Counts>();
+  std::vector<am355_ir_map> got(n_after), want(n_after);
+  std::vector<am355_ir_object> got_obj(mm.n_obj), want_obj(mm.n_obj);
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (n_after) HIPCHK(c, hipMemcpy(got.data(), c->ir.map, sizeof(am355_ir_map) * (size_t)n_after, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(got_obj.data(), c->ir.obj, sizeof(am355_ir_object) * (size_t)mm.n_obj, hipMemcpyDeviceToHost));
+  merge_run_maps(c->mb, c->ir, hc, st);
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
+  bool same = hc->n_map_emit == n_after;
+  if (same) {
+    if (n_after) HIPCHK(c, hipMemcpy(want.data(), c->ir.map, sizeof(am355_ir_map) * (size_t)n_after, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(want_obj.data(), c->ir.obj, sizeof(am355_ir_object) * (size_t)mm.n_obj, hipMemcpyDeviceToHost));
+    same = !n_after || memcmp(got.data(), want.data(), sizeof(am355_ir_map) * (size_t)n_after) == 0;
+    for (uint32_t k = 0; same && k < mm.n_obj; k++) same = got_obj[k].map_begin == want_obj[k].map_begin && got_obj[k].map_end == want_obj[k].map_end;
+  }
+  if (trace && !same) fprintf(stderr, "resident: map table verify: %u records in place, %u from scratch\n", n_after, hc->n_map_emit);
+  if (!same) return fail(c, AM355_E_DEVICE, "internal: the map table merged in place differs from the table computed from scratch");
+  return AM355_OK;
+}
+
+// The batch's map rows into the stored table: the first half (own_look: no list stage judged the batch -- the first half was enqueued
+// in front of the host's hashing and says itself whether every row is a plain map row; a batch with other rows is no attempt), its
+// words, and -- unless it declines -- the second half. served: the stored table is the merged one. Writes the context's map table
+// pointers, map counts and counters; runs behind the commit.
+static int resident_map_rows_in_place(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const ResidentLap& lap, bool own_look, bool& served) {
+  hipStream_t st = c->stream;
+  MergeBufs& b = c->mb;
+  MapMergeBufs& mm = rs.mm;
+  uint32_t w[MM_WORDS];
+  served = false;
+  if (!rs.map_merge_on) return AM355_OK;
+  if (!rs.map_merge_fits) {
+    c->n_map_merge_declined++;
+    lap("map table: batch beyond the stage's rows, left to the map half of the merge");
+    return AM355_OK;
+  }
+  if (!own_look) { const int frc = resident_map_find(c, rb, rs); if (frc) return frc; }
+  if (wait_host_signal(&b.sig->mapmerge_seq, b.sig_seq, st)) {
+    memcpy(w, (const void*)b.sig->mapmerge, sizeof w);
+    c->staging_in_flight = false;   // (the kernel that signalled ran behind everything that read the pinned arena)
+  } else {
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipMemcpy(w, mm.words, sizeof w, hipMemcpyDeviceToHost));
+  }
+  if (w[MM_FLAGS]) return error_for_flags(c, w[MM_FLAGS], "op set rejected");
+  if (own_look && w[MM_OTHER_ROWS]) return AM355_OK;
+  const uint32_t n_after = mm.n_map - w[MM_N_DEAD] + w[MM_N_NEW];
+  if (w[MM_DECLINE] || n_after > c->mb.row_stride) {
+    c->n_map_merge_declined++;
+    lap("map table: left to the map half of the merge");
+    return AM355_OK;
+  }
+  mapmerge_write(b, c->ir, mm, w[MM_N_NEW], w[MM_MAX_KEY], st);
+  am355_ir_map* const was = c->ir.map;
+  c->ir.map = c->map_alt_ptr;
+  c->map_alt_ptr = was;   // (the previous table is what the next in-place merge writes)
+  c->counts.n_map_emit = n_after;
+  c->counts.max_key_len = std::max(c->counts.max_key_len, w[MM_MAX_KEY]);   // (an upper bound: read to size the key passes of the map order only)
+  c->n_map_merge_calls++;
+  served = true;
+  lap("map table merged in place");
+  if (getenv("AM355_MAPMERGE_VERIFY")) return resident_map_verify(c, mm, n_after, lap.on);   // (tests; read per call)
+  return AM355_OK;
+}
+
+// The map half of a batch whose list stage found plain map rows (alone, or beside list edits merged in place): merged into the stored
+// records where the switch is on and the stage takes the batch, by merge_run_maps otherwise, whose counts the context then takes.
+// The flags that differ between the two callers stay with them.
+static int resident_map_half(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const ResidentLap& lap) {
+  bool in_place = false;
+  { const int mrc = resident_map_rows_in_place(c, rb, rs, lap, false, in_place); if (mrc) return mrc; }
+  if (in_place) return AM355_OK;
+  Counts* hc = c->h_counts.as<Counts>();
+  merge_run_maps(c->mb, c->ir, hc, c->stream);
+  lap("map half of the merge done");
+  if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
+  c->counts.n_map_emit = hc->n_map_emit;
+  c->counts.max_key_len = hc->max_key_len;
+  return AM355_OK;
+}
+
+// SHA-256 of staged change `ci` into c->h_hashes (columnar.js:693-705: over the chunk without magic + checksum); false: the checksum does not match
+static bool resident_hash_one(am355_ctx* c, uint32_t ci) {
+  const uint8_t* raw = c->raw.data();
+  uint8_t* h = c->h_hashes.as<uint8_t>() + 32 * (size_t)ci;
+  const uint64_t off = c->raw_off[ci], len = c->raw_off[ci + 1] - off;
+  if (len < 9) return false;
+  sha256_digest(raw + off + 8, (size_t)len - 8, h);
+  return memcmp(h, raw + off + 4, 4) == 0;
+}
+
+// The batch's hashes, and what depends on them: not a duplicate, every dependency an applied change (a change of this batch in
+// front counts), the heads. Run BEHIND the enqueue of the batch's device work (decode, resolution, list order): SHA-256 of a
+// 3 KB change is ~1.5 us of the calling thread -- 40 changes 60 us with the lookups -- which the device spends on the batch anyway.
+// A batch that fails here has changed the kept arrays: the full replay that follows starts from the staged bytes, as it does
+// after any failure. Writes h_hashes behind the applied changes, the hash index (the batch's changes enter it: a failure must drop
+// it, fallback_dirty) and rb's dependency lists and head marks. Returns the reason, nullptr when the batch passes.
+static const char* resident_hashes_and_dependencies(am355_ctx* c, ResidentBatch& rb) {
+  const uint32_t K = rb.K, nb = rb.nb;
+  std::atomic<int> bad_sum{0};
+  if (nb >= 32 && c->pool->size() >= 2) {
+    const unsigned parts = std::min<unsigned>(c->pool->size() + 1, 16u);
+    c->pool->run(parts, [&](unsigned t) { for (uint32_t i = t; i < nb; i += parts) if (!resident_hash_one(c, K + i)) bad_sum.store(1); });
+  } else {
+    for (uint32_t i = 0; i < nb; i++) if (!resident_hash_one(c, K + i)) bad_sum.store(1);
+  }
+  if (bad_sum.load()) return "checksum";
+  const uint8_t* hs = c->h_hashes.as<uint8_t>();
+  const uint8_t* prev_deps = nullptr;   // the dependency block of the change in front (a round of synced peers shares it): resolved once
+  uint32_t prev_n_deps = 0, prev_first = 0;
+  std::vector<uint32_t>&dep_first = rb.dep_first, &dep_index = rb.dep_index;
+  dep_first.reserve(nb + 1); dep_index.reserve(2 * (size_t)nb);
+  dep_first.assign(1, 0);
+  for (uint32_t i = 0; i < nb; i++) {
+    const ChangeMeta& m = rb.metas[i];
+    const uint32_t ci = K + i;
+    if (hash_index_find(c, hs + 32 * (size_t)ci) != NONE32) return "duplicate change";
+    const uint8_t* deps = c->raw.data() + m.base + m.deps_off;
+    if (prev_deps && prev_n_deps == m.n_deps && m.n_deps && memcmp(prev_deps, deps, 32 * (size_t)m.n_deps) == 0) {
+      for (uint32_t k = 0; k < m.n_deps; k++) dep_index.push_back(dep_index[prev_first + k]);   // (their head marks are already down)
+    } else {
+      for (uint32_t k = 0; k < m.n_deps; k++) {
+        const uint32_t di = hash_index_find(c, deps + 32 * (size_t)k);
+        if (di == NONE32) return "dependency not applied yet";
+        dep_index.push_back(di);
+        rb.is_head[di] = 0;
+      }
+    }
+    prev_deps = deps; prev_n_deps = m.n_deps; prev_first = dep_first.back();
+    dep_first.push_back((uint32_t)dep_index.size());
+    rb.is_head[ci] = 1;
+    hash_index_add(c, ci);   // (undone by dropping the index when a later change fails)
+  }
+  return nullptr;
+}
+
+// The commit: the ONLY phase that writes the context's host state, run once the batch has passed every check. Takes rb's tables by
+// swap (plans_dev, spans_new, tab_new, actors_new) or copy (amap); rb is spent behind it but for its sizes and flags.
+static void resident_commit(am355_ctx* c, ResidentBatch& rb) {
+  const uint32_t K = rb.K, n = rb.n, nb = rb.nb;
+  const uint8_t* hs = c->h_hashes.as<uint8_t>();
+  c->hash_index_n = n;
+  if (rb.grow) {
+    // every host table that is indexed by a rank or holds one: the actors, the clock's actors (below: the clock itself and the span
+    // tables, built by new rank above), the rank of a loaded document's actor indexes (read by am355_save / am355_doc_changes of a
+    // document context only, which never comes here: kept in step all the same), the id -> rank index and the per-author memo of
+    // this path (rebuilt by the next call). c->plans / c->amap are this batch's, by new rank; am355_save ranks and inverts per call.
+    c->actors.swap(rb.actors_new);
+    for (uint32_t& a : c->clock_actor) a = rb.remap[a];
+    if (c->doc_actor_rank.size() == rb.NA)
+      for (uint32_t& r : c->doc_actor_rank) if (r < rb.NA) r = rb.remap[r];
+    c->res_rank_of.clear();
+    c->res_rank_n = 0;
+    c->res_actor_memo.clear();
+    if (rb.rank_moved) {
+      // the host copies of the object and map tables hold the ranks from before: the in-place branch of the verdicts must not take them for current
+      c->h_tables_current = c->h_tables_were_current = false;
+      c->ir_copy_enqueued = 0;
+    }
+  }
+  for (uint32_t a : rb.new_clock_actors) c->clock_actor.push_back(a);
+  c->clock_seq.clear();
+  for (uint32_t a : c->clock_actor) c->clock_seq.push_back(rb.clock[a]);
+  {
+    std::vector<const uint8_t*> hv;
+    for (uint32_t i = 0; i < n; i++)
+      if (rb.is_head[i]) hv.push_back(hs + 32 * (size_t)i);
+    std::sort(hv.begin(), hv.end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; });
+    std::vector<uint8_t> heads_new(hv.size() * 32);
+    for (size_t k = 0; k < hv.size(); k++) memcpy(&heads_new[32 * k], hv[k], 32);
+    c->heads.swap(heads_new);
+  }
+  c->spans.swap(rb.spans_new);
+  c->actor_tab_off.swap(rb.tab_new);
+  for (uint32_t i = 0; i < nb; i++) { c->applied_change.push_back(K + i); c->applied_op_base.push_back(rb.op_base[i]); }
+  if (c->res_dep_first.empty()) c->res_dep_first.assign(1, 0);
+  for (uint32_t i = 0; i < nb; i++) {
+    c->res_dep_index.insert(c->res_dep_index.end(), rb.dep_index.begin() + rb.dep_first[i], rb.dep_index.begin() + rb.dep_first[i + 1]);
+    c->res_dep_first.push_back((uint32_t)c->res_dep_index.size());
+  }
+  c->n_applied = n; c->n_pending = 0;
+  c->pending_change.clear();
+  c->pass_first_row.clear();
+  c->n_ops = rb.N; c->n_preds = rb.P; c->max_op = rb.max_op;
+  c->has_unknown_cols = false;
+  c->plans.swap(rb.plans_dev);
+  c->amap = rb.amap;
+}
+
+// The verdict of the list-order stage and the flags of the resolution (signalled into pinned words by a launch behind it: two copy
+// dispatches and their wait otherwise), and what follows from it: the order merged in place (with the map half behind it when plain
+// map rows came beside the list edits), plain map rows only, or neither. Writes the context's order pointers, counts, patch-table
+// flags and counters; sets merged_in_place / maps_only. AM355_OK or an error.
+static int resident_list_verdict(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const ResidentLap& lap, bool& merged_in_place, bool& maps_only) {
+  hipStream_t st = c->stream;
+  MergeBufs& b = c->mb;
+  uint32_t* hw = c->h_resorder.as<uint32_t>();
+  if (wait_host_signal(&b.sig->resorder_seq, b.sig_seq, st)) {
+    memcpy(hw, (const void*)b.sig->resorder, 36);
+    c->staging_in_flight = false;   // (the kernel that signalled ran behind everything that read the pinned arena)
+  } else {
+    HIPCHK(c, hipMemcpyAsync(hw, rs.ro.words, 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hw + 8, &b.counts->flags, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+  }
+  if (hw[8]) return error_for_flags(c, hw[8], "op set rejected");
+  if (hw[0] == 0) {
+    // the order after the batch is the state's order from here on: in the other buffer after an odd number of chunks
+    if (rs.final_in_new) {
+      uint32_t* old_order = b.order;
+      b.order = rs.ro.order_new;
+      c->order_alt_ptr = old_order;   // (the previous order array is what the next in-place merge writes)
+    }
+    c->counts.n_list_ins = hw[2] + hw[1];
+    c->pos_valid = true;
+    c->ir_stale = true;
+    c->ir_fetched = false;
+    // the object and map tables are what they were (the batch has list rows only and makes no object): a host copy of them that was
+    // current before the call still is, and no copy is enqueued for the call's patch; the edit table it may have come with is not
+    c->h_tables_current = c->h_tables_were_current;
+    c->ir_copy_enqueued = c->h_tables_current ? 1 : 0;
+    c->hir.edits = nullptr;
+    c->n_resorder_calls++;
+    c->batch_list_only = true;
+    merged_in_place = true;
+    lap("list order merged in place");
+    if (hw[4]) {
+      // plain map rows beside the list edits (text typed and a key assigned in one change): the map half of the merge behind the
+      // in-place list merge -- the map records and the object table's map ranges change, the delta stage runs its map kernels
+      { const int mrc = resident_map_half(c, rb, rs, lap); if (mrc) return mrc; }
+      c->h_tables_current = false;
+      c->ir_copy_enqueued = 0;
+      c->batch_list_only = false;
+      c->n_maps_only_calls++;
+    }
+  } else if (hw[3] == 0 && !rs.no_maps_only) {
+    // a batch of plain map rows (`set` / `del` on string keys): no list changes -- the stored order, positions and element counts stay,
+    // the map half of the merge runs alone (visibility, object table, map records in patch order); the whole-document edit tables are
+    // stale from here on, as after an in-place list merge
+    { const int mrc = resident_map_half(c, rb, rs, lap); if (mrc) return mrc; }
+    c->ir_stale = true;
+    c->ir_fetched = false;
+    c->n_maps_only_calls++;
+    c->pos_valid = true;   // (the positions this call read or rebuilt: the order did not change)
+    maps_only = true;
+  } else {
+    c->pos_valid = false;
+    lap("list order: not a batch for the in-place merge");
+  }
+  return AM355_OK;
+}
+
+// One Backend.applyChanges onto the kept state: the phases above in their order. The host part decides on copies (rb); the device
+// part is enqueued; the host hashes behind it; the commit; the verdicts. Four things hold the path together, each marked below where
+// it is enforced: no host state of the context changes before the commit (but the two indexes, the memo and allocation growth);
+// resident_valid drops before the first write to kept arrays; hashing starts behind the last enqueue and in front of the first
+// wait; the hash index is dropped once changes of the batch have entered it and the batch fails.
+static int replay_resident(am355_ctx* c) {
+  const ResidentLap lap{getenv("AM355_TRACE") != nullptr, std::chrono::steady_clock::now()};
+  const bool trace = lap.on;
+  hipStream_t st = c->stream;
+  MergeBufs& b = c->mb;
+  ResidentBatch rb;   // (on this stack: gone on every path out, nothing points into it afterwards)
+  ResidentStages rs;
+  rs.no_maps_only = getenv("AM355_NO_MAPS_ONLY") != nullptr;   // (per call: tests flip it between calls)
+  int rc;
+
+  // ---- host: everything decided on copies; up to the commit the context's host state stays as it is ----
+  if (const char* why = resident_preconditions(c, rb)) return resident_fallback(c, why, trace);
+  if ((rc = resident_parse(c, rb))) return rc;
+  lap("batch parsed (host)");
+  resident_indexes(c, rb);
+  resident_rank_newcomers(c, rb);
+  if (const char* why = resident_clock_and_heads(c, rb)) return resident_fallback(c, why, trace);
+  if (const char* why = resident_schedule(c, rb)) return resident_fallback_dirty(c, why, trace);
+  lap("batch scheduled (host)");
+  resident_build_tables(c, rb);
+
+  // ---- device: tables, the batch's rows, their resolution, then the list order / the map merge's first half ----
+  if ((rc = resident_upload_tables(c, rb))) return rc;
+  if ((rc = resident_bind_merge(c, rb))) return rc;
+  if ((rc = resident_bind_list_order(c, rb, rs))) return rc;
+  // Behind the last fallback that leaves the state usable, in front of the flush and of the first launch that writes kept arrays:
+  // from here on the kept arrays change, a failure leaves no state behind.
+  c->resident_valid = false;
+  if ((rc = flush_uploads(c))) return rc;   // (the batch's bytes, its records, the tables, the delta stage's breaks: one launch; its hashes follow)
+  if ((rc = resident_decode(c, rb, rs))) return rc;
+  lap("decode enqueued");
   merge_resolve(b, st);
-  bool merged_in_place = false, maps_only = false, final_in_new = true;
-  if (try_resorder) {
-    if (!c->pos_valid) resorder_positions(b, NL_old, ro.pos_of, st);
-    resorder_run(b, ro, st, &final_in_new);
+  if (rs.try_resorder) {
+    if (!c->pos_valid) resorder_positions(b, rs.NL_old, rs.ro.pos_of, st);
+    resorder_run(b, rs.ro, st, &rs.final_in_new);
   }
   // ---- map table: with am355_set_resident_map_merge the batch's plain map rows are merged into the STORED records (am355_merge.h
   //      MapMergeBufs) where merge_run_maps would emit and order every record of the document again. Its first half reads the stored
@@ -1507,172 +1823,33 @@ static int replay_resident(am355_ctx* c) {
   //      objects' ranges -- a batch it declines goes on with the path of before on state nobody touched. A document without a list has
   //      no list stage whose verdict says "plain map rows only": the first half's own look at the rows decides, and it is enqueued
   //      here, in front of the host's hashing. ----
-  const bool map_merge_on = c->resident_map_merge && NN && c->mb.row_stride;
-  const bool map_merge_fits = NN <= MAPMERGE_ROWS_MAX;   // (a larger batch is declined here, before anything is enqueued for it)
-  const bool map_merge_alone = map_merge_on && !try_resorder && NL_old == 0;
-  MapMergeBufs mm{};
-  auto map_merge_find = [&]() -> int {
-    const uint32_t n_map = c->counts.n_map_emit, n_obj = c->counts.n_objects;
-    if (!c->map_alt_ptr) {
-      if (!c->d_map_alt.ensure(sizeof(am355_ir_map) * (size_t)c->mb.row_stride)) return fail(c, AM355_E_NOMEM, "device allocation failed (resident map table)");
-      c->map_alt_ptr = c->d_map_alt.as<am355_ir_map>();
-    }
-    if (!c->d_mapmerge.ensure(mapmerge_bytes(NN, n_map, n_obj))) return fail(c, AM355_E_NOMEM, "device allocation failed (resident map table)");
-    mapmerge_bind(mm, c->d_mapmerge.p, NN, n_map, n_obj);
-    mm.T0 = (uint32_t)old_ops;
-    mm.map = c->ir.map; mm.map_new = c->map_alt_ptr;
-    mm.sig = b.sig; mm.sig_seq = b.sig_seq;
-    mapmerge_find(b, c->ir, mm, st);
-    return AM355_OK;
-  };
-  // The batch's map rows into the stored table: the first half (own_look: no list stage judged the batch -- the first half was enqueued
-  // in front of the host's hashing and says itself whether every row is a plain map row; a batch with other rows is no attempt), its
-  // words, and -- unless it declines -- the second half. served: the stored table is the merged one.
-  auto map_rows_in_place = [&](bool own_look, bool& served) -> int {
-    uint32_t w[MM_WORDS];
-    served = false;
-    if (!map_merge_on) return AM355_OK;
-    if (!map_merge_fits) {
-      c->n_map_merge_declined++;
-      lap("map table: batch beyond the stage's rows, left to the map half of the merge");
-      return AM355_OK;
-    }
-    if (!own_look) { const int frc = map_merge_find(); if (frc) return frc; }
-    if (wait_host_signal(&b.sig->mapmerge_seq, b.sig_seq, st)) {
-      memcpy(w, (const void*)b.sig->mapmerge, sizeof w);
-      c->staging_in_flight = false;   // (the kernel that signalled ran behind everything that read the pinned arena)
-    } else {
-      HIPCHK(c, hipStreamSynchronize(st));
-      HIPCHK(c, hipMemcpy(w, mm.words, sizeof w, hipMemcpyDeviceToHost));
-    }
-    if (w[MM_FLAGS]) return error_for_flags(c, w[MM_FLAGS], "op set rejected");
-    if (own_look && w[MM_OTHER_ROWS]) return AM355_OK;
-    const uint32_t n_after = mm.n_map - w[MM_N_DEAD] + w[MM_N_NEW];
-    if (w[MM_DECLINE] || n_after > c->mb.row_stride) {
-      c->n_map_merge_declined++;
-      lap("map table: left to the map half of the merge");
-      return AM355_OK;
-    }
-    mapmerge_write(b, c->ir, mm, w[MM_N_NEW], w[MM_MAX_KEY], st);
-    am355_ir_map* const was = c->ir.map;
-    c->ir.map = c->map_alt_ptr;
-    c->map_alt_ptr = was;   // (the previous table is what the next in-place merge writes)
-    c->counts.n_map_emit = n_after;
-    c->counts.max_key_len = std::max(c->counts.max_key_len, w[MM_MAX_KEY]);   // (an upper bound: read to size the key passes of the map order only)
-    c->n_map_merge_calls++;
-    served = true;
-    lap("map table merged in place");
-    if (getenv("AM355_MAPMERGE_VERIFY")) {   // (tests; read per call)
-      std::vector<am355_ir_map> got(n_after), want(n_after);
-      std::vector<am355_ir_object> got_obj(mm.n_obj), want_obj(mm.n_obj);
-      HIPCHK(c, hipStreamSynchronize(st));
-      if (n_after) HIPCHK(c, hipMemcpy(got.data(), c->ir.map, sizeof(am355_ir_map) * (size_t)n_after, hipMemcpyDeviceToHost));
-      HIPCHK(c, hipMemcpy(got_obj.data(), c->ir.obj, sizeof(am355_ir_object) * (size_t)mm.n_obj, hipMemcpyDeviceToHost));
-      merge_run_maps(b, c->ir, hc, st);
-      HIPCHK(c, hipStreamSynchronize(st));
-      if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
-      bool same = hc->n_map_emit == n_after;
-      if (same) {
-        if (n_after) HIPCHK(c, hipMemcpy(want.data(), c->ir.map, sizeof(am355_ir_map) * (size_t)n_after, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(want_obj.data(), c->ir.obj, sizeof(am355_ir_object) * (size_t)mm.n_obj, hipMemcpyDeviceToHost));
-        same = !n_after || memcmp(got.data(), want.data(), sizeof(am355_ir_map) * (size_t)n_after) == 0;
-        for (uint32_t k = 0; same && k < mm.n_obj; k++) same = got_obj[k].map_begin == want_obj[k].map_begin && got_obj[k].map_end == want_obj[k].map_end;
-      }
-      if (trace && !same) fprintf(stderr, "resident: map table verify: %u records in place, %u from scratch\n", n_after, hc->n_map_emit);
-      if (!same) return fail(c, AM355_E_DEVICE, "internal: the map table merged in place differs from the table computed from scratch");
-    }
-    return AM355_OK;
-  };
-  if (map_merge_alone && map_merge_fits) { const int mrc = map_merge_find(); if (mrc) return mrc; }
+  rs.map_merge_on = c->resident_map_merge && rs.NN && c->mb.row_stride;
+  rs.map_merge_fits = rs.NN <= MAPMERGE_ROWS_MAX;   // (a larger batch is declined here, before anything is enqueued for it)
+  rs.map_merge_alone = rs.map_merge_on && !rs.try_resorder && rs.NL_old == 0;
+  if (rs.map_merge_alone && rs.map_merge_fits && (rc = resident_map_find(c, rb, rs))) return rc;
   lap("resolution / list order enqueued");
-  // ---- host, while the device works on the batch: hashes, duplicates, dependencies; then the commit ----
-  if (const char* why = hashes_and_dependencies()) {
+
+  // ---- host, while the device works on the batch (behind the last enqueue, in front of the first wait): hashes, duplicates, dependencies ----
+  if (const char* why = resident_hashes_and_dependencies(c, rb)) {
     (void)hipStreamSynchronize(st);   // (the copy kernel reads the pinned arena; the kernels behind it signal into this call's words)
     c->staging_in_flight = false;
     c->pos_valid = false;
-    return fallback_dirty(why);
+    return resident_fallback_dirty(c, why, trace);   // (changes of the batch may have entered the hash index: dropped)
   }
-  commit_host_state();
-  { int qrc = queue_upload(c, c->d_hashes.as<uint8_t>() + 32 * (size_t)K, hs + 32 * (size_t)K, 32 * (size_t)nb); if (!qrc) qrc = flush_uploads(c); if (qrc) return qrc; }
+  resident_commit(c, rb);   // (the batch has passed every check: the context's host state changes here and nowhere before)
+  { uint8_t* hs = c->h_hashes.as<uint8_t>() + 32 * (size_t)rb.K; rc = queue_upload(c, c->d_hashes.as<uint8_t>() + 32 * (size_t)rb.K, hs, 32 * (size_t)rb.nb); }
+  if (!rc) rc = flush_uploads(c);
+  if (rc) return rc;
   lap("batch hashed, dependencies checked, committed (host)");
-  if (try_resorder) {
-    // its verdict and the flags of the resolution: signalled into pinned words by a launch behind it (two copy dispatches and their wait otherwise)
-    uint32_t* hw = c->h_resorder.as<uint32_t>();
-    if (wait_host_signal(&b.sig->resorder_seq, b.sig_seq, st)) {
-      memcpy(hw, (const void*)b.sig->resorder, 36);
-      c->staging_in_flight = false;   // (the kernel that signalled ran behind everything that read the pinned arena)
-    } else {
-      HIPCHK(c, hipMemcpyAsync(hw, ro.words, 32, hipMemcpyDeviceToHost, st));
-      HIPCHK(c, hipMemcpyAsync(hw + 8, &b.counts->flags, 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(c, hipStreamSynchronize(st));
-    }
-    if (hw[8]) return error_for_flags(c, hw[8], "op set rejected");
-    if (hw[0] == 0) {
-      // the order after the batch is the state's order from here on: in the other buffer after an odd number of chunks
-      if (final_in_new) {
-        uint32_t* old_order = b.order;
-        b.order = ro.order_new;
-        c->order_alt_ptr = old_order;   // (the previous order array is what the next in-place merge writes)
-      }
-      c->counts.n_list_ins = hw[2] + hw[1];
-      c->pos_valid = true;
-      c->ir_stale = true;
-      c->ir_fetched = false;
-      // the object and map tables are what they were (the batch has list rows only and makes no object): a host copy of them that was
-      // current before the call still is, and no copy is enqueued for the call's patch; the edit table it may have come with is not
-      c->h_tables_current = c->h_tables_were_current;
-      c->ir_copy_enqueued = c->h_tables_current ? 1 : 0;
-      c->hir.edits = nullptr;
-      c->n_resorder_calls++;
-      c->batch_list_only = true;
-      merged_in_place = true;
-      lap("list order merged in place");
-      if (hw[4]) {
-        // plain map rows beside the list edits (text typed and a key assigned in one change): the map half of the merge behind the
-        // in-place list merge -- the map records and the object table's map ranges change, the delta stage runs its map kernels
-        bool in_place = false;
-        { const int mrc = map_rows_in_place(false, in_place); if (mrc) return mrc; }
-        if (!in_place) {
-          merge_run_maps(b, c->ir, hc, st);
-          lap("map half of the merge done");
-          if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
-          c->counts.n_map_emit = hc->n_map_emit;
-          c->counts.max_key_len = hc->max_key_len;
-        }
-        c->h_tables_current = false;
-        c->ir_copy_enqueued = 0;
-        c->batch_list_only = false;
-        c->n_maps_only_calls++;
-      }
-    } else if (hw[3] == 0 && !getenv("AM355_NO_MAPS_ONLY")) {
-      // a batch of plain map rows (`set` / `del` on string keys): no list changes -- the stored order, positions and element counts stay,
-      // the map half of the merge runs alone (visibility, object table, map records in patch order); the whole-document edit tables are
-      // stale from here on, as after an in-place list merge
-      bool in_place = false;
-      { const int mrc = map_rows_in_place(false, in_place); if (mrc) return mrc; }
-      if (!in_place) {
-        merge_run_maps(b, c->ir, hc, st);
-        lap("map half of the merge done");
-        if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
-        c->counts.n_map_emit = hc->n_map_emit;
-        c->counts.max_key_len = hc->max_key_len;
-      }
-      c->ir_stale = true;
-      c->ir_fetched = false;
-      c->n_maps_only_calls++;
-      c->pos_valid = true;   // (the positions this call read or rebuilt: the order did not change)
-      maps_only = true;
-    } else {
-      c->pos_valid = false;
-      lap("list order: not a batch for the in-place merge");
-    }
-  }
-  if (map_merge_alone) {
+
+  // ---- the verdicts: which stage served the call ----
+  bool merged_in_place = false, maps_only = false;
+  if (rs.try_resorder && (rc = resident_list_verdict(c, rb, rs, lap, merged_in_place, maps_only))) return rc;
+  if (rs.map_merge_alone) {
     // a document without a list: plain map rows only -> the stored map table merged in place is all the call changes (the edit tables
     // are stale from here on, as behind the map half alone); anything else goes on with merge_run below, as without the switch
     bool in_place = false;
-    const int mrc = map_rows_in_place(true, in_place);
-    if (mrc) return mrc;
+    if ((rc = resident_map_rows_in_place(c, rb, rs, lap, true, in_place))) return rc;
     if (in_place) {
       c->ir_stale = true;
       c->ir_fetched = false;
@@ -1684,6 +1861,7 @@ static int replay_resident(am355_ctx* c) {
     }
   }
   if (!merged_in_place && !maps_only) {
+    Counts* hc = c->h_counts.as<Counts>();
     if (!merge_prepare(b, st, MERGE_FILL_TABLES)) return fail(c, AM355_E_DEVICE, "merge fills: more ranges than one launch takes");
     merge_run(b, c->ir, hc, st, nullptr, c->ev_runs, true);
     lap("merge_run done");
@@ -1694,9 +1872,9 @@ static int replay_resident(am355_ctx* c) {
     c->ir_stale = false;
   }
   c->n_resident_calls++;
-  if (grow) {
+  if (rb.grow) {
     c->n_new_actor_calls++;
-    if (rank_moved) c->n_rank_rewrites++;
+    if (rb.rank_moved) c->n_rank_rewrites++;
   }
   return AM355_OK;
 }

@@ -397,6 +397,44 @@ def test_failure_behind_the_rewrite_gpu(monkeypatch):
     check_failure_behind_the_rewrite(_gpu)
 
 
+def check_known_author_beside_a_newcomer(make_engine):
+    """The per-author memo of the "other actors" table holds ranks from BEFORE an insertion. Two actors, three rounds; a resident call
+    with the second actor's second-round change leaves its table in the memo; the next batch holds the setup change of an independent
+    log -- a newcomer whose id sorts in front of every kept actor, so every kept rank moves -- and that actor's third-round change,
+    whose table of other actors is byte for byte the one in the memo: its ranks must be looked up anew (a batch that inserts actors
+    goes without the memo). One call, one insertion, one rewrite, the oracle's patches."""
+    for seed in range(7, 200):
+        ch, ids = text_log(2, 3, 8, 1, seed=seed)
+        mine = [c for c in ch[3:] if author_of(c) == ids[1]]
+        if len(mine) == 2 and other_actors_of(mine[0]) == other_actors_of(mine[1]) != []:
+            break
+    else:
+        raise AssertionError("no seed repeats the table of other actors")
+    theirs = [c for c in ch[3:] if author_of(c) == ids[0]]
+    for seed in range(300, 500):
+        setup = _changes_of(loggen.generate(loggen.KIND_TEXT_CONCURRENT, n_actors=1, n_rounds=1, ins_per_change=4, del_per_change=0, n_objects=1, seed=seed))[0]
+        if author_of(setup) < min(ids):
+            break
+    else:
+        raise AssertionError("no seed gives a newcomer in front of the kept actors")
+    batches = [ch[:3], [theirs[0]], [mine[0]], [setup, mine[1]], [theirs[1]]]
+    make = Switched(make_engine)
+    seen = drive(make, batches, {0: NOT_ATTEMPTED}, whole_after=(3,))
+    assert sum(s[1] for s in seen) == 0 and seen[3][:3] in (IN_PLACE, MERGE_RUN), seen
+    assert make.calls[3] == (1, 1, 3), make.calls
+
+
+def test_known_author_beside_a_newcomer_emulated(emu_lib, monkeypatch):
+    monkeypatch.setenv("AM355_RESORDER_VERIFY", "1")
+    check_known_author_beside_a_newcomer(_emulated(emu_lib))
+
+
+@pytest.mark.gpu
+def test_known_author_beside_a_newcomer_gpu(monkeypatch):
+    monkeypatch.setenv("AM355_RESORDER_VERIFY", "1")
+    check_known_author_beside_a_newcomer(_gpu)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # 6. the actor count crosses a key width
 # ---------------------------------------------------------------------------------------------------------------------------
