@@ -169,6 +169,19 @@ extern "C" int am355_resident_map_merge_calls(const am355_ctx* c, uint64_t out[2
   return AM355_OK;
 }
 
+extern "C" int am355_set_resident_new_objects(am355_ctx* c, int on) {
+  if (!c) return AM355_E_ARG;
+  c->resident_new_objects = on != 0;
+  return AM355_OK;
+}
+
+extern "C" int am355_resident_new_object_calls(const am355_ctx* c, uint64_t out[2]) {
+  if (!c || !out) return AM355_E_ARG;
+  out[0] = c->n_new_object_calls;
+  out[1] = c->n_new_object_declined;
+  return AM355_OK;
+}
+
 extern "C" int am355_get_raw(const am355_ctx* c, const uint8_t** arena, const uint64_t** offsets, uint32_t* n) {
   if (!c || !c->staged) return AM355_E_STATE;
   if (arena) *arena = c->raw.data();

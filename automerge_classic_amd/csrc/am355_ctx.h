@@ -511,6 +511,10 @@ struct am355_ctx {
   // of every record being emitted and ordered again (merge_run_maps); a document without a list is served that way too
   bool resident_map_merge = false;
   uint64_t n_map_merge_calls = 0, n_map_merge_declined = 0;   // resident calls whose map rows were merged in place | that tried and went on with the path of before
+  // am355_set_resident_new_objects: a batch that makes objects is merged in place -- the new objects take the next indexes of the stored
+  // object table and the end of the stored order (am355_resorder.hip kr_new_objects) -- instead of by merge_run over every row
+  bool resident_new_objects = false;
+  uint64_t n_new_object_calls = 0, n_new_object_declined = 0;   // resident calls that made objects and were served without merge_run | that tried and went on with merge_run
   DevBuf d_map_alt, d_mapmerge;                    // the other map table | the stage's scratch
   am355_ir_map* map_alt_ptr = nullptr;             // whichever of the two map tables c->ir.map does NOT point to (null: not set up since the last carve)
   std::string resident_why;                        // why the last attempt fell back (diagnostics, AM355_TRACE)

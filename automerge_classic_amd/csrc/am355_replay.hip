@@ -1143,6 +1143,7 @@ struct ResidentStages {
   bool try_resorder = false, final_in_new = true;
   bool map_merge_on = false, map_merge_fits = false, map_merge_alone = false;
   bool no_maps_only = false;             // AM355_NO_MAPS_ONLY (tests, A/B: read once per call)
+  bool new_objects = false;              // am355_set_resident_new_objects, and the carve holds an object per row of the batch
 };
 
 // Phase 1, preconditions. Reads the context; writes the sizes of `rb`, nothing of the context. Returns why the kept state or the mode
@@ -1445,9 +1446,18 @@ static int resident_bind_list_order(am355_ctx* c, const ResidentBatch& rb, Resid
     if (!c->d_order_alt.ensure(4 * (cap_rows + 2))) return fail(c, AM355_E_NOMEM, "device allocation failed (resident list order)");
     c->order_alt_ptr = c->d_order_alt.as<uint32_t>();
   }
-  if (!c->d_pos.ensure_keep(4 * cap_rows, c->pos_valid ? 4 * (size_t)rb.old_ops : 0) || !c->d_resorder.ensure(resorder_bytes(NN, rs.NO)) || !c->h_resorder.ensure(64))
+  // am355_set_resident_new_objects: every row of the batch may make an object (how many do is known behind the decode): the stage's
+  // per-object scratch is sized for that, and the kept per-object arrays must hold as many -- the object table row_stride + 1
+  // entries, obj_first_pos / obj_n row_stride + 3 (setup_buffers), the delta stage's tables go by the count the verdict leaves. An
+  // object has a row, so the carve that holds the rows holds them; where it does not the call goes on without the switch: decided
+  // here, in front of the first write.
+  rs.new_objects = c->resident_new_objects && (size_t)rs.NO + NN + 1 <= cap_rows;
+  const uint32_t obj_most = rs.NO + (rs.new_objects ? NN : 0u);
+  if (!c->d_pos.ensure_keep(4 * cap_rows, c->pos_valid ? 4 * (size_t)rb.old_ops : 0) || !c->d_resorder.ensure(resorder_bytes(NN, obj_most)) || !c->h_resorder.ensure(64))
     return fail(c, AM355_E_NOMEM, "device allocation failed (resident list order)");
-  resorder_bind(ro, c->d_resorder.p, NN, rs.NO);
+  resorder_bind(ro, c->d_resorder.p, NN, obj_most);
+  ro.new_objects = rs.new_objects ? 1u : 0u;
+  ro.obj = c->ir.obj;
   canary_arm();   // (AM355_CANARY=1 only)
   ro.T0 = (uint32_t)rb.old_ops; ro.n_new = NN; ro.n_list = rs.NL_old; ro.n_obj = rs.NO;
   ro.pos_of = c->d_pos.as<uint32_t>();
@@ -1592,9 +1602,18 @@ static int resident_map_rows_in_place(am355_ctx* c, const ResidentBatch& rb, Res
 // The map half of a batch whose list stage found plain map rows (alone, or beside list edits merged in place): merged into the stored
 // records where the switch is on and the stage takes the batch, by merge_run_maps otherwise, whose counts the context then takes.
 // The flags that differ between the two callers stay with them.
-static int resident_map_half(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const ResidentLap& lap) {
+// made: objects the batch makes (am355_set_resident_new_objects). The stored map records take no makes: such a batch is declined there
+// and merge_run_maps writes the object table with the new objects -- at the indexes kr_new_objects gave them, or the call fails --;
+// the context's object count grows and the call is counted.
+static int resident_map_half(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const ResidentLap& lap, uint32_t made = 0) {
   bool in_place = false;
-  { const int mrc = resident_map_rows_in_place(c, rb, rs, lap, false, in_place); if (mrc) return mrc; }
+  if (made && rs.map_merge_on) {
+    c->n_map_merge_declined++;
+    lap("map table: the batch makes objects, left to the map half of the merge");
+  } else {
+    const int mrc = resident_map_rows_in_place(c, rb, rs, lap, false, in_place);
+    if (mrc) return mrc;
+  }
   if (in_place) return AM355_OK;
   Counts* hc = c->h_counts.as<Counts>();
   merge_run_maps(c->mb, c->ir, hc, c->stream);
@@ -1602,6 +1621,13 @@ static int resident_map_half(am355_ctx* c, const ResidentBatch& rb, ResidentStag
   if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
   c->counts.n_map_emit = hc->n_map_emit;
   c->counts.max_key_len = hc->max_key_len;
+  if (made) {
+    if (hc->n_objects + 1 != c->counts.n_objects + made)
+      return fail(c, AM355_E_DEVICE, "internal: the object table holds %u objects behind the map half, %u kept + %u made in place", hc->n_objects + 1, c->counts.n_objects, made);
+    c->counts.n_objects += made;
+    c->n_new_object_calls++;
+    lap("new objects merged in place");
+  }
   return AM355_OK;
 }
 
@@ -1730,6 +1756,8 @@ static int resident_list_verdict(am355_ctx* c, const ResidentBatch& rb, Resident
     HIPCHK(c, hipStreamSynchronize(st));
   }
   if (hw[8]) return error_for_flags(c, hw[8], "op set rejected");
+  const uint32_t made = rs.new_objects ? hw[5] : 0u;   // objects the batch makes (kr_new_objects: in the words the host waits for anyway)
+  if (made && lap.on) fprintf(stderr, "resident: %-30s %u\n", "objects the batch makes", made);
   if (hw[0] == 0) {
     // the order after the batch is the state's order from here on: in the other buffer after an odd number of chunks
     if (rs.final_in_new) {
@@ -1750,10 +1778,12 @@ static int resident_list_verdict(am355_ctx* c, const ResidentBatch& rb, Resident
     c->batch_list_only = true;
     merged_in_place = true;
     lap("list order merged in place");
-    if (hw[4]) {
+    if (hw[4] || made) {
       // plain map rows beside the list edits (text typed and a key assigned in one change): the map half of the merge behind the
-      // in-place list merge -- the map records and the object table's map ranges change, the delta stage runs its map kernels
-      { const int mrc = resident_map_half(c, rb, rs, lap); if (mrc) return mrc; }
+      // in-place list merge -- the map records and the object table's map ranges change, the delta stage runs its map kernels.
+      // A batch that made objects always: the new objects have their entries and indexes (kr_new_objects), their map ranges and the
+      // records of the new maps come from here
+      { const int mrc = resident_map_half(c, rb, rs, lap, made); if (mrc) return mrc; }
       c->h_tables_current = false;
       c->ir_copy_enqueued = 0;
       c->batch_list_only = false;
@@ -1763,7 +1793,9 @@ static int resident_list_verdict(am355_ctx* c, const ResidentBatch& rb, Resident
     // a batch of plain map rows (`set` / `del` on string keys): no list changes -- the stored order, positions and element counts stay,
     // the map half of the merge runs alone (visibility, object table, map records in patch order); the whole-document edit tables are
     // stale from here on, as after an in-place list merge
-    { const int mrc = resident_map_half(c, rb, rs, lap); if (mrc) return mrc; }
+    // (am355_set_resident_new_objects: makes on string keys and rows inside the new maps too -- the new objects have their empty
+    // stretches at the end of the order all the same, kr_new_objects)
+    { const int mrc = resident_map_half(c, rb, rs, lap, made); if (mrc) return mrc; }
     c->ir_stale = true;
     c->ir_fetched = false;
     c->n_maps_only_calls++;
@@ -1771,6 +1803,7 @@ static int resident_list_verdict(am355_ctx* c, const ResidentBatch& rb, Resident
     maps_only = true;
   } else {
     c->pos_valid = false;
+    if (made) c->n_new_object_declined++;
     lap("list order: not a batch for the in-place merge");
   }
   return AM355_OK;
@@ -1888,11 +1921,22 @@ int ensure_ir_fresh(am355_ctx* c) {
   hipStream_t st = c->stream;
   MergeBufs& b = c->mb;
   const uint32_t N = b.n_ops;
-  std::vector<uint32_t> kept;
+  std::vector<uint32_t> kept, kept_first, kept_n;
+  std::vector<am355_ir_object> kept_obj;
   const bool verify = getenv("AM355_RESORDER_VERIFY") != nullptr;
   if (verify) {
+    // (the stream first: the in-place calls' last launches may still run)
+    HIPCHK(c, hipStreamSynchronize(st));
     kept.resize(c->counts.n_list_ins);
     HIPCHK(c, hipMemcpy(kept.data(), b.order, 4 * kept.size(), hipMemcpyDeviceToHost));
+    // the objects as the in-place calls left them (am355_set_resident_new_objects: the batch's objects entered the table there)
+    const size_t NO = c->counts.n_objects;
+    kept_obj.resize(NO); kept_first.resize(NO); kept_n.resize(NO);
+    if (NO) {
+      HIPCHK(c, hipMemcpy(kept_obj.data(), c->ir.obj, sizeof(am355_ir_object) * NO, hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(kept_first.data(), b.obj_first_pos, 4 * NO, hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(kept_n.data(), b.obj_n, 4 * NO, hipMemcpyDeviceToHost));
+    }
   }
   c->sig_seq++;
   b.sig_seq = c->sig_seq;
@@ -1919,6 +1963,26 @@ int ensure_ir_fresh(am355_ctx* c) {
     std::vector<uint32_t> now(c->counts.n_list_ins);
     HIPCHK(c, hipMemcpy(now.data(), b.order, 4 * now.size(), hipMemcpyDeviceToHost));
     if (now != kept) return fail(c, AM355_E_DEVICE, "internal: the list order merged in place differs from the order computed from scratch");
+    const size_t NO = c->counts.n_objects;
+    if (NO != kept_obj.size())
+      return fail(c, AM355_E_DEVICE, "internal: %zu objects kept from the in-place calls, %zu computed from scratch", kept_obj.size(), NO);
+    std::vector<am355_ir_object> obj(NO);
+    std::vector<uint32_t> first(NO), cnt(NO);
+    if (NO) {
+      HIPCHK(c, hipMemcpy(obj.data(), c->ir.obj, sizeof(am355_ir_object) * NO, hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(first.data(), b.obj_first_pos, 4 * NO, hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(cnt.data(), b.obj_n, 4 * NO, hipMemcpyDeviceToHost));
+    }
+    for (size_t k = 1; k < NO; k++) {   // (_root's id means nothing; its stretch is compared below like any other)
+      const am355_ir_object &x = kept_obj[k], &y = obj[k];
+      if (x.id_ctr != y.id_ctr || x.id_actor != y.id_actor || x.type != y.type || x.make_row != y.make_row)
+        return fail(c, AM355_E_DEVICE, "internal: object %zu kept from the in-place calls is %u@%u type %u row %u, computed from scratch %u@%u type %u row %u", k,
+                    x.id_ctr, x.id_actor, x.type, x.make_row, y.id_ctr, y.id_actor, y.type, y.make_row);
+    }
+    for (size_t k = 0; k < NO; k++)
+      if (kept_first[k] != first[k] || kept_n[k] != cnt[k])
+        return fail(c, AM355_E_DEVICE, "internal: object %zu kept from the in-place calls has %u elements from position %u, computed from scratch %u from %u", k,
+                    kept_n[k], kept_first[k], cnt[k], first[k]);
   }
   return AM355_OK;
 }

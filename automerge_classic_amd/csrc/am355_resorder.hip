@@ -14,6 +14,13 @@
 // Plain map rows among the batch's rows (`set` / `del` on string keys) take no part in any of this: they stand like deletions here, and
 // the caller runs the map half of the merge behind the list merge (words[3] / words[4]; a batch of map rows only is left to that half
 // alone, replay_resident / merge_run_maps).
+// Objects the batch MAKES (r.new_objects; am355_set_resident_new_objects): the object table is in row order of the live make rows
+// (k_compact_rows) and the batch's rows stand behind all kept rows, so its objects take the indexes behind the stored ones and nothing
+// kept is renumbered; the order is grouped by object index, so their elements land at the END of the stored order and no kept object's
+// first position moves because of them. kr_new_objects writes those entries for the whole batch in front of the first chunk; a list
+// insert that makes an object is then an element like any other, a head insert into a new object finds first == end == the end of
+// the order (several new objects share that gap: the object in front first, kr_order), and a make on a string key stands like a plain
+// map row -- the caller runs the map half behind the list merge whenever words[5] says the batch made objects.
 // The order after the batch is then a MERGE: an old element at position p moves up by the number of new elements with gap <= p, the
 // k-th new element (by gap, root id descending, depth in its run) lands at gap + k.
 #include "am355_resorder.h"
@@ -25,6 +32,7 @@ namespace am355 {
 static size_t al256(size_t b) { return carve_round(b); }
 constexpr uint16_t RO_NOT_ELEM = 0xfffe, RO_ROOT = 0xffff;   // r.par: not a new list element; a new element whose reference element is old (or a list head)
 
+// (n_obj: the objects the stage may come to hold -- with r.new_objects the stored ones + one per row of the batch)
 size_t resorder_bytes(uint32_t n_new, uint32_t n_obj) {
   return 3 * al256(4 * ((size_t)n_new + 1)) + al256(2 * ((size_t)n_new + 1)) + al256(4 * ((size_t)n_obj + 2)) + al256(64) + 256;
 }
@@ -52,6 +60,48 @@ void resorder_positions(const MergeBufs& b, uint32_t n_list, uint32_t* pos_of, h
   if (n_list) AM355_LAUNCH_INDEPENDENT(kr_positions, dim3((n_list + BLOCK - 1) / BLOCK), dim3(BLOCK), st, b, n_list, pos_of);
 }
 
+// The objects the batch makes, in front of its first chunk (a row of a later chunk may live in an object made in an earlier one): one
+// workgroup over the rows [T0, T0 + n_new), n_new known at launch. A make row by k_compact_rows' rule; the k-th in row order is object
+// n_obj + k (r.n_obj counts _root). Writes what k_compact_rows' object_table_entry writes for the batch's rows -- obj_index, the table
+// entry --, an empty stretch at the end of the stored order for each, and their count (words[5]).
+constexpr uint32_t NO_THREADS = 1024;
+__global__ __launch_bounds__(NO_THREADS) void kr_new_objects(MergeBufs b, ResOrderBufs r) {
+  __shared__ uint32_t s_tot[NO_THREADS / WAVE];
+  const uint32_t t0 = threadIdx.x, lane = t0 & (WAVE - 1), wv = t0 / WAVE;
+  const OpCols& o = b.ops;
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < r.n_new; base += NO_THREADS) {
+    const uint32_t t = base + t0, g = r.T0 + t;
+    const bool in_range = t < r.n_new;
+    const uint8_t kind = in_range ? b.kind[g] : (uint8_t)K_NONE;
+    const bool is_make = kind != K_NONE && kind != K_DEL && (o.action[g] & 1) == 0;
+    const uint32_t incl = wave_incl_scan_u32(is_make ? 1u : 0u, lane);
+    if (lane == WAVE - 1) s_tot[wv] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+    for (uint32_t k = 0; k < NO_THREADS / WAVE; k++) { const uint32_t x = s_tot[k]; before += k < wv ? x : 0u; all += x; }
+    __syncthreads();
+    if (in_range) {
+      if (is_make) {
+        const uint32_t idx = r.n_obj + carry + before + incl - 1;
+        r.obj[idx] = am355_ir_object{o.id_ctr[g], o.id_actor[g], o.action[g], 0, 0, 0, 0, g};
+        b.obj_index[g] = idx;
+        b.obj_first_pos[idx] = r.n_list;
+        b.obj_n[idx] = 0;
+      } else {
+        b.obj_index[g] = NONE32;
+      }
+    }
+    carry += all;
+  }
+  if (t0 == 0) {
+    // (the entry behind the last object: the end of the order, as the prefix sum over the objects leaves it)
+    b.obj_first_pos[r.n_obj + carry] = r.n_list;
+    b.obj_n[r.n_obj + carry] = 0;
+    r.words[5] = carry;
+  }
+}
+
 // one wavefront per new row: is the row one this path serves; the gap of a new element whose reference element is old
 constexpr uint32_t GAP_STEPS_MAX = 4096;   // 64 positions each: a scan past 262 k greater elements is left to the full ordering
 __global__ __launch_bounds__(WAVE) void kr_gaps(MergeBufs b, ResOrderBufs r) {
@@ -65,7 +115,9 @@ __global__ __launch_bounds__(WAVE) void kr_gaps(MergeBufs b, ResOrderBufs r) {
   // every list as it is: the caller then runs the map half of the merge alone (merge_run_maps). Every chunk's rows are looked at.
   // words[4]: some row IS a plain map row: it takes no part in the list order (a row like a deletion here), and the caller runs the map
   // half of the merge behind the in-place list merge.
-  const bool plain_map = plain_map_row(kind, a, o.key_len[g]);
+  // (r.new_objects: a make on a string key stands like one -- the object it makes has its table entry, its key's record comes from the map half)
+  const bool make = r.new_objects && kind != K_DEL && (a & 1) == 0;
+  const bool plain_map = plain_map_row(kind, a, o.key_len[g]) || (make && kind == K_MAP && o.key_len[g] != NONE32);
   if (lane == 0) r.words[plain_map ? 4 : 3] = 1;
   // (a chunk behind one that was refused: the order it would scan was never written)
   if (r.chunk && r.words[0]) return;
@@ -74,14 +126,16 @@ __global__ __launch_bounds__(WAVE) void kr_gaps(MergeBufs b, ResOrderBufs r) {
   const bool list_del = kind == K_DEL && o.key_len[g] == NONE32;
   if (plain_map && r.allow_maps) {}
   else if (!(kind == K_LIST_INS || kind == K_LIST_UPD || list_del)) refuse = true;   // other map rows (objects made, increments), foreign rows, rows k_resolve left without a kind
-  else if (kind != K_DEL && a != 1) refuse = true;                               // child objects (the object table grows), increments, links
+  else if (kind != K_DEL && a != 1 && !(make && kind == K_LIST_INS)) refuse = true;   // child objects (the object table grows; r.new_objects: an INSERT that makes one is an element like any other, an element assigned one is not served), increments, links
   else if (kind == K_LIST_INS) {
     const uint32_t parent = b.ref_row[g];
     const bool head = o.key_ctr[g] == 0;
     const uint32_t make_row = b.obj_row[g];
     if (!head && parent == NONE32) refuse = true;
-    else if (make_row != NONE32 && make_row >= r.T0) refuse = true;   // (an object this batch makes: it has no index in the object table yet -- its make row refuses the batch anyway)
+    else if (make_row != NONE32 && make_row >= r.T0 && !r.new_objects) refuse = true;   // (an object this batch makes: it has no index in the object table yet -- its make row refuses the batch anyway)
+    else if (obj_index_of(b, make_row) >= r.n_obj + r.words[5]) refuse = true;   // (its make row is none kr_new_objects counted: never expected)
     else if (head || parent < r.T0) {
+      // (an object this batch makes: the index, first position and count kr_new_objects and the chunks in front left)
       const uint32_t oi = obj_index_of(b, make_row);
       const uint32_t first = b.obj_first_pos[oi], end = first + b.obj_n[oi];
       uint32_t q = head ? first : r.pos_of[parent] + 1;
@@ -306,13 +360,14 @@ __device__ __forceinline__ void shift_item(const MergeBufs& b, const ResOrderBuf
 __device__ __forceinline__ void objects_block(const MergeBufs& b, const ResOrderBufs& r) {
   __shared__ uint32_t s_red[BLOCK / WAVE];
   uint32_t carry = 0;
-  for (uint32_t base = 0; base <= r.n_obj; base += BLOCK) {
+  const uint32_t n_obj = r.n_obj + r.words[5];   // (with the objects the batch makes: kr_new_objects)
+  for (uint32_t base = 0; base <= n_obj; base += BLOCK) {
     const uint32_t oi = base + threadIdx.x;
-    const uint32_t add = oi <= r.n_obj ? r.obj_add[oi] : 0u;
-    if (oi <= r.n_obj && add) r.obj_add[oi] = 0;   // (the next chunk counts anew)
+    const uint32_t add = oi <= n_obj ? r.obj_add[oi] : 0u;
+    if (oi <= n_obj && add) r.obj_add[oi] = 0;   // (the next chunk counts anew)
     uint32_t total;
     const uint32_t ex = block_exclusive_scan_u32(add, s_red, &total);
-    if (oi <= r.n_obj) {
+    if (oi <= n_obj) {
       b.obj_first_pos[oi] += carry + ex;
       b.obj_n[oi] += add;
     }
@@ -326,7 +381,7 @@ __device__ __forceinline__ void kinds_item(const MergeBufs& b, const ResOrderBuf
   const uint32_t g = r.T0 + t;
   const OpCols& o = b.ops;
   const uint8_t kind = b.kind[g];
-  if (kind == K_LIST_INS) { if (b.succ_cnt[g] == 0) b.kind[g] = K_LIST_INS_VIS; return; }   // (valued: kr_gaps admitted `set` rows only)
+  if (kind == K_LIST_INS) { if (b.succ_cnt[g] == 0) b.kind[g] = K_LIST_INS_VIS; return; }   // (valued, as k_emit judges it: kr_gaps admitted `set` rows and, with r.new_objects, make rows -- both carry a value; no increment, no link)
   for (uint32_t k = 0; k < o.pred_num[g]; k++) {
     const uint32_t pr = row_of(b, o.pred_actor[o.pred_first[g] + k], o.pred_ctr[o.pred_first[g] + k]);
     if (pr != NONE32 && b.kind[pr] == K_LIST_INS_VIS) b.kind[pr] = K_LIST_INS;   // (it has a successor now: this row)
@@ -362,6 +417,7 @@ void resorder_run(MergeBufs& b, ResOrderBufs& r, hipStream_t st, bool* final_in_
   uint32_t* dst = r.order_new;
   MergeBufs bb = b;
   ResOrderBufs rr = r;
+  if (r.new_objects) hipLaunchKernelGGL(kr_new_objects, dim3(1), dim3(NO_THREADS), 0, st, bb, rr);   // (the whole batch, in front of the first chunk)
   for (uint32_t c = 0; c < chunks; c++) {
     rr.chunk = c;
     rr.T0 = T0 + c * rows;

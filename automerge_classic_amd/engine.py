@@ -116,6 +116,11 @@ def _bind(path):
         L.am355_set_resident_new_actors.restype = ctypes.c_int
         L.am355_resident_new_actor_calls.argtypes = [vp, vp]
         L.am355_resident_new_actor_calls.restype = ctypes.c_int
+    if hasattr(L, "am355_set_resident_new_objects"):
+        L.am355_set_resident_new_objects.argtypes = [vp, ctypes.c_int]
+        L.am355_set_resident_new_objects.restype = ctypes.c_int
+        L.am355_resident_new_object_calls.argtypes = [vp, vp]
+        L.am355_resident_new_object_calls.restype = ctypes.c_int
     if hasattr(L, "am355_set_resident_map_merge"):
         L.am355_set_resident_map_merge.argtypes = [vp, ctypes.c_int]
         L.am355_set_resident_map_merge.restype = ctypes.c_int
@@ -388,6 +393,19 @@ class Engine:
         the path of before)."""
         out = (ctypes.c_uint64 * 2)()
         self._check(self._L.am355_resident_map_merge_calls(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def set_resident_new_objects(self, on):
+        """on: a batch that makes objects (`doc.cards.push({...})`, `doc.notes = new Text(...)`) is merged into the resident state in place
+        -- the new objects take the next indexes of the stored object table and the end of the stored list order -- instead of every
+        list being ranked and every table rebuilt by merge_run. Off by default."""
+        self._check(self._L.am355_set_resident_new_objects(self._h, 1 if on else 0))
+
+    def resident_new_object_calls(self):
+        """(resident calls whose batch made at least one object and was served without merge_run, calls that tried, declined and went on
+        with merge_run)."""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self._L.am355_resident_new_object_calls(self._h, out))
         return int(out[0]), int(out[1])
 
     def raw(self):

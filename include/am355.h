@@ -380,6 +380,25 @@ int am355_resident_new_actor_calls(const am355_ctx *ctx, uint64_t out[2]);
  * and declined, and were served by the path of before (out[1]). */
 int am355_set_resident_map_merge(am355_ctx *ctx, int on);
 int am355_resident_map_merge_calls(const am355_ctx *ctx, uint64_t out[2]);
+/* Batches that MAKE objects (`doc.cards.push({...})`: a list insert with makeMap and the `set`s inside the new map; `doc.notes = new
+ * Text('...')`: a makeText on a key and inserts into the new object) merged into the resident state in place. By default such a batch
+ * runs every kernel of merge_run over every row of the document: every list ranked anew, every table rebuilt. on != 0: one pass over the
+ * batch's rows gives the objects it makes the next indexes of the stored object table -- the table is in row order of the make rows and
+ * the batch's rows stand behind all kept rows, so nothing kept is renumbered -- and the next first positions of the stored list order,
+ * which is grouped by object index: the elements of a new object land at its END and no kept object moves because of them. A list
+ * insert that makes an object is then a list element like any other, and a make on a string key and the `set` / `del` rows inside maps
+ * (new ones too) stand like plain map rows: the list rows are merged into the stored order, the map half of the merge runs behind them
+ * (by merge_run_maps also where am355_set_resident_map_merge is on: its stored records do not take makes). Left to merge_run as before
+ * (out[1]): a list element ASSIGNED an object (`list[3] = {}`), any `inc` or `link` row in the batch, a make row that names no valid
+ * object, and what the in-place list merge declines anyway (a new element with two new children, a gap scan past its limit, more chunks
+ * than the path takes). A document without any list element never tries. AM355_RESORDER_VERIFY=1 in the environment: the next rebuild of
+ * the whole-document tables compares every object's id, type, make row, first position and element count with what these calls left.
+ * Off by default; no environment variable. What the reference has in this place: mergeDocChangeOps inserts the ops into the blocks it
+ * visits and updates objectMeta for a make op (new.js:1052-1290, 1118-1131).
+ * am355_resident_new_object_calls: resident calls whose batch made at least one object and was served without merge_run (out[0]);
+ * calls with the switch on whose batch made an object, were tried in place, were declined and went on with merge_run (out[1]). */
+int am355_set_resident_new_objects(am355_ctx *ctx, int on);
+int am355_resident_new_object_calls(const am355_ctx *ctx, uint64_t out[2]);
 
 /* For bindings that mirror per-state tables of the context in their own memory (the N-API addon: BackendDoc.changes, their hashes and
  * the raw arena, backend/new.js:1847, 1855-1879) and must not copy all of them for every one-change Backend.applyChanges:
