@@ -182,6 +182,19 @@ extern "C" int am355_resident_new_object_calls(const am355_ctx* c, uint64_t out[
   return AM355_OK;
 }
 
+extern "C" int am355_set_resident_counters(am355_ctx* c, int on) {
+  if (!c) return AM355_E_ARG;
+  c->resident_counters = on != 0;
+  return AM355_OK;
+}
+
+extern "C" int am355_resident_counter_calls(const am355_ctx* c, uint64_t out[2]) {
+  if (!c || !out) return AM355_E_ARG;
+  out[0] = c->n_counter_calls;
+  out[1] = c->n_counter_declined;
+  return AM355_OK;
+}
+
 extern "C" int am355_get_raw(const am355_ctx* c, const uint8_t** arena, const uint64_t** offsets, uint32_t* n) {
   if (!c || !c->staged) return AM355_E_STATE;
   if (arena) *arena = c->raw.data();

@@ -515,6 +515,10 @@ struct am355_ctx {
   // object table and the end of the stored order (am355_resorder.hip kr_new_objects) -- instead of by merge_run over every row
   bool resident_new_objects = false;
   uint64_t n_new_object_calls = 0, n_new_object_declined = 0;   // resident calls that made objects and were served without merge_run | that tried and went on with merge_run
+  // am355_set_resident_counters: the increments of map counters in a batch are written into the stored map records in place
+  // (am355_merge.hip kr_counters) instead of refusing the in-place stages
+  bool resident_counters = false;
+  uint64_t n_counter_calls = 0, n_counter_declined = 0;   // resident calls whose increments were written in place, no merge_run, no map half | where the stage declined
   DevBuf d_map_alt, d_mapmerge;                    // the other map table | the stage's scratch
   am355_ir_map* map_alt_ptr = nullptr;             // whichever of the two map tables c->ir.map does NOT point to (null: not set up since the last carve)
   std::string resident_why;                        // why the last attempt fell back (diagnostics, AM355_TRACE)

@@ -198,22 +198,7 @@ __global__ __launch_bounds__(BLOCK) void kd_touch(MergeBufs b, DeltaBufs d) {
   }
 }
 
-// The counter an increment feeds: among its preds the counter `set` with the greatest id (counterStates[succOp] = counterState, the
-// later assignment wins: new.js:944-950; k_resolve counts the increment for that row in inc_cnt / inc_sum). NONE32: none.
-__device__ __forceinline__ uint32_t inc_counter_of(const MergeBufs& b, uint32_t g) {
-  const OpCols& o = b.ops;
-  uint32_t fed = NONE32;
-  unsigned long long best = 0;
-  for (uint32_t k = 0; k < o.pred_num[g]; k++) {
-    const uint32_t pa = o.pred_actor[o.pred_first[g] + k], pc = o.pred_ctr[o.pred_first[g] + k];
-    const uint32_t r = row_of(b, pa, pc);
-    if (r == NONE32 || r >= g || o.action[r] != 1 || (o.val_tl[r] & 15) != 8) continue;
-    const unsigned long long id = pack_id(pc, pa);
-    if (fed == NONE32 || id > best) { fed = r; best = id; }
-  }
-  return fed;
-}
-
+// (inc_counter_of, the counter an increment feeds: am355_rows.h)
 __global__ __launch_bounds__(BLOCK) void kd_rows(MergeBufs b, DeltaBufs d) {
   uint32_t g = gtid();
   if (g >= b.n_ops) return;

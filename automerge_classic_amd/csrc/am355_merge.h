@@ -174,6 +174,13 @@ void mapmerge_find(MergeBufs& b, const PatchIR& ir, MapMergeBufs& m, hipStream_t
 // streamed into m.map_new, the objects' map ranges rewritten. n_new_rec / max_key: words[MM_N_NEW] / words[MM_MAX_KEY].
 void mapmerge_write(MergeBufs& b, PatchIR& ir, MapMergeBufs& m, uint32_t n_new_rec, uint32_t max_key, hipStream_t st);
 
+// ---- resident counters (am355_set_resident_counters; am355_merge.hip "resident counters") ----------------------------------------------
+// The increments of map counters among the rows [T0, T0 + n_new) (resolved) written into the stored map records `map` in place: one
+// launch of kr_counters, a wavefront per row. words: the list stage's (ResOrderBufs.words) -- [7] is set when some increment is not
+// served (its key holds conflicting values, its counter is a row of this batch); nothing else of them is written.
+void counters_in_place(const MergeBufs& b, const am355_ir_object* obj, am355_ir_map* map, uint32_t n_obj, uint32_t n_map, uint32_t T0, uint32_t n_new,
+                       uint32_t* words, hipStream_t st);
+
 // Document load: whole-document patch of rows already in canonical order (pred_* arrays = succ lists). `b.counts` must be
 // cleared by the caller before the decode kernels run.
 void doc_patch(MergeBufs& b, PatchIR& ir, Counts* h_counts, hipStream_t st);

@@ -698,6 +698,66 @@ __global__ __launch_bounds__(BLOCK) void k_mm_write(PatchIR ir, MapMergeBufs m, 
   ir.obj[oi].map_end = end_new > begin_new ? end_new : 0u;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// resident counters: the increments of a batch written into the STORED map records (am355_set_resident_counters; replay_resident,
+// launched by resorder_run). An `inc` on a string key emits nothing itself (map_row_emits) and k_resolve has added it to its counter's
+// accumulators, so all it changes in the whole-document tables is the counter's own record: the total, the flag on the first increment,
+// and -- only where the key holds conflicting values, a counter standing under its last increment's id -- its place among them.
+// One wavefront per batch row, as kr_gaps has; a wave whose row is no counter row returns at once. The counter is found among the
+// row's preds (inc_counter_of), its object's stretch of the table in the object table, the key's first record by binary search, and
+// ONE 64-wide look at the records from there decides: the key holds no record (a deleted or overwritten counter: it does not emit,
+// before or after -- nothing to write), one record (the counter's: lane 0 writes map_record_of over it; somebody else's: nothing), or
+// more (conflicting values: declined, words[7] -- so are an increment with more than one pred and everything never expected). A key with more than a wavefront of records has
+// more than one: no second step, and MAP_GROUP_MAX is never reached. Several increments of one counter write the same final record:
+// plain stores, no atomics. A decline leaves at most final records behind, which the map half the caller then runs writes again.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(WAVE) void kr_counters(MergeBufs b, const am355_ir_object* obj, am355_ir_map* map, uint32_t n_obj, uint32_t n_map, uint32_t T0,
+                                                    uint32_t n_new, uint32_t* words) {
+  const uint32_t t = blockIdx.x, lane = threadIdx.x;
+  if (t >= n_new) return;
+  const uint32_t g = T0 + t;
+  const OpCols& o = b.ops;
+  if (b.kind[g] != K_MAP || o.action[g] != 5 || o.key_len[g] == NONE32) return;
+  if (words[0] && words[3]) return;   // (the list stage refused the batch: merge_run writes every table anew)
+  const uint32_t cr = inc_counter_of(b, g), orow = b.obj_row[g];
+  // the counter is a kept row of this object and key (one made in this batch comes with a `set`: the map half runs anyway), the
+  // object a stored one whose stretch lies inside the table
+  bool decline = cr == NONE32 || cr >= T0 || (orow != NONE32 && orow >= T0);
+  // (an increment with several preds -- conflicting values under the frontend's hands -- is a successor of every one of them, k_resolve:
+  // a pred that is not the counter it feeds may stop emitting because of it, which only the map half looks at)
+  if (o.pred_num[g] != 1) decline = true;
+  if (!decline) decline = b.kind[cr] != K_MAP || !same_obj(b, cr, g) || !same_key(b, cr, g);
+  const uint32_t oi = decline ? 0u : obj_index_of(b, orow);
+  if (oi >= n_obj) decline = true;
+  uint32_t lo = 0, end = 0;
+  if (!decline) {
+    lo = obj[oi].map_begin; end = obj[oi].map_end;
+    if (lo > end || end > n_map) decline = true;
+  }
+  if (decline) { if (lane == 0) words[7] = 1; return; }
+  const uint32_t koff = o.key_off[g], klen = o.key_len[g];
+  for (uint32_t hi = end; lo < hi;) {   // the first record of the object whose key is not in front of this row's
+    const uint32_t mid = (lo + hi) >> 1;
+    if (map_keys_order(b, map[mid].key_off, map[mid].key_len, koff, klen) < 0) lo = mid + 1; else hi = mid;
+  }
+  bool same = false, mine = false;
+  if (lo + lane < end) {
+    const am355_ir_map rec = map[lo + lane];
+    same = map_keys_order(b, rec.key_off, rec.key_len, koff, klen) == 0;
+    mine = same && rec.id_ctr == o.id_ctr[cr] && rec.id_actor == o.id_actor[cr];
+  }
+  const unsigned long long m_same = __ballot(same), m_mine = __ballot(mine);
+  const uint32_t n_rec = (uint32_t)__popcll(m_same);
+  if (lane != 0) return;
+  if (n_rec > 1) words[7] = 1;
+  else if (m_mine) map[lo + (uint32_t)__ffsll(m_mine) - 1] = map_record_of(b, cr);
+}
+
+void counters_in_place(const MergeBufs& b, const am355_ir_object* obj, am355_ir_map* map, uint32_t n_obj, uint32_t n_map, uint32_t T0, uint32_t n_new,
+                       uint32_t* words, hipStream_t st) {
+  if (n_new) hipLaunchKernelGGL(kr_counters, dim3(n_new), dim3(WAVE), 0, st, b, obj, map, n_obj, n_map, T0, n_new, words);
+}
+
 static int bits_for(uint64_t max_value) {
   int b = 1;
   while (b < 64 && (max_value >> b)) b++;

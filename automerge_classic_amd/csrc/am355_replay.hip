@@ -1144,6 +1144,7 @@ struct ResidentStages {
   bool map_merge_on = false, map_merge_fits = false, map_merge_alone = false;
   bool no_maps_only = false;             // AM355_NO_MAPS_ONLY (tests, A/B: read once per call)
   bool new_objects = false;              // am355_set_resident_new_objects, and the carve holds an object per row of the batch
+  bool counters = false;                 // am355_set_resident_counters (the list stage runs: kr_counters rides with it)
 };
 
 // Phase 1, preconditions. Reads the context; writes the sizes of `rb`, nothing of the context. Returns why the kept state or the mode
@@ -1458,6 +1459,9 @@ static int resident_bind_list_order(am355_ctx* c, const ResidentBatch& rb, Resid
   resorder_bind(ro, c->d_resorder.p, NN, obj_most);
   ro.new_objects = rs.new_objects ? 1u : 0u;
   ro.obj = c->ir.obj;
+  rs.counters = c->resident_counters;
+  ro.counters = rs.counters ? 1u : 0u;
+  ro.map = c->ir.map; ro.n_map = c->counts.n_map_emit;
   canary_arm();   // (AM355_CANARY=1 only)
   ro.T0 = (uint32_t)rb.old_ops; ro.n_new = NN; ro.n_list = rs.NL_old; ro.n_obj = rs.NO;
   ro.pos_of = c->d_pos.as<uint32_t>();
@@ -1529,25 +1533,25 @@ static int resident_map_find(am355_ctx* c, const ResidentBatch& rb, ResidentStag
   return AM355_OK;
 }
 
-// AM355_MAPMERGE_VERIFY (tests): the table just merged in place against merge_run_maps' table of the same rows, record by record,
-// and the objects' map ranges. Leaves the table from scratch in place (the same, or the call fails).
-static int resident_map_verify(am355_ctx* c, const MapMergeBufs& mm, uint32_t n_after, bool trace) {
+// AM355_MAPMERGE_VERIFY, AM355_COUNTERS_VERIFY (tests): the table just merged or rewritten in place against merge_run_maps' table of
+// the same rows, record by record, and the map ranges of the n_obj objects. Leaves the table from scratch in place (the same, or the call fails).
+static int resident_map_verify(am355_ctx* c, uint32_t n_obj, uint32_t n_after, bool trace) {
   hipStream_t st = c->stream;
   Counts* hc = c->h_counts.as<Counts>();
   std::vector<am355_ir_map> got(n_after), want(n_after);
-  std::vector<am355_ir_object> got_obj(mm.n_obj), want_obj(mm.n_obj);
+  std::vector<am355_ir_object> got_obj(n_obj), want_obj(n_obj);
   HIPCHK(c, hipStreamSynchronize(st));
   if (n_after) HIPCHK(c, hipMemcpy(got.data(), c->ir.map, sizeof(am355_ir_map) * (size_t)n_after, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(got_obj.data(), c->ir.obj, sizeof(am355_ir_object) * (size_t)mm.n_obj, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(got_obj.data(), c->ir.obj, sizeof(am355_ir_object) * (size_t)n_obj, hipMemcpyDeviceToHost));
   merge_run_maps(c->mb, c->ir, hc, st);
   HIPCHK(c, hipStreamSynchronize(st));
   if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
   bool same = hc->n_map_emit == n_after;
   if (same) {
     if (n_after) HIPCHK(c, hipMemcpy(want.data(), c->ir.map, sizeof(am355_ir_map) * (size_t)n_after, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(want_obj.data(), c->ir.obj, sizeof(am355_ir_object) * (size_t)mm.n_obj, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(want_obj.data(), c->ir.obj, sizeof(am355_ir_object) * (size_t)n_obj, hipMemcpyDeviceToHost));
     same = !n_after || memcmp(got.data(), want.data(), sizeof(am355_ir_map) * (size_t)n_after) == 0;
-    for (uint32_t k = 0; same && k < mm.n_obj; k++) same = got_obj[k].map_begin == want_obj[k].map_begin && got_obj[k].map_end == want_obj[k].map_end;
+    for (uint32_t k = 0; same && k < n_obj; k++) same = got_obj[k].map_begin == want_obj[k].map_begin && got_obj[k].map_end == want_obj[k].map_end;
   }
   if (trace && !same) fprintf(stderr, "resident: map table verify: %u records in place, %u from scratch\n", n_after, hc->n_map_emit);
   if (!same) return fail(c, AM355_E_DEVICE, "internal: the map table merged in place differs from the table computed from scratch");
@@ -1595,7 +1599,7 @@ static int resident_map_rows_in_place(am355_ctx* c, const ResidentBatch& rb, Res
   c->n_map_merge_calls++;
   served = true;
   lap("map table merged in place");
-  if (getenv("AM355_MAPMERGE_VERIFY")) return resident_map_verify(c, mm, n_after, lap.on);   // (tests; read per call)
+  if (getenv("AM355_MAPMERGE_VERIFY")) return resident_map_verify(c, mm.n_obj, n_after, lap.on);   // (tests; read per call)
   return AM355_OK;
 }
 
@@ -1605,11 +1609,13 @@ static int resident_map_rows_in_place(am355_ctx* c, const ResidentBatch& rb, Res
 // made: objects the batch makes (am355_set_resident_new_objects). The stored map records take no makes: such a batch is declined there
 // and merge_run_maps writes the object table with the new objects -- at the indexes kr_new_objects gave them, or the call fails --;
 // the context's object count grows and the call is counted.
-static int resident_map_half(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const ResidentLap& lap, uint32_t made = 0) {
+// incs: the batch holds counter rows (am355_set_resident_counters): the stored map records take no increments either -- k_mm_rows looks at
+// plain map rows only -- and are declined the same way.
+static int resident_map_half(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const ResidentLap& lap, uint32_t made = 0, bool incs = false) {
   bool in_place = false;
-  if (made && rs.map_merge_on) {
+  if ((made || incs) && rs.map_merge_on) {
     c->n_map_merge_declined++;
-    lap("map table: the batch makes objects, left to the map half of the merge");
+    lap(made ? "map table: the batch makes objects, left to the map half of the merge" : "map table: the batch increments counters, left to the map half of the merge");
   } else {
     const int mrc = resident_map_rows_in_place(c, rb, rs, lap, false, in_place);
     if (mrc) return mrc;
@@ -1758,6 +1764,13 @@ static int resident_list_verdict(am355_ctx* c, const ResidentBatch& rb, Resident
   if (hw[8]) return error_for_flags(c, hw[8], "op set rejected");
   const uint32_t made = rs.new_objects ? hw[5] : 0u;   // objects the batch makes (kr_new_objects: in the words the host waits for anyway)
   if (made && lap.on) fprintf(stderr, "resident: %-30s %u\n", "objects the batch makes", made);
+  // counter rows (am355_set_resident_counters; kr_gaps words[6]): kr_counters has written the records of the counters they feed into the
+  // stored table, or declined (words[7]). Beside plain map rows or makes the map half runs anyway and judges counters by k_emit's rule:
+  // such a call counts in neither word. Alone, or beside list rows: served without a map half, or declined and left to it.
+  const bool incs = rs.counters && hw[6] != 0;
+  const bool incs_alone = incs && !hw[4] && !made;
+  const bool incs_served = incs_alone && hw[7] == 0;
+  if (incs_alone && !incs_served) { c->n_counter_declined++; lap("counters: declined, left to the map half of the merge"); }
   if (hw[0] == 0) {
     // the order after the batch is the state's order from here on: in the other buffer after an odd number of chunks
     if (rs.final_in_new) {
@@ -1778,24 +1791,46 @@ static int resident_list_verdict(am355_ctx* c, const ResidentBatch& rb, Resident
     c->batch_list_only = true;
     merged_in_place = true;
     lap("list order merged in place");
-    if (hw[4] || made) {
+    if (hw[4] || made || (incs && !incs_served)) {
       // plain map rows beside the list edits (text typed and a key assigned in one change): the map half of the merge behind the
       // in-place list merge -- the map records and the object table's map ranges change, the delta stage runs its map kernels.
       // A batch that made objects always: the new objects have their entries and indexes (kr_new_objects), their map ranges and the
       // records of the new maps come from here
-      { const int mrc = resident_map_half(c, rb, rs, lap, made); if (mrc) return mrc; }
+      { const int mrc = resident_map_half(c, rb, rs, lap, made, incs); if (mrc) return mrc; }
       c->h_tables_current = false;
       c->ir_copy_enqueued = 0;
       c->batch_list_only = false;
       c->n_maps_only_calls++;
+    } else if (incs_served) {
+      // increments beside the list edits (a vote and typing in one change): the counters' records are rewritten where they stand; the
+      // call's patch carries the counters, so the delta stage runs its map kernels and the host's copy of the tables is not current
+      c->h_tables_current = false;
+      c->ir_copy_enqueued = 0;
+      c->batch_list_only = false;
+      c->n_counter_calls++;
+      lap("counters written into the stored map records");
+      if (getenv("AM355_COUNTERS_VERIFY")) { const int vrc = resident_map_verify(c, c->counts.n_objects, c->counts.n_map_emit, lap.on); if (vrc) return vrc; }   // (tests; read per call)
     }
+  } else if (hw[3] == 0 && incs_served) {
+    // a batch of counter rows only: no list changes -- kr_order refused for want of a list row, the stored order, positions and element
+    // counts stay -- and no map half: the counters' records are rewritten where they stand. The edit tables are stale from here on, as
+    // behind the map half alone
+    c->ir_stale = true;
+    c->ir_fetched = false;
+    c->h_tables_current = false;
+    c->ir_copy_enqueued = 0;
+    c->pos_valid = true;   // (the positions this call read or rebuilt: the order did not change)
+    c->n_counter_calls++;
+    maps_only = true;      // (no merge_run; am355_resident_maps_only_calls does not count the call: no map half ran)
+    lap("counters written into the stored map records");
+    if (getenv("AM355_COUNTERS_VERIFY")) { const int vrc = resident_map_verify(c, c->counts.n_objects, c->counts.n_map_emit, lap.on); if (vrc) return vrc; }   // (tests; read per call)
   } else if (hw[3] == 0 && !rs.no_maps_only) {
     // a batch of plain map rows (`set` / `del` on string keys): no list changes -- the stored order, positions and element counts stay,
     // the map half of the merge runs alone (visibility, object table, map records in patch order); the whole-document edit tables are
     // stale from here on, as after an in-place list merge
     // (am355_set_resident_new_objects: makes on string keys and rows inside the new maps too -- the new objects have their empty
     // stretches at the end of the order all the same, kr_new_objects)
-    { const int mrc = resident_map_half(c, rb, rs, lap, made); if (mrc) return mrc; }
+    { const int mrc = resident_map_half(c, rb, rs, lap, made, incs); if (mrc) return mrc; }
     c->ir_stale = true;
     c->ir_fetched = false;
     c->n_maps_only_calls++;

@@ -19,6 +19,10 @@ struct ResOrderBufs {
   uint32_t new_objects;      // the batch may make objects (kr_new_objects gives them the indexes n_obj ... in row order): a list insert that
                              // makes one is a list element like any other, a make on a string key stands like a plain map row
   am355_ir_object* obj;      // [n_obj + n_new] the object table (new_objects: the entries of the objects the batch makes are written here)
+  uint32_t counters;         // an increment of a map counter (`inc` on a string key) is a counter row: no part of the list order, its counter's
+                             // stored map record rewritten in place (kr_counters, am355_merge.hip) -- am355_set_resident_counters
+  am355_ir_map* map;         // [n_map] the stored map records (counters: kr_counters writes the records of the counters the batch increments)
+  uint32_t n_map;
   uint32_t* pos_of;          // [row capacity] position of every element row in b.order (kept between calls)
   uint32_t* order_new;       // [row capacity + 2] the order after the call (the caller swaps it with b.order)
   uint32_t* gap;             // [n_new] a new element whose reference element is old / a head: the old position it goes in front of
@@ -29,7 +33,9 @@ struct ResOrderBufs {
   uint32_t* words;           // [8] (cleared by the caller): [0] != 0: not served here (the caller orders all lists anew), [1] new
                              // elements of the last chunk, [2] elements in front of them: the order holds [1] + [2] after the call;
                              // [3] != 0: some row of the batch is not a plain map row, [4] != 0: some row is one (kr_gaps);
-                             // [5]: objects the batch makes (kr_new_objects; 0 without new_objects)
+                             // [5]: objects the batch makes (kr_new_objects; 0 without new_objects);
+                             // [6] != 0: some row is a counter row (kr_gaps; never without counters), [7] != 0: kr_counters declined --
+                             // the stored map records do not hold the batch's increments, the caller runs the map half
   HostSignals* sig;          // the words + Counts.flags for the host through pinned memory (HostSignals.resorder), nullptr: the caller copies them
   uint32_t sig_seq;
 };

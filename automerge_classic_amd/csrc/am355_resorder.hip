@@ -21,6 +21,9 @@
 // insert that makes an object is then an element like any other, a head insert into a new object finds first == end == the end of
 // the order (several new objects share that gap: the object in front first, kr_order), and a make on a string key stands like a plain
 // map row -- the caller runs the map half behind the list merge whenever words[5] says the batch made objects.
+// Increments of map counters (r.counters; am355_set_resident_counters): an `inc` on a string key takes no part in the order either and
+// changes one stored map record, its counter's -- kr_counters (am355_merge.hip) rewrites it in place, launched once for the whole batch
+// in front of the last chunk's kr_apply (words[6] / words[7]); no map half follows from such a row.
 // The order after the batch is then a MERGE: an old element at position p moves up by the number of new elements with gap <= p, the
 // k-th new element (by gap, root id descending, depth in its run) lands at gap + k.
 #include "am355_resorder.h"
@@ -118,13 +121,19 @@ __global__ __launch_bounds__(WAVE) void kr_gaps(MergeBufs b, ResOrderBufs r) {
   // (r.new_objects: a make on a string key stands like one -- the object it makes has its table entry, its key's record comes from the map half)
   const bool make = r.new_objects && kind != K_DEL && (a & 1) == 0;
   const bool plain_map = plain_map_row(kind, a, o.key_len[g]) || (make && kind == K_MAP && o.key_len[g] != NONE32);
-  if (lane == 0) r.words[plain_map ? 4 : 3] = 1;
+  // words[6] (r.counters): the row is a counter row, an `inc` on a string key (k_resolve has validated it and added it to its counter's
+  // accumulators; it emits nothing itself): no part of the list order either, and all it changes in the whole-document tables is its
+  // counter's stored map record -- kr_counters, launched once behind the last chunk's kr_order. It sets neither words[3] nor words[4]:
+  // a batch of counter rows only leaves the lists AND the map half alone. An `inc` on a list element stays refused below.
+  const bool counter_row = r.counters && kind == K_MAP && a == 5 && o.key_len[g] != NONE32;
+  if (lane == 0) r.words[counter_row ? 6 : plain_map ? 4 : 3] = 1;
   // (a chunk behind one that was refused: the order it would scan was never written)
   if (r.chunk && r.words[0]) return;
   uint32_t gap = NONE32;
   bool refuse = false;
   const bool list_del = kind == K_DEL && o.key_len[g] == NONE32;
-  if (plain_map && r.allow_maps) {}
+  if (counter_row) {}   // (whether or not allow_maps: no map half follows from it)
+  else if (plain_map && r.allow_maps) {}
   else if (!(kind == K_LIST_INS || kind == K_LIST_UPD || list_del)) refuse = true;   // other map rows (objects made, increments), foreign rows, rows k_resolve left without a kind
   else if (kind != K_DEL && a != 1 && !(make && kind == K_LIST_INS)) refuse = true;   // child objects (the object table grows; r.new_objects: an INSERT that makes one is an element like any other, an element assigned one is not served), increments, links
   else if (kind == K_LIST_INS) {
@@ -427,6 +436,9 @@ void resorder_run(MergeBufs& b, ResOrderBufs& r, hipStream_t st, bool* final_in_
     rr.order_new = dst;
     hipLaunchKernelGGL(kr_gaps, dim3(rr.n_new), dim3(WAVE), 0, st, bb, rr);
     hipLaunchKernelGGL(kr_order, dim3(1), dim3(RO_THREADS), 0, st, bb, rr);
+    // (the counters the WHOLE batch increments, once: behind the resolution and the last verdict of the list stage, in front of the
+    // kr_apply that sends the words -- its own verdict, words[7], rides with them)
+    if (r.counters && c + 1 == chunks) counters_in_place(b, r.obj, r.map, r.n_obj, r.n_map, T0, n_all, r.words, st);
     const uint32_t n_list_most = r.n_list + c * rows;   // (what the running count can have reached)
     const uint32_t most = n_list_most > rr.n_new ? n_list_most : rr.n_new;
     const uint32_t shift_blocks = (most + BLOCK - 1) / BLOCK, kind_blocks = (rr.n_new + BLOCK - 1) / BLOCK;

@@ -1,4 +1,4 @@
-// Device helpers over the op rows and the merge results that more than one stage uses (am355_merge.hip, am355_delta.hip).
+// Device helpers over the op rows and the merge results that more than one stage uses (am355_merge.hip, am355_delta.hip, am355_resorder.hip).
 #pragma once
 #include "am355_merge.h"
 
@@ -54,6 +54,22 @@ __device__ __forceinline__ bool plain_map_row(uint8_t kind, uint32_t action, uin
 }
 
 __device__ __forceinline__ uint32_t obj_index_of(const MergeBufs& b, uint32_t make_row) { return make_row == NONE32 ? 0 : b.obj_index[make_row]; }
+
+// The counter an increment feeds: among its preds the counter `set` with the greatest id (counterStates[succOp] = counterState, the
+// later assignment wins: new.js:944-950; k_resolve counts the increment for that row in inc_cnt / inc_sum). NONE32: none.
+__device__ __forceinline__ uint32_t inc_counter_of(const MergeBufs& b, uint32_t g) {
+  const OpCols& o = b.ops;
+  uint32_t fed = NONE32;
+  unsigned long long best = 0;
+  for (uint32_t k = 0; k < o.pred_num[g]; k++) {
+    const uint32_t pa = o.pred_actor[o.pred_first[g] + k], pc = o.pred_ctr[o.pred_first[g] + k];
+    const uint32_t r = row_of(b, pa, pc);
+    if (r == NONE32 || r >= g || o.action[r] != 1 || (o.val_tl[r] & 15) != 8) continue;
+    const unsigned long long id = pack_id(pc, pa);
+    if (fed == NONE32 || id > best) { fed = r; best = id; }
+  }
+  return fed;
+}
 
 // JS compares strings by UTF-16 code units (new.js:84). On valid UTF-8 that equals byte order except that
 // supplementary-plane characters (lead bytes F0..F4) sort below U+E000..U+FFFF (lead bytes EE, EF): remap.

@@ -121,6 +121,11 @@ def _bind(path):
         L.am355_set_resident_new_objects.restype = ctypes.c_int
         L.am355_resident_new_object_calls.argtypes = [vp, vp]
         L.am355_resident_new_object_calls.restype = ctypes.c_int
+    if hasattr(L, "am355_set_resident_counters"):
+        L.am355_set_resident_counters.argtypes = [vp, ctypes.c_int]
+        L.am355_set_resident_counters.restype = ctypes.c_int
+        L.am355_resident_counter_calls.argtypes = [vp, vp]
+        L.am355_resident_counter_calls.restype = ctypes.c_int
     if hasattr(L, "am355_set_resident_map_merge"):
         L.am355_set_resident_map_merge.argtypes = [vp, ctypes.c_int]
         L.am355_set_resident_map_merge.restype = ctypes.c_int
@@ -406,6 +411,19 @@ class Engine:
         with merge_run)."""
         out = (ctypes.c_uint64 * 2)()
         self._check(self._L.am355_resident_new_object_calls(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def set_resident_counters(self, on):
+        """on: the increments of map counters in a batch (`doc.votes.increment()`) are written into the stored map records in place --
+        the rest of the batch is merged in place as before -- instead of the call running merge_run over the whole document. Off by
+        default."""
+        self._check(self._L.am355_set_resident_counters(self._h, 1 if on else 0))
+
+    def resident_counter_calls(self):
+        """(resident calls whose increments were written into the stored map records in place, with no merge_run and no map half; calls
+        where the stage tried and declined, served by the map half)."""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self._L.am355_resident_counter_calls(self._h, out))
         return int(out[0]), int(out[1])
 
     def raw(self):

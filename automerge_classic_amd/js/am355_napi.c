@@ -390,6 +390,39 @@ static napi_value js_resident_new_object_calls(napi_env env, napi_callback_info 
   return out;
 }
 
+/* setResidentCounters(ctx, on): am355_set_resident_counters (the increments of map counters in a batch are written into the stored map
+   records in place instead of every list being ranked and every table rebuilt) */
+static napi_value js_set_resident_counters(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  bool on = true;
+  if (argc > 1) NAPI_CALL(env, napi_get_value_bool(env, argv[1], &on));
+  int rc = am355_set_resident_counters(ctx, on ? 1 : 0);
+  if (rc) return throw_engine(env, ctx, rc);
+  return NULL;
+}
+
+/* residentCounterCalls(ctx) -> [served in place, tried and declined]: am355_resident_counter_calls */
+static napi_value js_resident_counter_calls(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1], out, v;
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  uint64_t w[2] = {0, 0};
+  int rc = am355_resident_counter_calls(ctx, w);
+  if (rc) return throw_engine(env, ctx, rc);
+  NAPI_CALL(env, napi_create_array_with_length(env, 2, &out));
+  for (uint32_t k = 0; k < 2; k++) {
+    NAPI_CALL(env, napi_create_double(env, (double)w[k], &v));
+    NAPI_CALL(env, napi_set_element(env, out, k, v));
+  }
+  return out;
+}
+
 /* hashGraphKnown(ctx, set) -> boolean: am355_hash_graph_known (set: 1 / 0 / -1 = only ask) */
 static napi_value js_hash_graph_known(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -835,6 +868,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"residentMapMergeCalls", NULL, js_resident_map_merge_calls, NULL, NULL, NULL, napi_enumerable, NULL},
       {"setResidentNewObjects", NULL, js_set_resident_new_objects, NULL, NULL, NULL, napi_enumerable, NULL},
       {"residentNewObjectCalls", NULL, js_resident_new_object_calls, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"setResidentCounters", NULL, js_set_resident_counters, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"residentCounterCalls", NULL, js_resident_counter_calls, NULL, NULL, NULL, napi_enumerable, NULL},
       {"depGraph", NULL, js_dep_graph, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomBuild", NULL, js_bloom_build, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomProbe", NULL, js_bloom_probe, NULL, NULL, NULL, napi_enumerable, NULL},

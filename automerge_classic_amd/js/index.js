@@ -22,6 +22,7 @@ const JS_ONLY = process.env.MI355X_BACKEND_JS_ONLY === '1'
 const HYDRATE_FROM_DOC = process.env.MI355X_HYDRATE === 'doc'
 const MAP_MERGE = process.env.MI355X_MAP_MERGE === '1'   // am355_set_resident_map_merge for every context of this module
 const NEW_OBJECTS = process.env.MI355X_NEW_OBJECTS !== '0'   // am355_set_resident_new_objects for every context of this module (MI355X_NEW_OBJECTS=0: off, for A/B)
+const COUNTERS = process.env.MI355X_COUNTERS !== '0'   // am355_set_resident_counters for every context of this module (MI355X_COUNTERS=0: off, for A/B)
 const PATCH_VIA_JSON = process.env.MI355X_PATCH_VIA_JSON === '1'   // A/B: JSON text rendered by the engine + JSON.parse
 const { materialize } = require('./materialize.js')
 let addon = null, ctx = null
@@ -36,6 +37,7 @@ if (!JS_ONLY) {
   ctx = addon.create(parseInt(process.env.MI355X_DEVICE || '0'))   // throws without an MI355X
   if (MAP_MERGE) addon.setResidentMapMerge(ctx, true)   // (as for every context acquireContext makes, see there)
   if (NEW_OBJECTS) addon.setResidentNewObjects(ctx, true)
+  if (COUNTERS) addon.setResidentCounters(ctx, true)
   contexts.push({ ctx, generation: 0, used: 0 })
 }
 
@@ -97,6 +99,10 @@ function acquireContext() {
     // order -- instead of every list being ranked and every table rebuilt (the reference inserts the ops into the blocks it visits,
     // new.js:1052-1290); measured faster than merge_run in every case timed, profiles/new_objects_apply_timings.txt: on unless MI355X_NEW_OBJECTS=0
     if (NEW_OBJECTS) addon.setResidentNewObjects(e.ctx, true)
+    // a counter increment (`doc.votes.increment()`) rewrites the counter's stored map record in place instead of every list being ranked
+    // and every table rebuilt (the reference adds the increment to the counter's succ list in the block it visits, new.js:1052-1290);
+    // measured faster than merge_run in every case timed, profiles/counter_apply_timings.txt: on unless MI355X_COUNTERS=0
+    if (COUNTERS) addon.setResidentCounters(e.ctx, true)
     contexts.push(e)
   } else {
     e = contexts.reduce((a, b) => (b.used < a.used ? b : a))
@@ -758,6 +764,8 @@ module.exports = {
   _residentMapMergeCalls: () => contexts.reduce((s, e) => { const w = addon.residentMapMergeCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),
   // [calls whose batch made objects and was served without merge_run, calls that tried and declined], over all contexts
   _residentNewObjectCalls: () => contexts.reduce((s, e) => { const w = addon.residentNewObjectCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),
+  // [calls whose counter increments were written into the stored map records in place, calls where that stage declined], over all contexts
+  _residentCounterCalls: () => contexts.reduce((s, e) => { const w = addon.residentCounterCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),
   _applyProfile: profile,
   _hydrate: hydrate   // (tests: the reference handle of an engine state, made the way the state came to be)
 }

@@ -399,6 +399,24 @@ int am355_resident_map_merge_calls(const am355_ctx *ctx, uint64_t out[2]);
  * calls with the switch on whose batch made an object, were tried in place, were declined and went on with merge_run (out[1]). */
 int am355_set_resident_new_objects(am355_ctx *ctx, int on);
 int am355_resident_new_object_calls(const am355_ctx *ctx, uint64_t out[2]);
+/* Increments of map counters (`doc.votes.increment()`: an `inc` row on a string key) written into the STORED map records in place. By
+ * default any `inc` row refuses the in-place stages above and the call runs merge_run over every row of the document. on != 0: such a
+ * row takes no part in the list order -- the rest of the batch is merged in place as before --, and one launch over the batch (a
+ * wavefront per row) finds the counter every increment feeds among its preds, the counter's object's stretch of the stored map table,
+ * the key's records by binary search, and rewrites the counter's record (total = value + increments, the counter flag) where the key
+ * holds that one record. Nothing is written for a counter that has no record (deleted or overwritten: it emits nothing before or
+ * after). Declined (out[1]) and served by the map half of the merge over the whole document: a key that holds conflicting values (the
+ * counter's record stands under its last increment's id and may have to move among them), an increment with more than one pred, a
+ * counter made in the same batch. A batch
+ * that also holds plain map rows or makes objects runs the map half anyway, which serves its increments too: counted in neither word.
+ * Left to merge_run as before: an `inc` on a list element, and -- the list stage never runs there -- a document without any list
+ * element. AM355_COUNTERS_VERIFY=1 in the environment: behind every call served, the map table and ranges are rebuilt by the map half
+ * and compared byte for byte. Off by default; no environment variable. What the reference has in this place: mergeDocChangeOps visits
+ * the block of the counter and adds the increment to its succ list (new.js:1052-1290, 937-965).
+ * am355_resident_counter_calls: resident calls whose increments were written into the stored map records in place, with no merge_run and
+ * no map half (out[0]); calls where the stage tried and declined (out[1]). */
+int am355_set_resident_counters(am355_ctx *ctx, int on);
+int am355_resident_counter_calls(const am355_ctx *ctx, uint64_t out[2]);
 
 /* For bindings that mirror per-state tables of the context in their own memory (the N-API addon: BackendDoc.changes, their hashes and
  * the raw arena, backend/new.js:1847, 1855-1879) and must not copy all of them for every one-change Backend.applyChanges:
