@@ -585,6 +585,8 @@ extern "C" int am355_save(am355_ctx* c, uint32_t flags, const uint8_t** out_byte
 extern "C" int am355_doc_changes(am355_ctx* c, uint32_t flags, const uint8_t** arena, const uint64_t** offsets, uint32_t* n, const uint8_t** hashes) { return guarded(c, [&]() { return doc_changes_impl(c, flags, arena, offsets, n, hashes); }); }
 extern "C" int am355_import_fragments(am355_ctx* c, const uint8_t* frags, const uint64_t* offsets, uint32_t world) { return guarded(c, [&]() { return import_fragments_impl(c, frags, offsets, world); }); }
 extern "C" int am355_apply_changes(am355_ctx* c, const uint8_t* arena, const uint64_t* offsets, uint32_t n) { return guarded(c, [&]() { return apply_changes_impl(c, arena, offsets, n); }); }
+extern "C" int am355_encode_change(am355_ctx* c, const am355_local_change* lc, const uint8_t** bytes, size_t* len, uint8_t hash[32]) { return guarded(c, [&]() { return encode_change_impl(c, lc, bytes, len, hash); }); }
+extern "C" int am355_apply_local_change(am355_ctx* c, const am355_local_change* lc, const uint8_t** change, size_t* len) { return guarded(c, [&]() { return apply_local_change_impl(c, lc, change, len); }); }
 extern "C" int am355_apply_patch_json(am355_ctx* c, const char** json, size_t* len) { return guarded(c, [&]() { return apply_patch_json_impl(c, json, len); }); }
 extern "C" int am355_get_dep_graph(am355_ctx* c, const uint32_t** dep_first, const uint32_t** dep_index, uint32_t* n) { return guarded(c, [&]() { return get_dep_graph_impl(c, dep_first, dep_index, n); }); }
 extern "C" int am355_sync_bloom_build(am355_ctx* c, const uint32_t* idx, uint32_t n, uint8_t* bits, size_t cap) {

@@ -15,6 +15,7 @@ struct ApplyPatch {
   std::vector<am355_ir_map> map;
   std::vector<am355_ir_edit> edits;  // + sentinel
   am355_patch_ir ir{};               // points into the vectors above and into the envelope / arena of the whole-document IR
+  am355_local_envelope local{};      // the patch of am355_apply_local_change: actor and seq behind diffs
 };
 
 // whole: the whole-document IR of the new state (host).  link / d_map / d_edits: the delta tables copied from the device.

@@ -196,17 +196,8 @@ static int run_delta_stage(am355_ctx* c, uint32_t T0, DeltaCounts* hc, bool chec
   return AM355_OK;
 }
 
-int apply_changes_impl(am355_ctx* c, const uint8_t* arena, const uint64_t* offsets, uint32_t n) {
-  if (!c || (!arena && n) || !offsets) return c ? fail(c, AM355_E_ARG, "null argument") : AM355_E_ARG;
-  (void)hipSetDevice(c->device);
-  c->apply_ready = false;
-  const bool trace = getenv("AM355_TRACE") != nullptr;
-  auto t_begin = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (trace) fprintf(stderr, "apply_changes: %-26s +%8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-  };
-  if (c->shard_world > 1) return fail(c, AM355_E_UNSUPPORTED, "am355_apply_changes on a sharded context");
-  if (c->staged && c->is_document) {
+// Backend.applyChanges / applyLocalChange onto a loaded document: the context's state becomes the replay of the document's rebuilt changes
+static int document_to_change_state(am355_ctx* c, const std::function<void(const char*)>& lap) {
     // Backend.applyChanges onto a loaded document. The reference rebuilds the document's changes first (computeHashGraph,
     // new.js:1887-1912, called from applyChanges :1809): the batch is scheduled against THEIR hashes. So does the engine
     // (am355_doc_changes: the device regroups rows into changes and encodes them, am355_hist.hip), then replays the rebuilt changes as
@@ -246,6 +237,23 @@ int apply_changes_impl(am355_ctx* c, const uint8_t* arena, const uint64_t* offse
     c->doc_head_index_known = head_index_known;
     lap("document history replayed");
     }
+  return AM355_OK;
+}
+
+int apply_changes_impl(am355_ctx* c, const uint8_t* arena, const uint64_t* offsets, uint32_t n) {
+  if (!c || (!arena && n) || !offsets) return c ? fail(c, AM355_E_ARG, "null argument") : AM355_E_ARG;
+  (void)hipSetDevice(c->device);
+  c->apply_ready = false;
+  c->apply.local = am355_local_envelope{};
+  const bool trace = getenv("AM355_TRACE") != nullptr;
+  auto t_begin = std::chrono::steady_clock::now();
+  auto lap = [&](const char* what) {
+    if (trace) fprintf(stderr, "apply_changes: %-26s +%8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+  };
+  if (c->shard_world > 1) return fail(c, AM355_E_UNSUPPORTED, "am355_apply_changes on a sharded context");
+  if (c->staged && c->is_document) {
+    int drc = document_to_change_state(c, lap);
+    if (drc) return drc;
   }
   const bool have_state = c->staged;
   if (have_state && !c->replayed) return fail(c, AM355_E_STATE, "the context holds no replayed state (the last replay failed?)");
@@ -416,6 +424,347 @@ int apply_changes_impl(am355_ctx* c, const uint8_t* arena, const uint64_t* offse
   return AM355_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Backend.applyLocalChange (include/am355.h am355_local_change; reference backend/backend.js:54-91, columnar.js:710-739)
+// ---------------------------------------------------------------------------------------------------------
+struct LocalPlan { uint32_t rows = 0, pred_rows = 0, val_cap = 0, key_bytes = 0; };
+
+static int actor_cmp(const am355_local_change* lc, uint32_t a, uint32_t b) {
+  const uint32_t la = lc->actor_off[a + 1] - lc->actor_off[a], lb = lc->actor_off[b + 1] - lc->actor_off[b];
+  const int r = memcmp(lc->actor_bytes + lc->actor_off[a], lc->actor_bytes + lc->actor_off[b], std::min(la, lb));
+  return r ? r : (la < lb ? -1 : la > lb ? 1 : 0);
+}
+
+// Is the request one the device stage can encode, and what does it expand to? Reads nothing of the context's state.
+// AM355_E_INVALID where the reference throws (expandMultiOps' two RangeErrors, a value it rejects), AM355_E_UNSUPPORTED for what is left to it.
+static int local_validate(am355_ctx* c, const am355_local_change* lc, LocalPlan& pl) {
+  if (!lc) return fail(c, AM355_E_ARG, "null argument");
+  if (lc->not_flat) return fail(c, AM355_E_UNSUPPORTED, "change request holds what the flat form does not express (child / link op, numeric action or datatype, extraBytes, hash): JS path");
+  if (!lc->n_actors || !lc->actor_off || !lc->actor_bytes || !lc->actor_rank || (lc->n_ops && !lc->ops) || (lc->n_values && !lc->values) || (lc->n_preds && !lc->preds) ||
+      (lc->n_deps && !lc->deps) || (lc->strings_len && !lc->strings) || (lc->message_len && !lc->message))
+    return fail(c, AM355_E_ARG, "change request: null array");
+  const uint32_t NA = lc->n_actors;
+  if (NA > (1u << 20) || lc->n_ops > (1u << 24) || lc->n_values > (1u << 24) || lc->n_preds > (1u << 24) || lc->strings_len > (1u << 30) || lc->n_deps > (1u << 20))
+    return fail(c, AM355_E_UNSUPPORTED, "change request larger than the device stage takes: JS path");
+  for (uint32_t a = 0; a < NA; a++)
+    if (lc->actor_off[a] >= lc->actor_off[a + 1]) return fail(c, AM355_E_ARG, "change request: empty actor id or descending actor offsets");
+  // author first, the others in id order (columnar.js:154-157); rank = position among all of them in id order
+  uint32_t author_rank = 0;
+  for (uint32_t a = 1; a < NA; a++) {
+    if (a > 1 && actor_cmp(lc, a - 1, a) >= 0) return fail(c, AM355_E_ARG, "change request: the other actors must ascend by id");
+    const int r = actor_cmp(lc, a, 0);
+    if (r == 0) return fail(c, AM355_E_ARG, "change request: the author appears twice in the actor table");
+    if (r < 0) author_rank++;
+  }
+  for (uint32_t a = 0; a < NA; a++)
+    if (lc->actor_rank[a] != (a == 0 ? author_rank : a - 1 < author_rank ? a - 1 : a)) return fail(c, AM355_E_ARG, "change request: actor ranks do not match the actor ids");
+  if (lc->seq < 1 || lc->seq >= (1ull << 53) || lc->start_op < 1 || lc->start_op > 0x7fffffffu) return fail(c, AM355_E_UNSUPPORTED, "change request: seq / startOp outside the engine's fields: JS path");
+  if (lc->time >= (1ll << 53) || lc->time <= -(1ll << 53)) return fail(c, AM355_E_INVALID, "change request: time is not a safe integer");
+  std::vector<uint8_t> used(NA, 0);
+  used[0] = 1;
+  uint64_t rows = 0, pred_rows = 0, val_cap = 0, key_bytes = 0;
+  auto value_ok = [&](uint32_t vi, int& rc) -> bool {
+    const am355_local_value& v = lc->values[vi];
+    switch (v.tag) {
+      case AM355_LV_NULL: case AM355_LV_FALSE: case AM355_LV_TRUE: return true;
+      case AM355_LV_UINT:
+        if (v.payload >= (1ull << 53)) { rc = fail(c, AM355_E_INVALID, "change request: uint value beyond 2^53"); return false; }
+        val_cap += 8; return true;
+      case AM355_LV_INT: case AM355_LV_COUNTER: case AM355_LV_TIMESTAMP:
+        if ((int64_t)v.payload >= (1ll << 53) || (int64_t)v.payload <= -(1ll << 53)) { rc = fail(c, AM355_E_INVALID, "change request: integer value beyond 2^53"); return false; }
+        val_cap += 8; return true;
+      case AM355_LV_FLOAT64: val_cap += 8; return true;
+      case AM355_LV_UTF8:
+        if ((uint64_t)v.off + v.len > lc->strings_len || v.len >= (1u << 28)) { rc = fail(c, AM355_E_ARG, "change request: string value outside the arena"); return false; }
+        val_cap += v.len; return true;
+      case AM355_LV_BAD: rc = fail(c, AM355_E_INVALID, "change request: a value the reference rejects (bad value / datatype pair)"); return false;
+      default: rc = fail(c, AM355_E_UNSUPPORTED, "change request: byte-array or unknown-typed value: JS path"); return false;
+    }
+  };
+  for (uint32_t i = 0; i < lc->n_ops; i++) {
+    const am355_local_op& op = lc->ops[i];
+    if (op.action > 6) return fail(c, AM355_E_UNSUPPORTED, "change request: link or unknown action: JS path");
+    if ((uint64_t)op.pred_first + op.pred_num > lc->n_preds) return fail(c, AM355_E_ARG, "change request: preds outside the pred array");
+    if (op.pred_num > 4096) return fail(c, AM355_E_UNSUPPORTED, "change request: an op of more than 4096 preds: JS path");
+    const bool ins = (op.flags & AM355_LOP_INSERT) != 0, has_values = (op.flags & AM355_LOP_VALUES) != 0;
+    const bool multi_ins = op.action == 1 && has_values && ins, multi_del = op.action == 3 && op.multi > 1;
+    if (has_values && !multi_ins) return fail(c, AM355_E_UNSUPPORTED, "change request: `values` on an op that is no inserting `set`: JS path");
+    if (multi_ins && op.pred_num != 0) return fail(c, AM355_E_INVALID, "multi-insert pred must be empty");
+    if (multi_del && op.pred_num != 1) return fail(c, AM355_E_INVALID, "multiOp deletion must have exactly one pred");
+    if (!multi_ins && !multi_del && op.multi != 1) return fail(c, AM355_E_ARG, "change request: an op without `values` / multiOp expands to one row");
+    if (op.obj_actor != NONE32) {
+      if (op.obj_actor >= NA || op.obj_ctr == 0 || op.obj_ctr > 0x7fffffffu) return fail(c, AM355_E_INVALID, "change request: unexpected objectId reference");
+      used[op.obj_actor] = 1;
+    }
+    if (op.key_kind == AM355_LK_STRING) {
+      if (op.key_len == 0) return fail(c, AM355_E_INVALID, "change request: unexpected operation key");
+      if ((uint64_t)op.key_off + op.key_len > lc->strings_len) return fail(c, AM355_E_ARG, "change request: key outside the arena");
+      if (multi_del) return fail(c, AM355_E_UNSUPPORTED, "change request: multiOp deletion without elemId: JS path");
+      key_bytes += (uint64_t)op.key_len + 8;
+    } else if (op.key_kind == AM355_LK_HEAD) {
+      if (!ins || multi_del) return fail(c, AM355_E_INVALID, "change request: unexpected operation key");
+    } else if (op.key_kind == AM355_LK_ELEM) {
+      if (op.elem_actor >= NA || op.elem_ctr == 0 || (uint64_t)op.elem_ctr + op.multi > 0x7fffffffu) return fail(c, AM355_E_INVALID, "change request: unexpected operation key");
+      used[op.elem_actor] = 1;
+    } else return fail(c, AM355_E_ARG, "change request: unknown key kind");
+    for (uint32_t k = 0; k < op.pred_num; k++) {
+      const am355_local_pred& pr = lc->preds[op.pred_first + k];
+      if (pr.actor >= NA || pr.ctr == 0 || (uint64_t)pr.ctr + op.multi > 0x7fffffffu) return fail(c, AM355_E_UNSUPPORTED, "change request: pred outside the engine's fields: JS path");
+      used[pr.actor] = 1;
+    }
+    if (op.action == 1 || op.action == 5) {
+      const uint32_t nv = multi_ins ? op.multi : 1;
+      if ((uint64_t)op.val_first + nv > lc->n_values) return fail(c, AM355_E_ARG, "change request: values outside the value array");
+      int rc = 0;
+      for (uint32_t k = 0; k < nv; k++) if (!value_ok(op.val_first + k, rc)) return rc;
+    }
+    rows += op.multi;
+    pred_rows += multi_del ? op.multi : multi_ins ? 0 : op.pred_num;
+    if (rows > (1u << 24) || pred_rows > (1u << 24) || val_cap > (1u << 30) || key_bytes > (1u << 30)) return fail(c, AM355_E_UNSUPPORTED, "change request larger than the device stage takes: JS path");
+  }
+  if (lc->start_op + rows > 0x7fffffffull) return fail(c, AM355_E_UNSUPPORTED, "change request: op counters beyond 2^31: JS path");
+  for (uint32_t a = 0; a < NA; a++)
+    if (!used[a]) return fail(c, AM355_E_ARG, "change request: the actor table lists an actor no op names");
+  pl.rows = (uint32_t)rows; pl.pred_rows = (uint32_t)pred_rows; pl.val_cap = (uint32_t)val_cap; pl.key_bytes = (uint32_t)key_bytes;
+  return AM355_OK;
+}
+
+// encodeChange of a validated request with the dependencies given (sorted by the caller): the uncompressed container into
+// c->local_plain, its hash into `hash`. Upload, expand + twelve encodes on the device, columns back, header + SHA-256 on the host.
+static int local_encode(am355_ctx* c, const am355_local_change* lc, const LocalPlan& pl, const std::vector<uint8_t>& deps, uint8_t hash[32]) {
+  (void)hipSetDevice(c->device);
+  const bool trace = getenv("AM355_TRACE") != nullptr;
+  auto t0 = std::chrono::steady_clock::now();
+  auto lap = [&](const char* what) {
+    if (!trace) return;
+    auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "local change: %-22s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t0).count());
+    t0 = now;
+  };
+  hipStream_t st = c->stream;
+  const uint32_t M = pl.rows, P = pl.pred_rows, NA = lc->n_actors;
+  const size_t lbytes = local_bytes(lc->n_ops, lc->n_values, lc->n_preds, NA, M, lc->strings_len, pl.val_cap);
+  const size_t hbytes = hist_bytes(M, P, 1, NA, 0, pl.key_bytes, pl.val_cap);
+  if (!c->d_local.ensure(lbytes) || !c->d_local_hist.ensure(hbytes)) return fail(c, AM355_E_NOMEM, "device allocation failed (local change)");
+  LocalBufs L, U;
+  local_bind(L, c->d_local.p, lc->n_ops, lc->n_values, lc->n_preds, NA, M, P, lc->strings_len, pl.val_cap, (uint32_t)lc->start_op);
+  if (!c->h_local.ensure(L.up_bytes + 256)) return fail(c, AM355_E_NOMEM, "host allocation failed (local change)");
+  local_bind(U, c->h_local.p, lc->n_ops, lc->n_values, lc->n_preds, NA, M, P, lc->strings_len, pl.val_cap, (uint32_t)lc->start_op);
+  HistBufs hb;
+  hist_bind(hb, c->d_local_hist.p, M, P, 1, NA, 0, pl.key_bytes, pl.val_cap);
+  canary_arm();
+  // the request's arrays, as they are, into the pinned block; rows / pred entries per op for the device's scans
+  if (lc->n_ops) memcpy(U.ops, lc->ops, sizeof(am355_local_op) * (size_t)lc->n_ops);
+  if (lc->n_values) memcpy(U.values, lc->values, sizeof(am355_local_value) * (size_t)lc->n_values);
+  if (lc->n_preds) memcpy(U.preds, lc->preds, sizeof(am355_local_pred) * (size_t)lc->n_preds);
+  memcpy(U.rank, lc->actor_rank, 4 * (size_t)NA);
+  for (uint32_t i = 0; i < lc->n_ops; i++) {
+    const am355_local_op& op = lc->ops[i];
+    const bool multi_ins = op.action == 1 && (op.flags & AM355_LOP_VALUES), multi_del = op.action == 3 && op.multi > 1;
+    U.multi[i] = op.multi;
+    U.pcnt[i] = multi_del ? op.multi : multi_ins ? 0 : op.pred_num;
+  }
+  U.multi[lc->n_ops] = 0; U.pcnt[lc->n_ops] = 0;
+  if (lc->strings_len) memcpy(U.arena, lc->strings, lc->strings_len);
+  int rc = queue_upload(c, c->d_local.p, c->h_local.p, L.up_bytes);
+  if (!rc) rc = flush_uploads(c);
+  if (rc) return rc;
+  lap("request staged");
+  local_expand_encode(L, hb, st);
+  size_t col_total_cap = 0;
+  for (int k = 0; k < HIST_NCOL; k++) col_total_cap += hb.col_cap[k] + 256;
+  if (!c->h_local_out.ensure(256 + col_total_cap)) return fail(c, AM355_E_NOMEM, "host allocation failed (local change)");
+  uint32_t* d_flags = c->h_local_out.as<uint32_t>();
+  uint32_t* d_col_len = d_flags + 4;
+  uint8_t* d_cols = c->h_local_out.as<uint8_t>() + 256;
+  HIPCHK(c, hipMemcpyAsync(d_flags, hb.flags, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(d_col_len, hb.col_len, 4 * HIST_NCOL, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  lap("expand + encodes (device)");
+  if (d_flags[0]) return fail(c, AM355_E_DEVICE, "internal: the request's values do not fit the arena sized for them");
+  ChangeParts parts;
+  {
+    uint8_t* q = d_cols;
+    for (int k = 0; k < HIST_NCOL; k++) {
+      if (d_col_len[k] > hb.col_cap[k]) return fail(c, AM355_E_DEVICE, "internal: encoded column larger than its bound");
+      parts.col[k] = q; parts.col_len[k] = d_col_len[k];
+      if (d_col_len[k]) HIPCHK(c, hipMemcpyAsync(q, hb.col_out[k], d_col_len[k], hipMemcpyDeviceToHost, st));
+      q += ((size_t)d_col_len[k] + 255) & ~(size_t)255;
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+  }
+  lap("columns on the host");
+  parts.author = lc->actor_bytes + lc->actor_off[0]; parts.author_len = lc->actor_off[1] - lc->actor_off[0];
+  parts.seq = lc->seq; parts.start_op = lc->start_op; parts.time = lc->time;
+  parts.message = lc->message; parts.message_len = lc->message_len;
+  parts.n_deps = (uint32_t)(deps.size() / 32);
+  for (uint32_t a = 1; a < NA; a++) parts.others.emplace_back(lc->actor_bytes + lc->actor_off[a], (size_t)(lc->actor_off[a + 1] - lc->actor_off[a]));
+  const uint64_t body = change_body_len(parts);
+  c->local_plain.assign(change_container_len(body), 0);
+  uint32_t deps_at = 0;
+  change_write(c->local_plain.data(), parts, body, &deps_at);
+  if (!deps.empty()) memcpy(c->local_plain.data() + deps_at, deps.data(), deps.size());
+  change_seal(c->local_plain.data(), c->local_plain.size(), hash);
+  lap("container + hash (host)");
+  return AM355_OK;
+}
+
+// the binary change in the form encodeChange returns it (columnar.js:738) into c->local_out
+static int local_result(am355_ctx* c, const uint8_t** bytes, size_t* len) {
+  if (c->local_plain.size() >= 256) {
+    if (!change_deflate(c->local_plain.data(), c->local_plain.size(), c->local_out)) return fail(c, AM355_E_UNSUPPORTED, "deflate failed");
+  } else c->local_out = c->local_plain;
+  if (bytes) *bytes = c->local_out.data();
+  if (len) *len = c->local_out.size();
+  return AM355_OK;
+}
+
+static void sort_hashes(std::vector<uint8_t>& deps, bool unique) {
+  const size_t n = deps.size() / 32;
+  std::vector<Hash32> v(n);
+  if (n) memcpy((void*)v.data(), deps.data(), deps.size());
+  std::sort(v.begin(), v.end(), [](const Hash32& x, const Hash32& y) { return memcmp(x.b, y.b, 32) < 0; });
+  if (unique) v.erase(std::unique(v.begin(), v.end()), v.end());
+  deps.resize(v.size() * 32);
+  if (!v.empty()) memcpy(deps.data(), (const void*)v.data(), deps.size());
+}
+
+int encode_change_impl(am355_ctx* c, const am355_local_change* lc, const uint8_t** bytes, size_t* len, uint8_t* hash) {
+  if (!c) return AM355_E_ARG;
+  LocalPlan pl;
+  int rc = local_validate(c, lc, pl);
+  if (rc) return rc;
+  std::vector<uint8_t> deps(lc->deps, lc->deps + 32 * (size_t)lc->n_deps);
+  sort_hashes(deps, false);   // (encodeChange sorts a copy, columnar.js:717)
+  uint8_t digest[32];
+  rc = local_encode(c, lc, pl, deps, digest);
+  if (rc) return rc;
+  if (hash) memcpy(hash, digest, 32);
+  return local_result(c, bytes, len);
+}
+
+// author and seq of the staged change ci, from its container header (columnar.js:744-760)
+static bool staged_author_seq(const am355_ctx* c, uint32_t ci, const uint8_t*& actor, size_t& actor_len, uint64_t& seq) {
+  const uint8_t* p = c->raw.data() + c->raw_off[ci];
+  const size_t n = (size_t)(c->raw_off[ci + 1] - c->raw_off[ci]);
+  size_t off = 9;
+  uint64_t v;
+  if (n < 10 || !read_uleb_host(p, n, off, v)) return false;     // body length
+  if (!read_uleb_host(p, n, off, v) || v > (n - off) / 32) return false;   // dependencies
+  off += 32 * (size_t)v;
+  if (!read_uleb_host(p, n, off, v) || v > n - off) return false;
+  actor = p + off; actor_len = (size_t)v;
+  off += (size_t)v;
+  return read_uleb_host(p, n, off, seq);
+}
+
+int apply_local_change_impl(am355_ctx* c, const am355_local_change* lc, const uint8_t** change, size_t* len) {
+  if (!c) return AM355_E_ARG;
+  auto refused = [&](int code) { c->n_local_refused++; return code; };
+  LocalPlan pl;
+  int rc = local_validate(c, lc, pl);
+  if (rc) return refused(rc);
+  (void)hipSetDevice(c->device);
+  if (c->shard_world > 1) return refused(fail(c, AM355_E_UNSUPPORTED, "am355_apply_local_change on a sharded context"));
+  if (c->staged && c->is_document) {
+    rc = document_to_change_state(c, [](const char*) {});
+    if (rc) return refused(rc);
+  }
+  const bool have_state = c->staged;
+  if (have_state && !c->replayed) return refused(fail(c, AM355_E_STATE, "the context holds no replayed state (the last replay failed?)"));
+  if (have_state && (!c->pending_change.empty() || c->n_pending)) return refused(fail(c, AM355_E_UNSUPPORTED, "local change onto a state with queued changes: JS path"));
+  const uint8_t* author = lc->actor_bytes + lc->actor_off[0];
+  const size_t author_len = lc->actor_off[1] - lc->actor_off[0];
+  // backend.js:56: a seq the clock already holds
+  if (have_state) {
+    const std::string id((const char*)author, author_len);
+    auto it = std::lower_bound(c->actors.begin(), c->actors.end(), id);
+    if (it != c->actors.end() && *it == id) {
+      const uint32_t rank = (uint32_t)(it - c->actors.begin());
+      for (size_t k = 0; k < c->clock_actor.size(); k++)
+        if (c->clock_actor[k] == rank && lc->seq <= c->clock_seq[k]) return refused(fail(c, AM355_E_INVALID, "Change request has already been applied"));
+    }
+  }
+  // backend.js:73-81: the author's last hash joins the deps (hashByActor: among the applied changes, the newest first)
+  std::vector<uint8_t> deps(lc->deps, lc->deps + 32 * (size_t)lc->n_deps);
+  bool graph_rebuilt = false;
+  if (lc->seq > 1) {
+    uint32_t found = NONE32;
+    if (have_state && c->h_hashes.p)
+      for (uint32_t ci = c->n_changes; ci-- > 0;) {
+        const uint8_t* a = nullptr;
+        size_t al = 0;
+        uint64_t s = 0;
+        if (!staged_author_seq(c, ci, a, al, s)) return refused(fail(c, AM355_E_DEVICE, "internal: staged change %u does not parse", ci));
+        if (s == lc->seq - 1 && al == author_len && memcmp(a, author, al) == 0) { found = ci; break; }
+      }
+    if (found == NONE32) return refused(fail(c, AM355_E_INVALID, "Unknown change: the author's change with seq %llu is not in the state", (unsigned long long)(lc->seq - 1)));
+    if (c->no_history && found < c->doc_n_changes && c->graph_mode != 0) {
+      // the hash lies inside the loaded document: the reference rebuilds the document's hash graph to find it (backend.js:38-39)
+      if (c->graph_mode == 2) return refused(fail(c, AM355_E_UNSUPPORTED, "local change onto a replayed lineage of a document: whether the reference has its hash graph is unknown: JS path"));
+      graph_rebuilt = true;
+    }
+    const uint8_t* h = c->h_hashes.as<uint8_t>() + 32 * (size_t)found;
+    deps.insert(deps.end(), h, h + 32);
+    sort_hashes(deps, true);   // (keys of an object, sorted)
+  } else sort_hashes(deps, false);
+  uint8_t digest[32];
+  rc = local_encode(c, lc, pl, deps, digest);
+  if (rc) return refused(rc);
+  if (graph_rebuilt) c->graph_mode = 0;
+  // the one-change batch through the apply path, as the uncompressed container: checksum and hash are over that form
+  const uint64_t offs[2] = {0, (uint64_t)c->local_plain.size()};
+  const std::vector<uint8_t> plain = c->local_plain;   // (the apply path may come back here through nothing, but keeps no pointer either)
+  rc = apply_changes_impl(c, plain.data(), offs, 1);
+  if (rc) return refused(rc);
+  if (!c->pending_change.empty() || c->n_pending) {
+    // a dependency the state does not hold: the reference queues the change and throws behind the apply (backend.js:88)
+    c->staged = c->replayed = c->ir_fetched = c->apply_ready = false;
+    return refused(fail(c, AM355_E_UNSUPPORTED, "local change depends on a change the state does not hold: JS path"));
+  }
+  // the envelope of a local patch: actor and seq behind diffs (new.js:1874-1877), deps without the change's own hash (backend.js:88-89)
+  am355_patch_ir& ir = c->apply.ir;
+  c->local_heads.clear();
+  for (uint32_t k = 0; k < ir.n_heads; k++)
+    if (memcmp(ir.heads + 32 * (size_t)k, digest, 32) != 0) c->local_heads.insert(c->local_heads.end(), ir.heads + 32 * (size_t)k, ir.heads + 32 * (size_t)k + 32);
+  ir.heads = c->local_heads.data();
+  ir.n_heads = (uint32_t)(c->local_heads.size() / 32);
+  am355_local_envelope& env = c->apply.local;
+  env.is_local = 1;
+  env.seq = lc->seq;
+  env.actor = NONE32;
+  {
+    const std::string id((const char*)author, author_len);
+    auto it = std::lower_bound(c->actors.begin(), c->actors.end(), id);
+    if (it != c->actors.end() && *it == id) env.actor = (uint32_t)(it - c->actors.begin());
+  }
+  if (env.actor == NONE32) {
+    env = am355_local_envelope{};
+    c->staged = c->replayed = c->ir_fetched = c->apply_ready = false;
+    return refused(fail(c, AM355_E_DEVICE, "internal: the author of the applied change is not in the actor table"));
+  }
+  c->apply_json.clear();
+  rc = local_result(c, change, len);
+  if (rc) return refused(rc);
+  c->n_local_served++;
+  return AM355_OK;
+}
+
+extern "C" int am355_apply_local_envelope(const am355_ctx* c, am355_local_envelope* out) {
+  if (!c || !out) return AM355_E_ARG;
+  if (!c->apply_ready) return AM355_E_STATE;
+  *out = c->apply.local;
+  return AM355_OK;
+}
+
+extern "C" int am355_local_change_calls(const am355_ctx* c, uint64_t out[2]) {
+  if (!c || !out) return AM355_E_ARG;
+  out[0] = c->n_local_served;
+  out[1] = c->n_local_refused;
+  return AM355_OK;
+}
+
 extern "C" int am355_reset(am355_ctx* c) {
   if (!c) return AM355_E_ARG;
   (void)hipSetDevice(c->device);
@@ -486,7 +835,7 @@ int apply_patch_json_impl(am355_ctx* c, const char** json, size_t* len) {
   if (!c->apply_ready) return fail(c, AM355_E_STATE, "am355_apply_changes must succeed first");
   if (c->apply_json.empty()) {
     std::string err;
-    if (!am355::render_patch_json(c->apply.ir, c->apply_json, err)) { c->apply_json.clear(); return fail(c, AM355_E_UNSUPPORTED, "%s", err.c_str()); }
+    if (!am355::render_patch_json(c->apply.ir, c->apply_json, err, &c->apply.local)) { c->apply_json.clear(); return fail(c, AM355_E_UNSUPPORTED, "%s", err.c_str()); }
   }
   if (json) *json = c->apply_json.c_str();
   if (len) *len = c->apply_json.size();

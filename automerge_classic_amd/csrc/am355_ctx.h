@@ -519,6 +519,12 @@ struct am355_ctx {
   // (am355_merge.hip kr_counters) instead of refusing the in-place stages
   bool resident_counters = false;
   uint64_t n_counter_calls = 0, n_counter_declined = 0;   // resident calls whose increments were written in place, no merge_run, no map half | where the stage declined
+  // am355_encode_change / am355_apply_local_change: a change request expanded and encoded on the device (am355_hist.hip kl_expand)
+  DevBuf d_local, d_local_hist;                    // LocalBufs block | the HistBufs block its encodes run in
+  HostBuf h_local, h_local_out;                    // pinned: the request's arrays on their way up | flags, column lengths and column bytes on their way down
+  std::vector<uint8_t> local_plain, local_out;     // the change as an uncompressed container | as encodeChange returns it
+  std::vector<uint8_t> local_heads;                // `deps` of the patch of a local change: the heads without the change's own hash
+  uint64_t n_local_served = 0, n_local_refused = 0;
   DevBuf d_map_alt, d_mapmerge;                    // the other map table | the stage's scratch
   am355_ir_map* map_alt_ptr = nullptr;             // whichever of the two map tables c->ir.map does NOT point to (null: not set up since the last carve)
   std::string resident_why;                        // why the last attempt fell back (diagnostics, AM355_TRACE)
@@ -625,6 +631,8 @@ int fetch_ir_impl(am355_ctx* c, am355_patch_ir* out, bool with_edits = true);
 int patch_json_impl(am355_ctx* c, const char** json, size_t* len);
 int apply_changes_impl(am355_ctx* c, const uint8_t* arena, const uint64_t* offsets, uint32_t n);
 int apply_patch_json_impl(am355_ctx* c, const char** json, size_t* len);
+int encode_change_impl(am355_ctx* c, const am355_local_change* lc, const uint8_t** bytes, size_t* len, uint8_t* hash);
+int apply_local_change_impl(am355_ctx* c, const am355_local_change* lc, const uint8_t** change, size_t* len);
 int get_dep_graph_impl(am355_ctx* c, const uint32_t** dep_first, const uint32_t** dep_index, uint32_t* n_changes);
 int sync_bloom_impl(am355_ctx* c, const uint32_t* idx, uint32_t n, uint32_t num_entries, uint32_t bits_per_entry, uint32_t num_probes, const uint8_t* bits, size_t n_bytes,
                     uint8_t* out, size_t cap, bool build);

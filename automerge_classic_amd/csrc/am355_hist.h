@@ -2,6 +2,7 @@
 #pragma once
 #include "am355_encode.h"
 #include "am355_internal.h"
+#include "../../include/am355.h"
 
 namespace am355 {
 
@@ -51,5 +52,30 @@ void hist_stage1(const OpCols& rows, HistBufs& h, hipStream_t st);
 // Stage 2: actor tables, the op columns of every change (values by slot), the twelve column encodes segmented by change.
 // n_sorted: entries of h.sorted_base / h.sorted_chg. Afterwards h.col_out / h.col_off / h.col_len / h.abits / h.flags are complete.
 void hist_stage2(const OpCols& rows, const uint8_t* arena, size_t arena_len, HistBufs& h, uint32_t n_sorted, uint32_t M, hipStream_t st);
+
+// A local change REQUEST (include/am355.h am355_local_change) turned into the value arrays the same twelve encodes read. The request's
+// arrays are uploaded as one block (`up`, the layout local_bind gives both the pinned and the device copy); HistBufs is bound with
+// N = rows, P = pred_rows, NC = 1 and its v_* / p_* / col_* members are used as by hist_stage2, with one segment.
+struct LocalBufs {
+  uint32_t n_ops, n_values, n_preds, n_actors, rows, pred_rows, str_len, val_cap, start_op;
+  // uploaded
+  am355_local_op* ops;          // [n_ops]
+  am355_local_value* values;    // [n_values]
+  am355_local_pred* preds;      // [n_preds]
+  uint32_t* rank;               // [n_actors]
+  uint32_t *multi, *pcnt;       // [n_ops + 1] rows / pred entries an op expands to (last: 0)
+  uint8_t* arena;               // [str_len] keys and UTF-8 values | [val_cap] the value bytes of the rows, written by kl_values
+  size_t up_bytes;              // the block up to and including the strings: what the host fills and uploads
+  // device only
+  uint32_t *row_base, *pred_base;   // [n_ops + 1]
+  uint32_t *vidx, *vlen, *voff;     // [rows + 1] value record of a row (NONE32: none) | its bytes | their offset behind str_len
+  void* scan_ws;
+};
+size_t local_bytes(uint32_t n_ops, uint32_t n_values, uint32_t n_preds, uint32_t n_actors, uint32_t rows, uint32_t str_len, uint32_t val_cap);
+// carves `block` (device or pinned: the same offsets); only the uploaded members are valid for a pinned block of up_bytes
+void local_bind(LocalBufs& L, void* block, uint32_t n_ops, uint32_t n_values, uint32_t n_preds, uint32_t n_actors, uint32_t rows, uint32_t pred_rows, uint32_t str_len,
+                uint32_t val_cap, uint32_t start_op);
+// scans, kl_expand, kl_values, the twelve encodes (enqueued on st). Afterwards h.flags / h.col_len / h.col_out are complete.
+void local_expand_encode(const LocalBufs& L, HistBufs& h, hipStream_t st);
 
 }  // namespace am355

@@ -388,6 +388,29 @@ __global__ __launch_bounds__(BLOCK) void kh_col_ranges(HistBufs h, int c, bool b
   else { out[2 * k] = h.enc.off_ex[h.enc.run_ex[b]]; out[2 * k + 1] = h.enc.off_ex[h.enc.run_ex[e < n_vals ? e : n_vals]]; }
 }
 
+// The twelve column encodes of change ops given as value arrays by row ([0, M): v_*, segments h.seg) and by pred entry ([0, h.P): p_*,
+// segments h.pseg) -- every change a segment. after(column, by_pred, raw, n_vals) runs behind each encode, while h.enc still describes it.
+template <class After>
+static void hist_encode_columns(const uint8_t* arena, HistBufs& h, uint32_t M, hipStream_t st, After after) {
+  enc_rle_numbers(h.v_obj_actor, nullptr, M, false, h.enc, h.col_out[0], h.col_len + 0, st, h.seg); after(0, false, false, M);
+  enc_rle_numbers(h.v_obj_ctr, nullptr, M, false, h.enc, h.col_out[1], h.col_len + 1, st, h.seg); after(1, false, false, M);
+  enc_rle_numbers(h.v_key_actor, nullptr, M, false, h.enc, h.col_out[2], h.col_len + 2, st, h.seg); after(2, false, false, M);
+  enc_delta_prepare(h.v_key_ctr, M, h.deltas, h.nullmask, h.enc, st, h.seg);
+  enc_rle_numbers(h.deltas, h.nullmask, M, true, h.enc, h.col_out[3], h.col_len + 3, st, h.seg); after(3, false, false, M);
+  enc_rle_strings(arena, h.v_key_off, h.v_key_len, M, h.enc, h.col_out[4], h.col_len + 4, st, h.seg, (uint32_t)std::min<size_t>(h.col_cap[4], 0xffffffffu)); after(4, false, false, M);
+  enc_boolean(h.v_insert, M, h.enc, h.col_out[5], h.col_len + 5, st, h.seg); after(5, false, false, M);
+  enc_rle_numbers(h.v_action, nullptr, M, false, h.enc, h.col_out[6], h.col_len + 6, st, h.seg); after(6, false, false, M);
+  enc_rle_numbers(h.v_val_tl, nullptr, M, false, h.enc, h.col_out[7], h.col_len + 7, st, h.seg); after(7, false, false, M);
+  enc_raw_values(arena, h.v_val_off, h.v_val_tl, M, h.enc, h.col_out[8], h.col_len + 8, st); after(8, false, true, M);
+  enc_rle_numbers(h.v_pred_num, nullptr, M, false, h.enc, h.col_out[9], h.col_len + 9, st, h.seg); after(9, false, false, M);
+  // (the pred columns run over the pred entries: their count sits in flags[3], the host passes it as h.P for this stage)
+  if (h.P) {
+    enc_rle_numbers(h.p_actor, nullptr, h.P, false, h.enc, h.col_out[10], h.col_len + 10, st, h.pseg); after(10, true, false, h.P);
+    enc_delta_prepare(h.p_ctr, h.P, h.deltas, h.nullmask, h.enc, st, h.pseg);
+    enc_rle_numbers(h.deltas, h.nullmask, h.P, true, h.enc, h.col_out[11], h.col_len + 11, st, h.pseg); after(11, true, false, h.P);
+  }
+}
+
 void hist_stage2(const OpCols& rows, const uint8_t* arena, size_t arena_len, HistBufs& h, uint32_t n_sorted, uint32_t M, hipStream_t st) {
   (void)hipMemsetAsync(h.abits, 0, 4 * (size_t)(h.NC + 1) * h.AW, st);
   (void)hipMemsetAsync(h.col_len, 0, 4 * HIST_NCOL, st);
@@ -399,28 +422,151 @@ void hist_stage2(const OpCols& rows, const uint8_t* arena, size_t arena_len, His
   AM355_LAUNCH_INDEPENDENT(kh_seg_bases, grid_for(h.NC + 1), dim3(BLOCK), st, h, M);
   if (!M) return;
   // the twelve columns, every one segmented by change; after each encode the byte range of every change in it
-  const uint32_t PT = h.P;   // (pred entries in use: pred_first[M]; the arrays behind them are never read: every encode covers [0, n))
-  auto ranges = [&](int c, bool by_pred, bool raw, uint32_t n_vals) {
+  hist_encode_columns(arena, h, M, st, [&](int c, bool by_pred, bool raw, uint32_t n_vals) {
     AM355_LAUNCH_INDEPENDENT(kh_col_ranges, grid_for(h.NC), dim3(BLOCK), st, h, c, by_pred, raw, n_vals);
-  };
-  (void)PT;
-  enc_rle_numbers(h.v_obj_actor, nullptr, M, false, h.enc, h.col_out[0], h.col_len + 0, st, h.seg); ranges(0, false, false, M);
-  enc_rle_numbers(h.v_obj_ctr, nullptr, M, false, h.enc, h.col_out[1], h.col_len + 1, st, h.seg); ranges(1, false, false, M);
-  enc_rle_numbers(h.v_key_actor, nullptr, M, false, h.enc, h.col_out[2], h.col_len + 2, st, h.seg); ranges(2, false, false, M);
-  enc_delta_prepare(h.v_key_ctr, M, h.deltas, h.nullmask, h.enc, st, h.seg);
-  enc_rle_numbers(h.deltas, h.nullmask, M, true, h.enc, h.col_out[3], h.col_len + 3, st, h.seg); ranges(3, false, false, M);
-  enc_rle_strings(arena, h.v_key_off, h.v_key_len, M, h.enc, h.col_out[4], h.col_len + 4, st, h.seg, (uint32_t)std::min<size_t>(h.col_cap[4], 0xffffffffu)); ranges(4, false, false, M);
-  enc_boolean(h.v_insert, M, h.enc, h.col_out[5], h.col_len + 5, st, h.seg); ranges(5, false, false, M);
-  enc_rle_numbers(h.v_action, nullptr, M, false, h.enc, h.col_out[6], h.col_len + 6, st, h.seg); ranges(6, false, false, M);
-  enc_rle_numbers(h.v_val_tl, nullptr, M, false, h.enc, h.col_out[7], h.col_len + 7, st, h.seg); ranges(7, false, false, M);
-  enc_raw_values(arena, h.v_val_off, h.v_val_tl, M, h.enc, h.col_out[8], h.col_len + 8, st); ranges(8, false, true, M);
-  enc_rle_numbers(h.v_pred_num, nullptr, M, false, h.enc, h.col_out[9], h.col_len + 9, st, h.seg); ranges(9, false, false, M);
-  // (the pred columns run over the pred entries: their count sits in flags[3], the host passes it as h.P for this stage)
-  if (h.P) {
-    enc_rle_numbers(h.p_actor, nullptr, h.P, false, h.enc, h.col_out[10], h.col_len + 10, st, h.pseg); ranges(10, true, false, h.P);
-    enc_delta_prepare(h.p_ctr, h.P, h.deltas, h.nullmask, h.enc, st, h.pseg);
-    enc_rle_numbers(h.deltas, h.nullmask, h.P, true, h.enc, h.col_out[11], h.col_len + 11, st, h.pseg); ranges(11, true, false, h.P);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// a local change request -> the same value arrays (include/am355.h am355_local_change; backend/columnar.js:446-475 expandMultiOps,
+// :122-170 parseAllOpIds, :259-292 encodeValue, :394-396 / :423 the pred order)
+// ---------------------------------------------------------------------------------------------------------
+size_t local_bytes(uint32_t n_ops, uint32_t n_values, uint32_t n_preds, uint32_t n_actors, uint32_t rows, uint32_t str_len, uint32_t val_cap) {
+  const size_t O = (size_t)n_ops + 1, R = (size_t)rows + 1;
+  return al256(sizeof(am355_local_op) * O) + al256(sizeof(am355_local_value) * ((size_t)n_values + 1)) + al256(sizeof(am355_local_pred) * ((size_t)n_preds + 1)) +
+         al256(4 * ((size_t)n_actors + 1)) + 4 * al256(4 * O) + al256((size_t)str_len + val_cap + 16) + 3 * al256(4 * R) + al256(2 * scan_workspace_bytes((uint32_t)std::max(O, R))) + 4096;
+}
+
+void local_bind(LocalBufs& L, void* block, uint32_t n_ops, uint32_t n_values, uint32_t n_preds, uint32_t n_actors, uint32_t rows, uint32_t pred_rows, uint32_t str_len,
+                uint32_t val_cap, uint32_t start_op) {
+  const size_t O = (size_t)n_ops + 1, R = (size_t)rows + 1;
+  uint8_t* p = (uint8_t*)block;
+  auto take = [&](size_t bytes) { void* r = p; p += al256(bytes); return r; };
+  L.n_ops = n_ops; L.n_values = n_values; L.n_preds = n_preds; L.n_actors = n_actors; L.rows = rows; L.pred_rows = pred_rows; L.str_len = str_len; L.val_cap = val_cap;
+  L.start_op = start_op;
+  L.ops = (am355_local_op*)take(sizeof(am355_local_op) * O);
+  L.values = (am355_local_value*)take(sizeof(am355_local_value) * ((size_t)n_values + 1));
+  L.preds = (am355_local_pred*)take(sizeof(am355_local_pred) * ((size_t)n_preds + 1));
+  L.rank = (uint32_t*)take(4 * ((size_t)n_actors + 1));
+  L.multi = (uint32_t*)take(4 * O); L.pcnt = (uint32_t*)take(4 * O);
+  L.arena = (uint8_t*)p;
+  L.up_bytes = (size_t)(p - (uint8_t*)block) + str_len;
+  (void)take((size_t)str_len + val_cap + 16);
+  L.row_base = (uint32_t*)take(4 * O); L.pred_base = (uint32_t*)take(4 * O);
+  L.vidx = (uint32_t*)take(4 * R); L.vlen = (uint32_t*)take(4 * R); L.voff = (uint32_t*)take(4 * R);
+  L.scan_ws = take(2 * scan_workspace_bytes((uint32_t)std::max(O, R)));
+}
+
+__device__ __forceinline__ uint32_t local_uleb_len(unsigned long long v) { uint32_t n = 1; while (v >= 0x80) { v >>= 7; n++; } return n; }
+__device__ __forceinline__ uint32_t local_sleb_len(long long v) {
+  for (uint32_t n = 1;; n++) {
+    const uint32_t b = (uint32_t)(v & 0x7f);
+    v >>= 7;
+    if ((v == 0 && !(b & 0x40)) || (v == -1 && (b & 0x40))) return n;
   }
+}
+// bytes a value takes in valRaw (columnar.js:259-292: Uint53 / Int53 as LEB128, a float64 as its 8 bytes, a string as its UTF-8)
+__device__ __forceinline__ uint32_t local_value_len(const am355_local_value& v) {
+  switch (v.tag) {
+    case AM355_LV_UINT: return local_uleb_len(v.payload);
+    case AM355_LV_INT: case AM355_LV_COUNTER: case AM355_LV_TIMESTAMP: return local_sleb_len((long long)v.payload);
+    case AM355_LV_FLOAT64: return 8;
+    case AM355_LV_UTF8: return v.len;
+    default: return 0;
+  }
+}
+
+// One thread per ROW of the expanded change (columnar.js:446-475): the request op that owns the row by binary search over the scan of
+// `multi`, then the row's fields as encodeOps appends them (:397-428). Row `rows` (one past the end) closes the value-length array.
+__global__ __launch_bounds__(BLOCK) void kl_expand(LocalBufs L, HistBufs h) {
+  const uint32_t row = gtid();
+  if (row > L.rows) return;
+  if (row == L.rows) { L.vlen[row] = 0; L.vidx[row] = NONE32; return; }
+  uint32_t lo = 0, hi = L.n_ops;   // the last op whose first row is <= row (ops without rows share their successor's first row)
+  while (lo + 1 < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (L.row_base[mid] <= row) lo = mid; else hi = mid;
+  }
+  const am355_local_op op = L.ops[lo];
+  const uint32_t k = row - L.row_base[lo];
+  const bool multi_ins = op.action == 1 && (op.flags & AM355_LOP_VALUES) && (op.flags & AM355_LOP_INSERT);
+  const bool multi_del = op.action == 3 && op.multi > 1;
+  uint32_t ka = NONE32, kc = NONE32, koff = 0, klen = NONE32;
+  if (op.key_kind == AM355_LK_STRING) { koff = op.key_off; klen = op.key_len; }
+  else if (op.key_kind == AM355_LK_HEAD) kc = 0;
+  else { ka = op.elem_actor; kc = op.elem_ctr; }
+  if (multi_ins && k > 0) { ka = 0; kc = L.start_op + row - 1; }   // behind the value in front of it: the id of the row before (:457)
+  if (multi_del) kc += k;                                           // (:464)
+  h.v_obj_actor[row] = op.obj_actor;
+  h.v_obj_ctr[row] = op.obj_actor == NONE32 ? NONE32 : op.obj_ctr;
+  h.v_key_actor[row] = ka; h.v_key_ctr[row] = kc; h.v_key_off[row] = koff; h.v_key_len[row] = klen;
+  h.v_insert[row] = (op.flags & AM355_LOP_INSERT) ? 1 : 0;
+  h.v_action[row] = op.action;
+  uint32_t vi = NONE32, len = 0, tl = 0;
+  if (op.action == 1 || op.action == 5) {
+    vi = op.val_first + (multi_ins ? k : 0);
+    const am355_local_value v = L.values[vi];
+    len = local_value_len(v);
+    tl = len << 4 | v.tag;
+  }
+  h.v_val_tl[row] = tl;
+  h.v_val_off[row] = 0;   // (kl_values, once the lengths are scanned)
+  L.vidx[row] = vi; L.vlen[row] = len;
+  // preds in (counter, actor id) order: compareParsedOpIds compares the id STRINGS, so by the table's ranks, not by local number
+  const uint32_t pb = L.pred_base[lo] + (multi_del ? k : 0), pn = multi_ins ? 0u : multi_del ? 1u : op.pred_num;
+  h.v_pred_num[row] = pn;
+  if (multi_del) { h.p_actor[pb] = L.preds[op.pred_first].actor; h.p_ctr[pb] = L.preds[op.pred_first].ctr + k; return; }   // (:465)
+  for (uint32_t i = 0; i < pn; i++) {
+    const am355_local_pred pr = L.preds[op.pred_first + i];
+    const unsigned long long key = (unsigned long long)pr.ctr << 32 | L.rank[pr.actor];
+    uint32_t j = i;
+    for (; j > 0; j--) {
+      const uint32_t qa = h.p_actor[pb + j - 1], qc = h.p_ctr[pb + j - 1];
+      if (((unsigned long long)qc << 32 | L.rank[qa]) <= key) break;
+      h.p_actor[pb + j] = qa; h.p_ctr[pb + j] = qc;
+    }
+    h.p_actor[pb + j] = pr.actor; h.p_ctr[pb + j] = pr.ctr;
+  }
+}
+
+// One thread per row: the value's bytes into the value arena at the scanned offset
+__global__ __launch_bounds__(BLOCK) void kl_values(LocalBufs L, HistBufs h) {
+  const uint32_t row = gtid();
+  if (row >= L.rows) return;
+  const uint32_t len = L.vlen[row], vi = L.vidx[row];
+  if (!len || vi == NONE32) return;
+  const uint32_t at = L.voff[row];
+  if ((unsigned long long)at + len > L.val_cap) { atomicOr(&h.flags[0], (uint32_t)HF_INVALID); return; }   // (the host sized the arena from the same values)
+  const am355_local_value v = L.values[vi];
+  uint8_t* out = L.arena + L.str_len + at;
+  h.v_val_off[row] = L.str_len + at;
+  if (v.tag == AM355_LV_UTF8) {
+    const uint8_t* src = L.arena + v.off;
+    for (uint32_t i = 0; i < len; i++) out[i] = src[i];
+  } else if (v.tag == AM355_LV_FLOAT64) {
+    for (uint32_t i = 0; i < 8; i++) out[i] = (uint8_t)(v.payload >> (8 * i));
+  } else if (v.tag == AM355_LV_UINT) {
+    unsigned long long x = v.payload;
+    for (uint32_t i = 0; i < len; i++) { out[i] = (uint8_t)((x & 0x7f) | (i + 1 < len ? 0x80 : 0)); x >>= 7; }
+  } else {
+    long long x = (long long)v.payload;
+    for (uint32_t i = 0; i < len; i++) { out[i] = (uint8_t)((x & 0x7f) | (i + 1 < len ? 0x80 : 0)); x >>= 7; }
+  }
+}
+
+void local_expand_encode(const LocalBufs& L, HistBufs& h, hipStream_t st) {
+  const uint32_t M = L.rows;
+  (void)hipMemsetAsync(h.flags, 0, 16, st);
+  (void)hipMemsetAsync(h.col_len, 0, 4 * HIST_NCOL, st);
+  if (!M) return;
+  (void)hipMemsetAsync(h.seg, 0, 4 * (size_t)M, st);   // one change: every row and every pred entry in segment 0
+  if (L.pred_rows) (void)hipMemsetAsync(h.pseg, 0, 4 * (size_t)L.pred_rows, st);
+  exclusive_scan2_u32(L.multi, L.row_base, nullptr, L.pcnt, L.pred_base, nullptr, L.n_ops + 1, L.scan_ws, st);
+  AM355_LAUNCH_INDEPENDENT(kl_expand, grid_for(M + 1), dim3(BLOCK), st, L, h);
+  exclusive_scan_u32(L.vlen, L.voff, M + 1, nullptr, L.scan_ws, st);
+  AM355_LAUNCH_INDEPENDENT(kl_values, grid_for(M), dim3(BLOCK), st, L, h);
+  h.P = L.pred_rows;
+  hist_encode_columns(L.arena, h, M, st, [](int, bool, bool, uint32_t) {});
 }
 
 }  // namespace am355

@@ -348,6 +348,79 @@ inline uint8_t* w_sleb(uint8_t* p, int64_t v) {
 inline uint8_t* w_bytes(uint8_t* p, const void* src, size_t n) { if (n) memcpy(p, src, n); return p + n; }
 }  // namespace
 
+// ---- one change's container (encodeChange, columnar.js:710-739; encodeContainer :664-686): shared by the history of a loaded document
+// (every change of it, below) and by a local change request encoded on the device (am355_calls.hip) ----
+static const uint32_t CHANGE_COL_ID[HISTORY_NCOL] = {0x01, 0x02, 0x11, 0x13, 0x15, 0x34, 0x42, 0x56, 0x57, 0x70, 0x71, 0x73};  // (chldActor 0x61 / chldCtr 0x63: all null = empty = omitted)
+
+uint64_t change_body_len(const ChangeParts& c) {
+  uint64_t n = uleb_len(c.n_deps) + 32ull * c.n_deps;
+  n += uleb_len(c.author_len) + c.author_len + uleb_len(c.seq) + uleb_len(c.start_op) + sleb_len(c.time) + uleb_len(c.message_len) + c.message_len;
+  n += uleb_len(c.others.size());
+  for (auto& a : c.others) n += uleb_len(a.second) + a.second;
+  size_t ncols = 0;
+  for (int q = 0; q < HISTORY_NCOL; q++)
+    if (c.col_len[q]) { ncols++; n += uleb_len(CHANGE_COL_ID[q]) + uleb_len(c.col_len[q]) + c.col_len[q]; }
+  n += uleb_len(ncols) + c.extra_len;
+  return n;
+}
+
+uint8_t* change_write(uint8_t* base, const ChangeParts& c, uint64_t body_len, uint32_t* deps_at) {
+  static const uint8_t MAGIC[4] = {0x85, 0x6f, 0x4a, 0x83};
+  uint8_t* p = w_bytes(base, MAGIC, 4);
+  p += 4;   // checksum: the first four bytes of the hash (change_seal)
+  *p++ = 1;
+  p = w_uleb(p, body_len);
+  p = w_uleb(p, c.n_deps);
+  *deps_at = (uint32_t)(p - base);
+  p += 32ull * c.n_deps;
+  p = w_uleb(p, c.author_len); p = w_bytes(p, c.author, c.author_len);
+  p = w_uleb(p, c.seq);
+  p = w_uleb(p, c.start_op);
+  p = w_sleb(p, c.time);
+  p = w_uleb(p, c.message_len); p = w_bytes(p, c.message, c.message_len);
+  p = w_uleb(p, c.others.size());
+  for (auto& a : c.others) { p = w_uleb(p, a.second); p = w_bytes(p, a.first, a.second); }
+  size_t ncols = 0;
+  for (int q = 0; q < HISTORY_NCOL; q++) ncols += c.col_len[q] ? 1 : 0;
+  p = w_uleb(p, ncols);
+  for (int q = 0; q < HISTORY_NCOL; q++) if (c.col_len[q]) { p = w_uleb(p, CHANGE_COL_ID[q]); p = w_uleb(p, c.col_len[q]); }
+  for (int q = 0; q < HISTORY_NCOL; q++) p = w_bytes(p, c.col[q], c.col_len[q]);
+  p = w_bytes(p, c.extra, c.extra_len);
+  return p;
+}
+
+size_t change_container_len(uint64_t body_len) { return 9 + uleb_len(body_len) + (size_t)body_len; }
+
+void change_seal(uint8_t* base, size_t len, uint8_t digest[32]) {
+  sha256_digest(base + 8, len - 8, digest);   // over [chunk type][LEB length][body]
+  memcpy(base + 4, digest, 4);
+}
+
+bool change_deflate(const uint8_t* plain, size_t len, std::vector<uint8_t>& o) {
+  const uint8_t* full = plain + 8;   // [type][length][body]
+  const size_t full_len = len - 8;
+  size_t hdr = 1;  // chunk data = everything after [type][length]
+  while (full[hdr] & 0x80) hdr++;
+  hdr++;
+  z_stream zs;
+  memset(&zs, 0, sizeof zs);
+  if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+  Bytes z(deflateBound(&zs, (uLong)(full_len - hdr)) + 64);
+  zs.next_in = const_cast<uint8_t*>(full + hdr); zs.avail_in = (uInt)(full_len - hdr);
+  zs.next_out = z.data(); zs.avail_out = (uInt)z.size();
+  int zr = ::deflate(&zs, Z_FINISH);
+  size_t zn = zs.total_out;
+  deflateEnd(&zs);
+  if (zr != Z_STREAM_END) return false;
+  o.clear();
+  o.reserve(16 + zn);
+  o.insert(o.end(), plain, plain + 8);
+  o.push_back(2);
+  put_uleb(o, zn);
+  o.insert(o.end(), z.begin(), z.begin() + zn);
+  return true;
+}
+
 // The dependency index column (depsIndex, delta-coded: columnar.js:945-981 reads it change by change): meta.dep_index[c.dep_first ..
 // + c.dep_num) of every change. One sequential decode of one value per dependency edge -- independent of everything the device stages
 // need, so doc_changes_impl runs it on a thread of its own beside them.
@@ -391,7 +464,6 @@ int history_finish(const HistoryInput& in, HistoryMeta& meta, const HistoryPiece
   const uint32_t NC = (uint32_t)chg.size();
   const unsigned T = 256;
   const unsigned TE = NC < T ? std::max(NC, 1u) : T;
-  static const uint32_t col_id[HISTORY_NCOL] = {0x01, 0x02, 0x11, 0x13, 0x15, 0x34, 0x42, 0x56, 0x57, 0x70, 0x71, 0x73};  // (chldActor 0x61 / chldCtr 0x63: all null = empty = omitted)
   auto col_range = [&](uint32_t k, int q, uint32_t& off, uint32_t& len) {
     const uint32_t* o = pc.col_off + (size_t)q * 2 * (NC + 1);
     off = o[2 * k];
@@ -407,63 +479,45 @@ int history_finish(const HistoryInput& in, HistoryMeta& meta, const HistoryPiece
         if (a != chg[k].actor && a < NA) others.push_back(a);
       }
   };
+  auto parts_of = [&](uint32_t k, const std::vector<uint32_t>& others, ChangeParts& p) {
+    const ChangeRec& c = chg[k];
+    const std::string& author = actors[c.actor];
+    p.author = (const uint8_t*)author.data(); p.author_len = author.size();
+    p.seq = c.seq; p.start_op = c.start_op; p.time = c.time;
+    p.message = (const uint8_t*)c.message.data(); p.message_len = c.message.size();
+    p.n_deps = c.dep_num;
+    p.others.clear();
+    for (uint32_t a : others) p.others.emplace_back((const uint8_t*)actors[a].data(), actors[a].size());
+    for (int q = 0; q < HISTORY_NCOL; q++) { uint32_t off, len; col_range(k, q, off, len); p.col[q] = pc.col_bytes[q] + off; p.col_len[q] = len; }
+    p.extra = (const uint8_t*)c.extra.data(); p.extra_len = c.extra.size();
+  };
   // ---- sizes: container = magic 4 | checksum 4 | type 1 | LEB(body) | body; body = deps (count, hashes) | rest (header, columns, extra) ----
   std::vector<uint64_t> body_len(NC), plain_off((size_t)NC + 1, 0);
   par(TE, [&](unsigned t) {
     std::vector<uint32_t> others;
+    ChangeParts parts;
     for (uint32_t k = t; k < NC; k += TE) {
       ChangeRec& c = chg[k];
       c.n_ops = pc.chg_nops[k];
       c.start_op = c.max_op - c.n_ops + 1;
       others_of(k, others);
-      const std::string& author = actors[c.actor];
-      uint64_t n = uleb_len(c.dep_num) + 32ull * c.dep_num;
-      n += uleb_len(author.size()) + author.size() + uleb_len(c.seq) + uleb_len(c.start_op) + sleb_len(c.time) + uleb_len(c.message.size()) + c.message.size();
-      n += uleb_len(others.size());
-      for (uint32_t a : others) n += uleb_len(actors[a].size()) + actors[a].size();
-      size_t ncols = 0;
-      for (int q = 0; q < HISTORY_NCOL; q++) {
-        uint32_t off, len;
-        col_range(k, q, off, len);
-        if (len) { ncols++; n += uleb_len(col_id[q]) + uleb_len(len) + len; }
-      }
-      n += uleb_len(ncols) + c.extra.size();
+      parts_of(k, others, parts);
+      const uint64_t n = change_body_len(parts);
       body_len[k] = n;
     }
   });
-  for (uint32_t k = 0; k < NC; k++) plain_off[k + 1] = plain_off[k] + 9 + uleb_len(body_len[k]) + body_len[k];
+  for (uint32_t k = 0; k < NC; k++) plain_off[k + 1] = plain_off[k] + change_container_len(body_len[k]);
   std::vector<uint8_t>& plain = out.arena;   // (the result itself unless the changes are to be compressed)
   plain.resize(plain_off[NC]);
   // ---- 5b. every change: header (the dependency hashes are filled in by the chain below) + its stretch of each encoded column ----
   std::vector<uint32_t> deps_at(NC);   // offset of the dependency hashes inside the arena
   par(TE, [&](unsigned t) {
-    static const uint8_t MAGIC[4] = {0x85, 0x6f, 0x4a, 0x83};
     std::vector<uint32_t> others;
+    ChangeParts parts;
     for (uint32_t k = t; k < NC; k += TE) {
-      const ChangeRec& c = chg[k];
       others_of(k, others);
-      uint8_t* p = plain.data() + plain_off[k];
-      p = w_bytes(p, MAGIC, 4);
-      p += 4;   // checksum: the first four bytes of the hash
-      *p++ = 1;
-      p = w_uleb(p, body_len[k]);
-      p = w_uleb(p, c.dep_num);
-      deps_at[k] = (uint32_t)(p - (plain.data() + plain_off[k]));
-      p += 32ull * c.dep_num;
-      const std::string& author = actors[c.actor];
-      p = w_uleb(p, author.size()); p = w_bytes(p, author.data(), author.size());
-      p = w_uleb(p, c.seq);
-      p = w_uleb(p, c.start_op);
-      p = w_sleb(p, c.time);
-      p = w_uleb(p, c.message.size()); p = w_bytes(p, c.message.data(), c.message.size());
-      p = w_uleb(p, others.size());
-      for (uint32_t a : others) { p = w_uleb(p, actors[a].size()); p = w_bytes(p, actors[a].data(), actors[a].size()); }
-      size_t ncols = 0;
-      for (int q = 0; q < HISTORY_NCOL; q++) { uint32_t off, len; col_range(k, q, off, len); ncols += len ? 1 : 0; }
-      p = w_uleb(p, ncols);
-      for (int q = 0; q < HISTORY_NCOL; q++) { uint32_t off, len; col_range(k, q, off, len); if (len) { p = w_uleb(p, col_id[q]); p = w_uleb(p, len); } }
-      for (int q = 0; q < HISTORY_NCOL; q++) { uint32_t off, len; col_range(k, q, off, len); p = w_bytes(p, pc.col_bytes[q] + off, len); }
-      p = w_bytes(p, c.extra.data(), c.extra.size());
+      parts_of(k, others, parts);
+      change_write(plain.data() + plain_off[k], parts, body_len[k], &deps_at[k]);
     }
   });
   lap("headers + column pieces");
@@ -502,9 +556,7 @@ int history_finish(const HistoryInput& in, HistoryMeta& meta, const HistoryPiece
       uint8_t* base = plain.data() + plain_off[k];
       uint8_t* p = base + deps_at[k];
       for (const uint8_t* h : deps) { memcpy(p, h, 32); p += 32; }
-      uint8_t* digest = &out.hashes[(size_t)k * 32];
-      sha256_digest(base + 8, (size_t)(plain_off[k + 1] - plain_off[k] - 8), digest);   // over [chunk type][LEB length][body]
-      memcpy(base + 4, digest, 4);
+      change_seal(base, (size_t)(plain_off[k + 1] - plain_off[k]), &out.hashes[(size_t)k * 32]);
     };
     // ONE run of the pool for all levels: a task takes changes of the current level until none is left, waits for the ones others
     // took, and goes on to the next level. (A task only ever waits for changes some RUNNING task holds, so the pool may execute the
@@ -549,28 +601,9 @@ int history_finish(const HistoryInput& in, HistoryMeta& meta, const HistoryPiece
   std::vector<int> pack_rc(NC, 0);
   par(TE, [&](unsigned t) {
     for (uint32_t k = t; k < NC; k += TE) {
-      const uint8_t* full = plain.data() + plain_off[k] + 8;   // [type][length][body]
-      const size_t full_len = (size_t)(plain_off[k + 1] - plain_off[k] - 8);
-      if (8 + full_len < 256) continue;   // stays as it is
-      size_t hdr = 1;  // chunk data = everything after [type][length]
-      while (full[hdr] & 0x80) hdr++;
-      hdr++;
-      z_stream zs;
-      memset(&zs, 0, sizeof zs);
-      if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) { pack_rc[k] = 1; continue; }
-      Bytes z(deflateBound(&zs, (uLong)(full_len - hdr)) + 64);
-      zs.next_in = const_cast<uint8_t*>(full + hdr); zs.avail_in = (uInt)(full_len - hdr);
-      zs.next_out = z.data(); zs.avail_out = (uInt)z.size();
-      int zr = ::deflate(&zs, Z_FINISH);
-      size_t zn = zs.total_out;
-      deflateEnd(&zs);
-      if (zr != Z_STREAM_END) { pack_rc[k] = 1; continue; }
-      Bytes& o = packed[k];
-      o.reserve(16 + zn);
-      o.insert(o.end(), plain.data() + plain_off[k], plain.data() + plain_off[k] + 8);
-      o.push_back(2);
-      put_uleb(o, zn);
-      o.insert(o.end(), z.begin(), z.begin() + zn);
+      const size_t plain_len = (size_t)(plain_off[k + 1] - plain_off[k]);
+      if (plain_len < 256) continue;   // stays as it is
+      if (!change_deflate(plain.data() + plain_off[k], plain_len, packed[k])) pack_rc[k] = 1;
     }
   });
   lap("containers");

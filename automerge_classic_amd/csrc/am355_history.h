@@ -69,6 +69,27 @@ struct HistoryOutput {
 
 enum { HISTORY_OK = 0, HISTORY_INVALID = 1, HISTORY_UNSUPPORTED = 2 };
 
+// One change's container around its encoded op columns (encodeChange, columnar.js:710-739): what history_finish writes for every change
+// of a document and am355_encode_change / am355_apply_local_change for a change request. Pointers are borrowed.
+struct ChangeParts {
+  const uint8_t* author = nullptr; size_t author_len = 0;
+  uint64_t seq = 0, start_op = 0;
+  int64_t time = 0;
+  const uint8_t* message = nullptr; size_t message_len = 0;
+  uint32_t n_deps = 0;                                       // (their hashes: written by the caller at *deps_at, sorted)
+  std::vector<std::pair<const uint8_t*, size_t>> others;     // the actors the ops mention besides the author, in id order
+  const uint8_t* col[HISTORY_NCOL] = {}; uint32_t col_len[HISTORY_NCOL] = {};   // the encoded columns (an empty one is left out)
+  const uint8_t* extra = nullptr; size_t extra_len = 0;
+};
+uint64_t change_body_len(const ChangeParts& c);
+size_t change_container_len(uint64_t body_len);   // magic 4 | checksum 4 | type 1 | LEB(body) | body
+// writes the container without dependency hashes and checksum at base; *deps_at: where the 32 * n_deps bytes of hashes go. Returns the end.
+uint8_t* change_write(uint8_t* base, const ChangeParts& c, uint64_t body_len, uint32_t* deps_at);
+// SHA-256 over [chunk type][LEB length][body] into digest; its first four bytes into the checksum field
+void change_seal(uint8_t* base, size_t len, uint8_t digest[32]);
+// the DEFLATEd form (chunk type 2, columnar.js:798-811; zlib level 6 raw = pako's defaults) of a plain container; false: zlib failed
+bool change_deflate(const uint8_t* plain, size_t len, std::vector<uint8_t>& out);
+
 // par(k, fn): runs fn(0..k-1) on the caller's host threads and returns when all are done.
 using ParallelFor = std::function<void(unsigned, const std::function<void(unsigned)>&)>;
 

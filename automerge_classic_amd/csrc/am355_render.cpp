@@ -25,6 +25,7 @@ struct R {
   std::string& out;
   std::string err;
   int depth = 0;
+  const am355_local_envelope* local = nullptr;   // the patch of applyLocalChange: actor and seq behind diffs
   explicit R(const am355_patch_ir& i, std::string& o) : ir(i), out(o) {}
 
   bool fail(const char* m) { if (err.empty()) err = m; return false; }
@@ -462,6 +463,12 @@ struct R {
     snprintf(t, sizeof t, "],\"pendingChanges\":%u,\"diffs\":", ir.pending);
     out += t;
     if (!object(0)) return false;
+    if (local && local->is_local) {   // the patch of applyLocalChange: actor and seq behind diffs (new.js:1874-1877)
+      out += ",\"actor\":\"";
+      hex(ir.actor_bytes + ir.actor_off[local->actor], ir.actor_off[local->actor + 1] - ir.actor_off[local->actor]);
+      snprintf(t, sizeof t, "\",\"seq\":%llu", (unsigned long long)local->seq);
+      out += t;
+    }
     out.push_back('}');
     return true;
   }
@@ -469,8 +476,9 @@ struct R {
 
 }  // namespace
 
-bool render_patch_json(const am355_patch_ir& ir, std::string& out, std::string& err) {
+bool render_patch_json(const am355_patch_ir& ir, std::string& out, std::string& err, const am355_local_envelope* local) {
   R r(ir, out);
+  r.local = local;
   bool ok = r.run();
   if (!ok) err = r.err;
   return ok;

@@ -4,5 +4,6 @@
 #include <string>
 
 namespace am355 {
-bool render_patch_json(const am355_patch_ir& ir, std::string& out, std::string& err);
+// local: the envelope of a patch of am355_apply_local_change (actor and seq behind diffs), or null
+bool render_patch_json(const am355_patch_ir& ir, std::string& out, std::string& err, const am355_local_envelope* local = nullptr);
 }

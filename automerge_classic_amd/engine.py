@@ -55,6 +55,211 @@ class UnsupportedChanges(EngineError):
     """Legal input outside the GPU-served subset (documented in DESIGN.md); the JS host uses the JS path."""
 
 
+class LocalChange(ctypes.Structure):
+    """am355_local_change (include/am355.h): a change request as plain arrays."""
+    _fields_ = [
+        ("seq", ctypes.c_uint64), ("start_op", ctypes.c_uint64), ("time", ctypes.c_int64),
+        ("message", ctypes.c_void_p), ("message_len", ctypes.c_uint32),
+        ("deps", ctypes.c_void_p), ("n_deps", ctypes.c_uint32),
+        ("n_actors", ctypes.c_uint32), ("actor_off", ctypes.c_void_p), ("actor_bytes", ctypes.c_void_p), ("actor_rank", ctypes.c_void_p),
+        ("strings", ctypes.c_void_p), ("strings_len", ctypes.c_uint32),
+        ("ops", ctypes.c_void_p), ("n_ops", ctypes.c_uint32),
+        ("values", ctypes.c_void_p), ("n_values", ctypes.c_uint32),
+        ("preds", ctypes.c_void_p), ("n_preds", ctypes.c_uint32),
+        ("not_flat", ctypes.c_uint32),
+    ]
+
+
+_ACTIONS = ("makeMap", "set", "makeList", "del", "makeText", "inc", "makeTable")   # (`link`, numeric actions: not in the flat form)
+LK_STRING, LK_HEAD, LK_ELEM = 0, 1, 2
+LOP_INSERT, LOP_VALUES = 1, 2
+LV_NULL, LV_FALSE, LV_TRUE, LV_UINT, LV_INT, LV_FLOAT64, LV_UTF8, LV_BYTES, LV_COUNTER, LV_TIMESTAMP, LV_BAD = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 15
+_VALUE_DTYPE = np.dtype([("tag", "<u4"), ("off", "<u4"), ("len", "<u4"), ("pad", "<u4"), ("payload", "<u8")])
+_MAX_SAFE = 2 ** 53 - 1
+
+
+class _NotFlat(Exception):
+    pass
+
+
+def _hex_id(s):
+    if not isinstance(s, str) or not s or len(s) % 2 or s != s.lower():
+        raise _NotFlat(f"actor id {s!r}")
+    try:
+        return bytes.fromhex(s)
+    except ValueError:
+        raise _NotFlat(f"actor id {s!r}")
+
+
+def _op_id(s):
+    if not isinstance(s, str) or "@" not in s:
+        raise _NotFlat(f"op id {s!r}")
+    ctr, actor = s.split("@", 1)
+    if not ctr.isdigit() or int(ctr) >= 2 ** 32:
+        raise _NotFlat(f"op id {s!r}")
+    return int(ctr), _hex_id(actor)
+
+
+def flatten_change_request(request):
+    """The reference's change request ({actor, seq, startOp, time, message, deps, ops: [...]}, backend.js:54) as the arrays of
+    am355_local_change. Returns (LocalChange, keep-alive list). What the flat form cannot express sets not_flat (the engine answers
+    AM355_E_UNSUPPORTED); what the reference throws on travels as it is and is refused there (AM355_E_INVALID).
+    A number without datatype is an int when it is a safe integer, else a float64 (getNumberTypeAndValue, columnar.js:245)."""
+    lc = LocalChange()
+    keep = []
+
+    def arr(a):
+        keep.append(a)
+        return a.ctypes.data if a.size else None
+
+    try:
+        if "hash" in request or request.get("extraBytes") is not None:
+            raise _NotFlat("hash / extraBytes")
+        author = _hex_id(request["actor"])
+        actors = {author}
+        ops_in = request["ops"]
+        strings = bytearray()
+        ops = np.zeros((len(ops_in), 13), dtype=np.uint32)
+        values, preds, parsed = [], [], []
+
+        def put_string(s):
+            try:
+                b = s.encode("utf-8")
+            except UnicodeEncodeError:
+                raise _NotFlat("lone surrogate")
+            off = len(strings)
+            strings.extend(b)
+            return off, len(b)
+
+        def put_value(v, datatype, multi):
+            tag, off, ln, payload = LV_BAD, 0, 0, 0
+            is_num = isinstance(v, (int, float)) and not isinstance(v, bool)
+            if isinstance(datatype, (int, float)) and not isinstance(datatype, bool):
+                raise _NotFlat("numeric datatype")
+            if multi and ((datatype is None) == is_num or (datatype is not None and not is_num)):
+                pass   # (validDatatype, columnar.js:438-444: the reference throws)
+            elif v is None:
+                tag = LV_NULL
+            elif v is False or v is True:
+                tag = LV_TRUE if v else LV_FALSE
+            elif isinstance(v, str):
+                tag = LV_UTF8
+                off, ln = put_string(v)
+            elif isinstance(v, (bytes, bytearray, memoryview)):
+                tag = LV_BYTES
+            elif is_num:
+                whole = isinstance(v, int) or (v == v and abs(v) != float("inf") and float(v).is_integer())
+                if datatype in ("counter", "timestamp", "int", "uint"):
+                    if whole and abs(int(v)) <= _MAX_SAFE and (datatype != "uint" or int(v) >= 0):
+                        tag = {"counter": LV_COUNTER, "timestamp": LV_TIMESTAMP, "int": LV_INT, "uint": LV_UINT}[datatype]
+                        payload = int(v) & 0xFFFFFFFFFFFFFFFF
+                elif datatype != "float64" and whole and abs(int(v)) <= _MAX_SAFE:
+                    tag, payload = LV_INT, int(v) & 0xFFFFFFFFFFFFFFFF
+                else:
+                    tag, payload = LV_FLOAT64, int(np.array([float(v)], dtype="<f8").view("<u8")[0])
+            else:
+                raise _NotFlat("value that is no primitive")
+            values.append((tag, off, ln, 0, payload))
+
+        for i, op in enumerate(ops_in):
+            action = op.get("action")
+            if action not in _ACTIONS or "child" in op:
+                raise _NotFlat(f"action {action!r} / child")
+            r = ops[i]
+            r[0] = _ACTIONS.index(action)
+            if op["obj"] == "_root":
+                obj = None
+                r[1] = 0xFFFFFFFF
+            else:
+                obj = _op_id(op["obj"])
+                actors.add(obj[1])
+                r[2] = obj[0]
+            insert = bool(op.get("insert"))
+            elem = None
+            if op.get("key"):
+                if not isinstance(op["key"], str):
+                    raise _NotFlat("key")
+                r[3] = LK_STRING
+                r[4], r[5] = put_string(op["key"])
+            elif op.get("elemId") == "_head":
+                r[3] = LK_HEAD
+            elif op.get("elemId"):
+                r[3] = LK_ELEM
+                elem = _op_id(op["elemId"])
+                actors.add(elem[1])
+                r[7] = elem[0]
+            else:
+                r[3], r[5] = LK_STRING, 0   # (no key at all: the reference throws)
+            if not isinstance(op.get("pred"), list):
+                raise _NotFlat("pred")
+            op_preds = [_op_id(p) for p in op["pred"]]
+            for _, a in op_preds:
+                actors.add(a)
+            multi_ins = action == "set" and insert and op.get("values") is not None
+            r[8] = (LOP_INSERT if insert else 0) | (LOP_VALUES if multi_ins else 0)
+            r[9] = 1
+            r[10] = len(values)
+            if multi_ins:
+                if not isinstance(op["values"], list):
+                    raise _NotFlat("values")
+                r[9] = len(op["values"])
+                for v in op["values"]:
+                    put_value(v, op.get("datatype"), True)
+            elif action in ("set", "inc"):
+                if "value" not in op:
+                    values.append((LV_BAD, 0, 0, 0, 0))
+                else:
+                    put_value(op["value"], op.get("datatype"), False)
+            if action == "del" and isinstance(op.get("multiOp"), (int, float)) and op["multiOp"] > 1:
+                if int(op["multiOp"]) != op["multiOp"] or op["multiOp"] >= 2 ** 31 or elem is None:
+                    raise _NotFlat("multiOp")
+                r[9] = int(op["multiOp"])
+            r[11], r[12] = len(preds), len(op_preds)
+            preds.extend(op_preds)
+            parsed.append((obj, elem))
+        others = sorted(actors - {author})
+        table = [author] + others
+        local = {a: k for k, a in enumerate(table)}
+        order = sorted(table)
+        rank = np.array([order.index(a) for a in table], dtype=np.uint32)
+        for r, (obj, elem) in zip(ops, parsed):
+            if obj is not None:
+                r[1] = local[obj[1]]
+            if elem is not None:
+                r[6] = local[elem[1]]
+        pred_arr = np.array([(local[a], ctr) for ctr, a in preds], dtype=np.uint32).reshape(-1, 2)
+        val_arr = np.array(values, dtype=_VALUE_DTYPE) if values else np.zeros(0, dtype=_VALUE_DTYPE)
+        message = (request.get("message") or "").encode("utf-8")
+        deps = np.frombuffer(b"".join(bytes.fromhex(h) for h in request["deps"]), dtype=np.uint8).copy()
+        if deps.size != 32 * len(request["deps"]):
+            raise _NotFlat("deps")
+        for f in ("seq", "startOp", "time"):
+            if not isinstance(request[f], int) or isinstance(request[f], bool) or abs(request[f]) >= 2 ** 63:
+                raise _NotFlat(f)
+        if request["seq"] < 0 or request["startOp"] < 0:
+            raise _NotFlat("seq / startOp")
+    except (_NotFlat, KeyError, TypeError, ValueError, AttributeError, UnicodeEncodeError):
+        lc.not_flat = 1
+        return lc, keep
+    lc.seq, lc.start_op, lc.time = request["seq"], request["startOp"], request["time"]
+    msg = np.frombuffer(message, dtype=np.uint8).copy()
+    lc.message, lc.message_len = arr(msg), msg.size
+    lc.deps, lc.n_deps = arr(deps), deps.size // 32
+    offs = np.zeros(len(table) + 1, dtype=np.uint32)
+    np.cumsum([len(a) for a in table], out=offs[1:])
+    lc.n_actors = len(table)
+    lc.actor_off = arr(offs)
+    lc.actor_bytes = arr(np.frombuffer(b"".join(table), dtype=np.uint8).copy())
+    lc.actor_rank = arr(rank)
+    st = np.frombuffer(bytes(strings), dtype=np.uint8).copy()
+    lc.strings, lc.strings_len = arr(st), st.size
+    ops = np.ascontiguousarray(ops)
+    lc.ops, lc.n_ops = arr(ops), ops.shape[0]
+    lc.values, lc.n_values = arr(val_arr), val_arr.size
+    lc.preds, lc.n_preds = arr(pred_arr), pred_arr.shape[0]
+    return lc, keep
+
+
 def _bind(path):
     if not os.path.exists(path):
         raise RuntimeError(f"HIP engine library not found: {path}. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -131,6 +336,12 @@ def _bind(path):
         L.am355_set_resident_map_merge.restype = ctypes.c_int
         L.am355_resident_map_merge_calls.argtypes = [vp, vp]
         L.am355_resident_map_merge_calls.restype = ctypes.c_int
+    if hasattr(L, "am355_apply_local_change"):   # (libraries of earlier commits, loaded for an A/B run, end before these)
+        L.am355_encode_change.argtypes = [vp, ctypes.POINTER(LocalChange), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), vp]
+        L.am355_apply_local_change.argtypes = [vp, ctypes.POINTER(LocalChange), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+        L.am355_local_change_calls.argtypes = [vp, vp]
+        for f in ("am355_encode_change", "am355_apply_local_change", "am355_local_change_calls"):
+            getattr(L, f).restype = ctypes.c_int
     L.am355_get_raw.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32)]
     L.am355_doc_changes.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_void_p)]
     L.am355_apply_changes.argtypes = [vp, vp, u64p, u32]
@@ -227,6 +438,31 @@ class Engine:
         offsets = np.ascontiguousarray(log.offsets, dtype=np.uint64)
         self._check(self._L.am355_apply_changes(self._h, arena.ctypes.data if arena.size else None, offsets.ctypes.data, int(offsets.size - 1)))
         self._n_changes = int(self.stats().n_changes)
+
+    def encode_change(self, request):
+        """encodeChange(request) (columnar.js:710-739) with the deps as given, the op columns encoded on the device: (bytes, hash).
+        Nothing of the state is read or touched. `request`: the reference's change request, see flatten_change_request."""
+        lc, keep = flatten_change_request(request)
+        p, n, h = ctypes.c_void_p(), ctypes.c_size_t(), (ctypes.c_uint8 * 32)()
+        self._check(self._L.am355_encode_change(self._h, ctypes.byref(lc), ctypes.byref(p), ctypes.byref(n), h))
+        del keep
+        return ctypes.string_at(p, n.value), bytes(h)
+
+    def apply_local_change(self, request):
+        """Backend.applyLocalChange(state, request) (backend.js:54-91): returns the binary change; apply_patch_json() then gives the patch.
+        InvalidChanges where the reference throws, UnsupportedChanges for what is left to the JS path (include/am355.h)."""
+        lc, keep = flatten_change_request(request)
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._L.am355_apply_local_change(self._h, ctypes.byref(lc), ctypes.byref(p), ctypes.byref(n)))
+        del keep
+        self._n_changes = int(self.stats().n_changes)
+        return ctypes.string_at(p, n.value)
+
+    def local_change_calls(self):
+        """(requests apply_local_change served, requests it refused)."""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self._L.am355_local_change_calls(self._h, out))
+        return int(out[0]), int(out[1])
 
     def reset(self):
         """Forget the state: the next apply_changes starts from Backend.init()."""

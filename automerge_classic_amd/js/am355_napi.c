@@ -686,6 +686,10 @@ static napi_value fetch_ir_common(napi_env env, napi_callback_info info, int app
   set_num(env, o, "nObjects", ir.n_objects); set_num(env, o, "nMap", ir.n_map); set_num(env, o, "nEdits", ir.n_edits);
   set_num(env, o, "nValues", ir.n_values); set_num(env, o, "nActors", ir.n_actors); set_num(env, o, "maxOp", (double)ir.max_op);
   set_num(env, o, "pending", ir.pending);
+  am355_local_envelope local;
+  if (apply && am355_apply_local_envelope(ctx, &local) == AM355_OK && local.is_local) {   /* the patch of applyLocalChange: actor and seq behind diffs; heads came without the change's own hash */
+    set_num(env, o, "isLocal", 1); set_num(env, o, "localActor", local.actor); set_num(env, o, "localSeq", (double)local.seq);
+  }
   return o;
 }
 static napi_value js_fetch_ir(napi_env env, napi_callback_info info) { return fetch_ir_common(env, info, 0); }
@@ -842,6 +846,98 @@ static napi_value js_shard_finalize(napi_env env, napi_callback_info info) {
   return u;
 }
 
+/* A change request as js/local_change.js flattens it: { seq, startOp, time, notFlat, message, deps, actorBytes, strings: Uint8Array,
+ * actorOff, actorRank, ops (13 words per op), values (6 words per value: tag, off, len, 0, payload low, payload high), preds (2 words
+ * per pred): Uint32Array } -> am355_local_change. No logic of its own: the arrays are handed over as they are. */
+static bool flat_array(napi_env env, napi_value o, const char *name, size_t elem, const void **data, size_t *count) {
+  napi_value v;
+  napi_typedarray_type type;
+  size_t length = 0;
+  void *p = NULL;
+  *data = NULL; *count = 0;
+  if (napi_get_named_property(env, o, name, &v) != napi_ok || napi_get_typedarray_info(env, v, &type, &length, &p, NULL, NULL) != napi_ok) return false;
+  if ((elem == 1 && type != napi_uint8_array) || (elem == 4 && type != napi_uint32_array)) return false;
+  *data = p; *count = length;
+  return true;
+}
+static bool flat_number(napi_env env, napi_value o, const char *name, double *out) {
+  napi_value v;
+  return napi_get_named_property(env, o, name, &v) == napi_ok && napi_get_value_double(env, v, out) == napi_ok;
+}
+static bool flat_request(napi_env env, napi_value o, am355_local_change *lc) {
+  double seq = 0, start_op = 0, time = 0, not_flat = 0;
+  const void *p;
+  size_t n, n_off, n_rank;
+  memset(lc, 0, sizeof *lc);
+  if (!flat_number(env, o, "seq", &seq) || !flat_number(env, o, "startOp", &start_op) || !flat_number(env, o, "time", &time) || !flat_number(env, o, "notFlat", &not_flat)) return false;
+  lc->not_flat = not_flat != 0 || seq < 0 || start_op < 0 || seq > 9007199254740991.0 || start_op > 9007199254740991.0 || time > 9007199254740991.0 || time < -9007199254740991.0;
+  if (lc->not_flat) return true;
+  lc->seq = (uint64_t)seq; lc->start_op = (uint64_t)start_op; lc->time = (int64_t)time;
+  if (!flat_array(env, o, "message", 1, &p, &n)) return false;
+  lc->message = (const uint8_t *)p; lc->message_len = (uint32_t)n;
+  if (!flat_array(env, o, "deps", 1, &p, &n) || n % 32) return false;
+  lc->deps = (const uint8_t *)p; lc->n_deps = (uint32_t)(n / 32);
+  if (!flat_array(env, o, "actorOff", 4, &p, &n_off) || n_off < 2) return false;
+  lc->actor_off = (const uint32_t *)p; lc->n_actors = (uint32_t)(n_off - 1);
+  if (!flat_array(env, o, "actorRank", 4, &p, &n_rank) || n_rank != n_off - 1) return false;
+  lc->actor_rank = (const uint32_t *)p;
+  if (!flat_array(env, o, "actorBytes", 1, &p, &n) || n < lc->actor_off[lc->n_actors]) return false;
+  lc->actor_bytes = (const uint8_t *)p;
+  if (!flat_array(env, o, "strings", 1, &p, &n)) return false;
+  lc->strings = (const uint8_t *)p; lc->strings_len = (uint32_t)n;
+  if (!flat_array(env, o, "ops", 4, &p, &n) || n % (sizeof(am355_local_op) / 4)) return false;
+  lc->ops = (const am355_local_op *)p; lc->n_ops = (uint32_t)(n / (sizeof(am355_local_op) / 4));
+  if (!flat_array(env, o, "values", 4, &p, &n) || n % (sizeof(am355_local_value) / 4) || ((uintptr_t)p & 7)) return false;
+  lc->values = (const am355_local_value *)p; lc->n_values = (uint32_t)(n / (sizeof(am355_local_value) / 4));
+  if (!flat_array(env, o, "preds", 4, &p, &n) || n % 2) return false;
+  lc->preds = (const am355_local_pred *)p; lc->n_preds = (uint32_t)(n / 2);
+  return true;
+}
+/* encodeChange(ctx, flat) -> { change: Uint8Array, hash: Uint8Array(32) } = am355_encode_change;
+ * applyLocalChange(ctx, flat) -> Uint8Array (the binary change) = am355_apply_local_change: the patch is then read with fetchApplyIR */
+static napi_value local_change_common(napi_env env, napi_callback_info info, int apply) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  am355_local_change lc;
+  if (argc < 2 || !flat_request(env, argv[1], &lc)) { napi_throw_type_error(env, NULL, "expected a flattened change request (js/local_change.js)"); return NULL; }
+  const uint8_t *bytes = NULL;
+  size_t len = 0;
+  uint8_t hash[32];
+  int rc = apply ? am355_apply_local_change(ctx, &lc, &bytes, &len) : am355_encode_change(ctx, &lc, &bytes, &len, hash);
+  if (rc) return throw_engine(env, ctx, rc);
+  napi_value ab = copy_to_arraybuffer(env, bytes, len), change;
+  if (!ab) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &change));
+  if (apply) return change;
+  napi_value o, hab = copy_to_arraybuffer(env, hash, 32), h;
+  if (!hab) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, 32, hab, 0, &h));
+  NAPI_CALL(env, napi_create_object(env, &o));
+  napi_set_named_property(env, o, "change", change);
+  napi_set_named_property(env, o, "hash", h);
+  return o;
+}
+static napi_value js_encode_change(napi_env env, napi_callback_info info) { return local_change_common(env, info, 0); }
+static napi_value js_apply_local_change(napi_env env, napi_callback_info info) { return local_change_common(env, info, 1); }
+/* localChangeCalls(ctx) -> [served, refused] = am355_local_change_calls */
+static napi_value js_local_change_calls(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  uint64_t out[2] = {0, 0};
+  int rc = am355_local_change_calls(ctx, out);
+  if (rc) return throw_engine(env, ctx, rc);
+  napi_value arr, v;
+  NAPI_CALL(env, napi_create_array_with_length(env, 2, &arr));
+  for (uint32_t k = 0; k < 2; k++) { napi_create_double(env, (double)out[k], &v); napi_set_element(env, arr, k, v); }
+  return arr;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"create", NULL, js_create, NULL, NULL, NULL, napi_enumerable, NULL},
@@ -874,6 +970,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"bloomBuild", NULL, js_bloom_build, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomProbe", NULL, js_bloom_probe, NULL, NULL, NULL, napi_enumerable, NULL},
       {"fetchApplyIR", NULL, js_fetch_apply_ir, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"encodeChange", NULL, js_encode_change, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"applyLocalChange", NULL, js_apply_local_change, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"localChangeCalls", NULL, js_local_change_calls, NULL, NULL, NULL, napi_enumerable, NULL},
       {"shardUniqueId", NULL, js_shard_unique_id, NULL, NULL, NULL, napi_enumerable, NULL},
       {"shardInit", NULL, js_shard_init, NULL, NULL, NULL, napi_enumerable, NULL},
       {"shardedReplay", NULL, js_sharded_replay, NULL, NULL, NULL, napi_enumerable, NULL},

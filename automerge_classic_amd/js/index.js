@@ -9,7 +9,9 @@
 //   applyChanges(state, changes) with its incremental patch        (backend/backend.js:27-31; SURVEY.md 8f-2) when `state` is empty
 //                                                                  or was built by the engine
 //   load / save / getAllChanges after load                         (SURVEY.md a21, 8f-1, 8f-3)
-// Everything else (applyLocalChange, clone, hash-graph queries with dependencies) is delegated to the reference JS backend, onto
+//   applyLocalChange(state, request) -> [state', patch, change]    (backend/backend.js:54-91) for the states applyChanges is served on:
+//                                                                  the change is built on the device (local_change.js, am355_apply_local_change)
+// Everything else (clone, getChangesAdded, requests the engine refuses) is delegated to the reference JS backend, onto
 // which a GPU-built state is hydrated lazily -- by replaying the retained change buffers -- the first time such a
 // call is made.  Inputs the engine rejects (AM355_E_INVALID: the reference would throw; AM355_E_UNSUPPORTED: legal
 // but outside the GPU-served subset) are re-run on the JS path so the caller sees the reference's exact exception
@@ -24,7 +26,9 @@ const MAP_MERGE = process.env.MI355X_MAP_MERGE === '1'   // am355_set_resident_m
 const NEW_OBJECTS = process.env.MI355X_NEW_OBJECTS !== '0'   // am355_set_resident_new_objects for every context of this module (MI355X_NEW_OBJECTS=0: off, for A/B)
 const COUNTERS = process.env.MI355X_COUNTERS !== '0'   // am355_set_resident_counters for every context of this module (MI355X_COUNTERS=0: off, for A/B)
 const PATCH_VIA_JSON = process.env.MI355X_PATCH_VIA_JSON === '1'   // A/B: JSON text rendered by the engine + JSON.parse
+const LOCAL_CHANGE = process.env.MI355X_LOCAL_CHANGE !== '0'   // applyLocalChange on the engine (MI355X_LOCAL_CHANGE=0: the reference path, for A/B)
 const { materialize } = require('./materialize.js')
+const { flatten } = require('./local_change.js')
 let addon = null, ctx = null
 // A few engine contexts, used least-recently-used first: a GPU-built state remembers which replay (generation) made it, and as
 // long as that replay still sits in one of the contexts, Backend.save of the state is served from it instead of replaying the
@@ -118,7 +122,7 @@ function contextOf(gen) {
   if (e) { e.used = ++tick; ctx = e.ctx }
   return e || null
 }
-const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0 }   // (diagnostics: which path served the calls)
+const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0 }   // (diagnostics: which path served the calls)
 
 function isFrozenCheck(backend) {
   // reference util.js:1-10
@@ -425,8 +429,10 @@ function hashesExtended(g, state, n) {
 const PROFILE = !!process.env.AM355_JS_PROFILE
 const now = () => Number(process.hrtime.bigint()) / 1e6
 const profile = { calls: 0, before_ms: 0, engine_ms: 0, patch_ms: 0, state_ms: 0 }
-function gpuApplyChanges(backend, changes) {
-  const tpIn = PROFILE ? now() : 0
+// The context that holds the state of `backend` (replayed into one if none does), ready for a call that goes onto it; null: the
+// state's history is not to be had from the engine (the reference path serves the call). handed: queued changes that are not in the
+// context (see heldBack), to be given behind the batch.
+function contextForApply(backend) {
   const g = backend.state instanceof GpuState ? backend.state : null
   if (g && g.doc && !g.changes) {
     loadedHistory(g)   // a loaded document: its changes, rebuilt by the engine (am355_doc_changes)
@@ -461,6 +467,14 @@ function gpuApplyChanges(backend, changes) {
   }
   const docLineage = !!(g && (g.doc || g.fromDocument))
   if (docLineage && g.graphKnown) addon.hashGraphKnown(ctx, 1)
+  return { g, entry, handed, docLineage }
+}
+
+function gpuApplyChanges(backend, changes) {
+  const tpIn = PROFILE ? now() : 0
+  const at = contextForApply(backend)
+  if (!at) return null
+  const { entry, handed } = at
   const tp0 = PROFILE ? now() : 0
   try {
     addon.applyChanges(ctx, handed ? changes.concat(handed) : changes)
@@ -471,6 +485,16 @@ function gpuApplyChanges(backend, changes) {
   const tp1 = PROFILE ? now() : 0
   const patch = materialize(addon.fetchApplyIR(ctx, true))
   const tp2 = PROFILE ? now() : 0
+  const result = stateAfterApply(at, changes, patch, false)
+  counters.gpuApplyChanges++
+  if (PROFILE) { const tp3 = now(); profile.calls++; profile.before_ms += tp0 - tpIn; profile.engine_ms += tp1 - tp0; profile.patch_ms += tp2 - tp1; profile.state_ms += tp3 - tp2 }
+  return result
+}
+
+// The new state behind a call the engine served on the context of contextForApply: `changes` is the batch (a local change: the one
+// binary change the engine made). graphFirst: the reference rebuilt the document's hash graph BEFORE it applied the batch
+// (applyLocalChange looking for the author's last hash, backend.js:38-39).
+function stateAfterApply({ g, entry, handed, docLineage }, changes, patch, graphFirst) {
   // the engine's list of changes: those applied so far in application order, the batch, those that were queued
   const list = !g ? changes.slice() : g.inOrder ? g.changes.concat(changes)
     : Array.from(g.applied, i => g.changes[i]).concat(changes, Array.from(g.pendingIdx, i => g.changes[i]))
@@ -496,10 +520,59 @@ function gpuApplyChanges(backend, changes) {
   state.graphKnown = docLineage ? addon.hashGraphKnown(ctx, -1) : undefined   // (has this call made the reference rebuild the document's hash graph?)
   state.docChanges = g ? (g.doc ? g.changes.length : (g.docChanges || 0)) : 0   // the leading changes that are a loaded document's
   state.baseDoc = g ? (g.baseDoc || g.doc || null) : null
-  state.batches = (g && g.batches ? g.batches : (g && g.doc && g.graphKnown ? [GRAPH_QUERY] : [])).concat([changes.slice()])
-  counters.gpuApplyChanges++
-  if (PROFILE) { const tp3 = now(); profile.calls++; profile.before_ms += tp0 - tpIn; profile.engine_ms += tp1 - tp0; profile.patch_ms += tp2 - tp1; profile.state_ms += tp3 - tp2 }
-  return [{ state, heads: patch.deps }, patch]
+  state.batches = (g && g.batches ? g.batches : (g && g.doc && g.graphKnown ? [GRAPH_QUERY] : [])).concat(graphFirst ? [GRAPH_QUERY] : [], [changes.slice()])
+  return [{ state, heads: state.heads }, patch]
+}
+
+// Backend.applyLocalChange(backend, request) -> [backend', patch, binaryChange] (backend.js:54-91) on the engine, for the states
+// applyChanges is served on: the request is flattened (local_change.js), the engine builds the binary change on the device, applies it
+// as a one-change batch onto the state its context holds and returns the change; the patch carries `actor` and `seq` and its deps
+// leave out the change's own hash, the state's heads do not (backend.js:88-90). A lineage that began with a loaded document: the
+// engine notices when the reference would rebuild the document's hash graph to find the author's last hash (am355.h), and the new
+// state remembers it as a graph query in front of the batch. null: not served (the reference path runs the request).
+function gpuApplyLocalChange(backend, request) {
+  const flat = flatten(request)
+  const at = contextForApply(backend)
+  if (!at || at.handed) return null
+  const knownBefore = at.docLineage ? !!addon.hashGraphKnown(ctx, -1) : true
+  let binaryChange
+  try {
+    binaryChange = addon.applyLocalChange(ctx, flat)
+  } catch (e) {
+    at.entry.generation = 0   // (whatever the context holds now is taken to be nobody's state: the reference path goes on from here)
+    throw e
+  }
+  const ir = addon.fetchApplyIR(ctx, true)
+  const patch = materialize(ir)
+  const graphFirst = at.docLineage && !knownBefore && !!addon.hashGraphKnown(ctx, -1)
+  const result = stateAfterApply(at, [binaryChange], patch, graphFirst)
+  // the state's heads are the document's, the new change's hash among them (backend.js:90 returns state.heads, not patch.deps)
+  const own = hexOfHash(result[0].state, result[0].state.hashes.length / 32 - 1)
+  const heads = patch.deps.concat([own]).sort()
+  result[0].state.heads = heads
+  result[0].heads = heads
+  counters.gpuApplyLocalChange++
+  return [result[0], patch, binaryChange]
+}
+function applyLocalChange(backend, request) {
+  isFrozenCheck(backend)
+  const served = !JS_ONLY && LOCAL_CHANGE && ((backend.state instanceof GpuState && !backend.state.js) || isEmptyRefState(backend))
+  if (served) {
+    try {
+      const result = gpuApplyLocalChange(backend, request)
+      if (result) { backend.frozen = true; return result }
+      counters.localFallbacks++
+    } catch (e) {
+      if (e.am355Code !== AM355_E_INVALID && e.am355Code !== AM355_E_UNSUPPORTED && !(e instanceof TypeError)) throw e
+      counters.localFallbacks++
+    }
+  }
+  // (the reference freezes the handle it is given only once the request is through, backend.js:85: a request it throws on leaves the
+  // wrapper's handle usable as well)
+  const handle = hydrate(backend)
+  const result = ref().applyLocalChange(handle, request)
+  if (backend.state instanceof GpuState) { backend.state.js = null; backend.frozen = true }
+  return result
 }
 
 function applyChanges(backend, changes) {
@@ -747,7 +820,7 @@ module.exports = {
   init, load, loadChanges, getPatch, getHeads, free, save, getAllChanges, getChanges, getChangeByHash, getMissingDeps,
   clone: backend => { noteGraphQuery(backend); return ref().clone(hydrate(backend)) },
   applyChanges,
-  applyLocalChange: delegate1('applyLocalChange'),
+  applyLocalChange,
   getChangesAdded: (b1, b2) => { noteGraphQuery(b1); return ref().getChangesAdded(hydrate(b1), hydrate(b2)) },
   // sync protocol: the reference's own backend/sync.js bound to this module (boundSync above)
   generateSyncMessage: (...a) => syncModule().generateSyncMessage(...a),

@@ -210,7 +210,12 @@ class Materializer {
     for (let i = 0; i < clockActor.length; i++) clock[this.actors[clockActor[i]].slice(1)] = clockSeq[i]
     const heads = new Uint8Array(ir.heads), deps = []
     for (let i = 0; i + 32 <= heads.length; i += 32) deps.push(hexOf(heads, i, i + 32))
-    return { maxOp: ir.maxOp, clock, deps, pendingChanges: ir.pending, diffs: this.object(0) }
+    const patch = { maxOp: ir.maxOp, clock, deps, pendingChanges: ir.pending, diffs: this.object(0) }
+    if (ir.isLocal) {   // the patch of applyLocalChange: actor and seq behind diffs (new.js:1874-1877); `heads` came without the change's own hash
+      patch.actor = this.actors[ir.localActor].slice(1)
+      patch.seq = ir.localSeq
+    }
+    return patch
   }
 }
 

@@ -285,6 +285,88 @@ int am355_apply_patch_json(am355_ctx *ctx, const char **json, size_t *len);
 int am355_fetch_apply_ir(am355_ctx *ctx, am355_patch_ir *out);
 
 /*
+ * Backend.applyLocalChange(state, request) (reference: backend/backend.js:54-91; backend/columnar.js:710-739 encodeChange, :446-475
+ * expandMultiOps, :122-170 parseAllOpIds, :370-444 encodeOps). A change REQUEST is what the frontend hands over: ops that still carry
+ * `values` / `multiOp`, no hash. Here it is flat -- the bindings fill it (engine.py, js/local_change.js), nothing in C parses JS
+ * objects or JSON --, the device expands the ops into rows, gives numbers their bytes and encodes the twelve op columns
+ * (am355_hist.hip kl_expand + the encoders of am355_encode.hip); the host writes the container around them and hashes it.
+ *
+ * Actors are CHANGE-LOCAL numbers: the table holds the author first, then every other actor an op names, in byte order
+ * (columnar.js:154-157), each exactly once; actor_rank[i] = position of entry i among all entries in byte order (preds of an op are
+ * ordered by counter, then by actor id -- not by local number: compareParsedOpIds). Keys and UTF-8 values are ranges of `strings`.
+ */
+enum { AM355_LK_STRING = 0, AM355_LK_HEAD = 1, AM355_LK_ELEM = 2 };          /* am355_local_op.key_kind */
+enum { AM355_LOP_INSERT = 1u, AM355_LOP_VALUES = 2u };                       /* am355_local_op.flags: `insert` | the op has `values` */
+enum { AM355_LV_NULL = 0, AM355_LV_FALSE = 1, AM355_LV_TRUE = 2, AM355_LV_UINT = 3, AM355_LV_INT = 4, AM355_LV_FLOAT64 = 5,
+       AM355_LV_UTF8 = 6, AM355_LV_BYTES = 7, AM355_LV_COUNTER = 8, AM355_LV_TIMESTAMP = 9,
+       AM355_LV_BAD = 15 /* a value the reference throws on: a bad value / datatype pair of a multi-insert, a number its datatype cannot hold */ };
+typedef struct {
+  uint32_t action;                 /* index into ACTIONS: 0 makeMap, 1 set, 2 makeList, 3 del, 4 makeText, 5 inc, 6 makeTable */
+  uint32_t obj_actor, obj_ctr;     /* obj_actor UINT32_MAX: _root */
+  uint32_t key_kind;               /* AM355_LK_* */
+  uint32_t key_off, key_len;       /* AM355_LK_STRING */
+  uint32_t elem_actor, elem_ctr;   /* AM355_LK_ELEM */
+  uint32_t flags;                  /* AM355_LOP_* */
+  uint32_t multi;                  /* rows the op expands to: values.length with AM355_LOP_VALUES, multiOp of a `del`, else 1 */
+  uint32_t val_first;              /* `set` / `inc`: its value; with AM355_LOP_VALUES the first of `multi` values */
+  uint32_t pred_first, pred_num;
+} am355_local_op;
+typedef struct {
+  uint32_t tag;                    /* AM355_LV_* */
+  uint32_t off, len;               /* AM355_LV_UTF8: range of `strings` */
+  uint32_t pad;
+  uint64_t payload;                /* UINT; INT / COUNTER / TIMESTAMP (two's complement); FLOAT64 (the IEEE 754 bits) */
+} am355_local_value;
+typedef struct { uint32_t actor, ctr; } am355_local_pred;
+typedef struct {
+  uint64_t seq, start_op;
+  int64_t time;
+  const uint8_t *message; uint32_t message_len;   /* UTF-8, may be empty */
+  const uint8_t *deps; uint32_t n_deps;           /* 32 bytes each, any order: the frontend's (other actors' heads) */
+  uint32_t n_actors;                              /* >= 1; entry 0 is the author */
+  const uint32_t *actor_off;                      /* [n_actors + 1] into actor_bytes (raw bytes, not hex) */
+  const uint8_t *actor_bytes;
+  const uint32_t *actor_rank;                     /* [n_actors] */
+  const uint8_t *strings; uint32_t strings_len;
+  const am355_local_op *ops; uint32_t n_ops;
+  const am355_local_value *values; uint32_t n_values;
+  const am355_local_pred *preds; uint32_t n_preds;
+  uint32_t not_flat;   /* != 0: the request holds what this form cannot express (child / link ops, numeric actions or datatypes, extraBytes,
+                          a `hash` field ...): refused with AM355_E_UNSUPPORTED like what the engine itself does not serve */
+} am355_local_change;
+/*
+ * am355_encode_change: encodeChange(request) with the deps as given -- nothing of the context's state is read or touched. *bytes is the
+ * binary change as encodeChange returns it (DEFLATEd from 256 bytes on), owned by ctx, valid until the next of these two calls.
+ * am355_apply_local_change: backend.js:54-91 -- the seq check; for seq > 1 the author's last hash joins the deps; encode; the
+ * one-change batch goes through am355_apply_changes (as the uncompressed container) with the local flag; *change as above. Afterwards
+ * am355_apply_patch_json / am355_fetch_apply_ir give the patch applyLocalChange returned.
+ * AM355_E_INVALID: the reference throws (a multi-insert with a pred, a multiOp deletion without exactly one pred, a bad value /
+ * datatype pair, a seq already applied, no change of the author with seq - 1). AM355_E_UNSUPPORTED: not_flat, byte-array values,
+ * unknown actions or value tags, an op of more than 4096 preds, counters beyond 2^31, changes still queued in the state, a sharded
+ * context. Both are decided before anything of the state is touched (a document context is at most turned into the state of its
+ * rebuilt changes, as am355_apply_changes does); the JS host runs the reference on a refused request, so the exception is the
+ * reference's own. A refusal of the apply path itself drops the state as am355_apply_changes does; so does a change that did not
+ * apply because a dependency is missing (the reference throws behind the apply then).
+ * A lineage that began with a document: the reference rebuilds the document's hash graph when the author's last hash is not among
+ * the changes applied since the load (hashByActor, backend.js:34-45) -- the call does what am355_hash_graph_known(ctx, 1) does at
+ * exactly that point, and refuses where the host replayed retained changes and the engine cannot tell (am355_forget_call_history).
+ * am355_local_change_calls: out[0] requests am355_apply_local_change served, out[1] requests it refused (whatever the code);
+ * am355_encode_change applies nothing and is not counted.
+ */
+int am355_encode_change(am355_ctx *ctx, const am355_local_change *request, const uint8_t **bytes, size_t *len, uint8_t hash[32]);
+int am355_apply_local_change(am355_ctx *ctx, const am355_local_change *request, const uint8_t **change, size_t *len);
+int am355_local_change_calls(const am355_ctx *ctx, uint64_t out[2]);
+/* What the patch of am355_apply_local_change carries beyond the record tables of am355_fetch_apply_ir (whose layout stays as it is):
+ * `actor` and `seq` behind `diffs` (new.js:1874-1877). The tables' `heads` are already without the new change's own hash
+ * (backend.js:88-89). is_local == 0 when the last patch came from am355_apply_changes. Valid when am355_fetch_apply_ir is. */
+typedef struct {
+  uint32_t is_local;
+  uint32_t actor;   /* actor rank (am355_patch_ir.actor_off / actor_bytes) */
+  uint64_t seq;
+} am355_local_envelope;
+int am355_apply_local_envelope(const am355_ctx *ctx, am355_local_envelope *out);
+
+/*
  * Sync protocol, bulk side (reference backend/sync.js).  A sync message that carries changes is served by
  * am355_apply_changes; what the protocol computes around it over the hashes of a replayed state:
  *   am355_get_dep_graph     the dependency graph of the context's list of changes by index (change i depends on
