@@ -772,6 +772,7 @@ extern "C" int am355_reset(am355_ctx* c) {
   c->staged = c->replayed = c->ir_fetched = c->apply_ready = false;
   c->resident_valid = false;
   c->arena_epoch++;
+  c->graph_epoch++;
   c->state_checked = true;
   c->stream_breaks.clear();
   c->breaks_exact = true;
@@ -924,3 +925,9 @@ int sync_bloom_impl(am355_ctx* c, const uint32_t* idx, uint32_t n, uint32_t num_
 // ---------------------------------------------------------------------------------------------------------
 // diagnostics
 // ---------------------------------------------------------------------------------------------------------
+
+// ---------------------------------------------------------------------------------------------------------
+// hash-graph queries over the applied changes: a file of their own, compiled as part of this translation unit (the lists of sources of
+// the product build and of the CPU test harness stay as they are)
+// ---------------------------------------------------------------------------------------------------------
+#include "am355_graph.hip"

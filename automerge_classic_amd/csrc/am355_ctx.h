@@ -1,7 +1,7 @@
 // Context of the C ABI (include/am355.h) and what its translation units share: device / pinned buffers, the host thread pool, struct
 // am355_ctx, error helpers. am355_api.hip: entry points; am355_stage.hip: staging; am355_replay.hip: scheduler, plan, orchestration of
-// the device stages; am355_calls.hip: patch IR, applyChanges, dependency graph, Bloom filters; am355_save.hip: save + history after
-// load; am355_shard.hip: objectId sharding.
+// the device stages; am355_calls.hip: patch IR, applyChanges, dependency graph, Bloom filters -- and, included at its end,
+// am355_graph.hip: the hash-graph queries; am355_save.hip: save + history after load; am355_shard.hip: objectId sharding.
 #pragma once
 #include "../../include/am355.h"
 #include "am355_decode.h"
@@ -452,6 +452,32 @@ struct am355_ctx {
   std::vector<uint32_t> dep_first, dep_index;   // am355_get_dep_graph
   bool dep_graph_ready = false;
   DevBuf d_sync;                                // am355_sync_bloom_*: index list, filter bits, flags
+  // Hash-graph queries (am355_graph.hip: am355_find_changes, am355_changes_since, am355_changes_added, am355_missing_deps). The host
+  // half describes the first n_applied entries of applied_change of replay `epoch` (graph_epoch: bumped by every replay that makes the
+  // applied list anew; a resident call appends to it) and is extended, not rebuilt, while only that list has grown.
+  struct GraphIndex {
+    uint64_t epoch = ~0ull;
+    uint32_t n_staged = 0, n_applied = 0;           // staged changes with a dependency record | applied entries indexed
+    std::vector<uint32_t> dep_first, dep_index;     // dependencies by staged index (of applied changes: the applied copy's index)
+    std::vector<uint8_t> is_applied;                // by staged index
+    std::vector<uint32_t> table;                    // hash -> staged index of the applied change: open addressing, index + 1, 0 empty
+    // dependents in the order the reference pushes them (new.js:1853-1856): a CSR over the first dpt_applied applied entries, and the
+    // pushes made since as chains behind it (folded into the CSR once they outnumber it)
+    std::vector<uint32_t> dpt_first, dpt_index;
+    uint32_t dpt_applied = 0;
+    std::vector<uint32_t> chain_head, chain_tail, chain_child, chain_next;
+    std::vector<uint32_t> out_idx;                  // result of the last query
+    std::vector<uint8_t> out_hashes;
+    std::vector<uint64_t> absent;                   // am355_changes_added: one bit per staged change, set = `other` does not hold it
+    // device half: d_hash_tab holds staged changes [0, tab_n) of replay tab_epoch under tab_mask (am355_graph.hip k_graph_insert)
+    uint64_t tab_epoch = ~0ull;
+    uint32_t tab_n = 0, tab_mask = 0;
+  } graph;
+  uint64_t graph_epoch = 0;
+  uint32_t graph_probe_min = 65536;                 // am355_set_graph_probe_min: fewest probes that go to the device (0xffffffff: never); the default: profiles/hash_graph_timings.txt
+  uint64_t n_graph_device = 0, n_graph_host = 0;    // am355_graph_query_calls
+  DevBuf d_graph;                                   // queries | found indexes | table over `other` | absence words
+  HostBuf h_graph;                                  // pinned: found indexes / absence words on their way down
   // am355_apply_changes: where the op streams of the calls so far began (a call of applyChanges, a scheduling pass of one) -- the
   // reference's merge calls never cross them --, whether that record is complete, and whether some call skipped values of a property
   // that holds a child object (then objectMeta.children of the reference differs from the visible values: delta_key_history)
@@ -636,6 +662,12 @@ int apply_local_change_impl(am355_ctx* c, const am355_local_change* lc, const ui
 int get_dep_graph_impl(am355_ctx* c, const uint32_t** dep_first, const uint32_t** dep_index, uint32_t* n_changes);
 int sync_bloom_impl(am355_ctx* c, const uint32_t* idx, uint32_t n, uint32_t num_entries, uint32_t bits_per_entry, uint32_t num_probes, const uint8_t* bits, size_t n_bytes,
                     uint8_t* out, size_t cap, bool build);
+// hash-graph queries over the applied changes (am355_graph.hip)
+int find_changes_impl(am355_ctx* c, const uint8_t* hashes, uint32_t n, uint32_t* out_idx);
+int changes_since_impl(am355_ctx* c, const uint8_t* have, uint32_t n_have, const uint32_t** idx, uint32_t* n);
+int changes_added_impl(am355_ctx* c, const uint8_t* other, uint32_t n_other, const uint32_t** idx, uint32_t* n);
+int missing_deps_impl(am355_ctx* c, const uint8_t* heads, uint32_t n_heads, const uint8_t** hashes, uint32_t* n);
+int test_hash_probe_impl(am355_ctx* c, const uint8_t* table_hashes, uint32_t n_table, const uint8_t* queries, uint32_t n_queries, uint32_t* out_idx);
 // documents out: Backend.save, history after load (am355_save.hip); objectId sharding (am355_shard.hip)
 int save_impl(am355_ctx* c, uint32_t flags, const uint8_t** out_bytes, size_t* out_len);
 int doc_changes_impl(am355_ctx* c, uint32_t flags, const uint8_t** arena, const uint64_t** offsets, uint32_t* n_changes, const uint8_t** hashes);

@@ -61,11 +61,7 @@ struct CurT {
 using Cur = CurT<const uint8_t*>;
 using CurLds = CurT<LdsBytes>;
 
-// 16-byte loads at arbitrary alignment (changes are packed back to back in the arena; gfx950 global loads are
-// alignment-agnostic, so this compiles to global_load_dwordx4)
-struct __attribute__((packed)) U4 {
-  uint32_t x, y, z, w;
-};
+// (U4 -- 16-byte loads at arbitrary alignment --, equal32 and hash_slot: am355_device.h)
 struct alignas(16) V4 {  // the same 16 bytes at a 16-byte aligned LDS address
   uint32_t x, y, z, w;
 };
@@ -930,15 +926,6 @@ __global__ __launch_bounds__(2 * HASH_LANES) void k_hash_changes(const uint8_t* 
   out[1] = hi;
 }
 
-__device__ __forceinline__ bool equal32(const uint8_t* a, const uint8_t* b) {
-  U4 a0 = *(const U4*)a, a1 = *(const U4*)(a + 16), b0 = *(const U4*)b, b1 = *(const U4*)(b + 16);
-  return a0.x == b0.x && a0.y == b0.y && a0.z == b0.z && a0.w == b0.w && a1.x == b1.x && a1.y == b1.y && a1.z == b1.z && a1.w == b1.w;
-}
-__device__ __forceinline__ uint32_t hash_slot(const uint8_t* h, uint32_t mask) {
-  uint64_t v = 0;
-  for (int k = 0; k < 8; k++) v |= (uint64_t)h[k] << (8 * k);
-  return (uint32_t)((v * 0x9e3779b97f4a7c15ull) >> 32) & mask;
-}
 
 // device hash table of change hashes: tab[slot] = (index of the first change that claimed the slot) + 1;
 // min_idx[claimer] = smallest input index among the changes with that same hash (duplicates)

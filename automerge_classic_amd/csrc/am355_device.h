@@ -65,6 +65,25 @@ typedef const __attribute__((address_space(3))) uint8_t* LdsBytes;
 
 __device__ __forceinline__ uint32_t gtid() { return blockIdx.x * blockDim.x + threadIdx.x; }
 
+// 16-byte loads at arbitrary alignment (changes are packed back to back in the arena; gfx950 global loads are
+// alignment-agnostic, so this compiles to global_load_dwordx4)
+struct __attribute__((packed)) U4 {
+  uint32_t x, y, z, w;
+};
+
+// The tables of change hashes (am355_decode.hip k_hash_insert, am355_graph.hip): open addressing over a power of two of words that
+// hold change index + 1 (0: empty), probed linearly from hash_slot -- the first eight bytes of the hash, little-endian, times the
+// golden-ratio constant, upper half, masked --, every hit confirmed by the full 32-byte compare.
+__device__ __forceinline__ bool equal32(const uint8_t* a, const uint8_t* b) {
+  U4 a0 = *(const U4*)a, a1 = *(const U4*)(a + 16), b0 = *(const U4*)b, b1 = *(const U4*)(b + 16);
+  return a0.x == b0.x && a0.y == b0.y && a0.z == b0.z && a0.w == b0.w && a1.x == b1.x && a1.y == b1.y && a1.z == b1.z && a1.w == b1.w;
+}
+__device__ __forceinline__ uint32_t hash_slot(const uint8_t* h, uint32_t mask) {
+  uint64_t v = 0;
+  for (int k = 0; k < 8; k++) v |= (uint64_t)h[k] << (8 * k);
+  return (uint32_t)((v * 0x9e3779b97f4a7c15ull) >> 32) & mask;
+}
+
 // Publishes `n_words` result words and then the sequence number into pinned host memory (HostSignals, am355_internal.h): called by
 // ONE thread, after everything the words summarise has been written by this or an earlier kernel.
 __device__ __forceinline__ void signal_host(uint32_t* host_words, const uint32_t* values, uint32_t n_words, volatile uint32_t* host_seq, uint32_t seq) {

@@ -2034,7 +2034,7 @@ int replay_impl(am355_ctx* c) {
   c->batch_list_only = false;
   c->h_tables_were_current = c->h_tables_current;   // (of the state before this replay: replay_resident may find them unchanged)
   c->h_tables_current = false;
-  if (c->is_document) return replay_document(c);
+  if (c->is_document) { c->graph_epoch++; return replay_document(c); }
   auto t_begin = std::chrono::steady_clock::now();
   if (c->in_apply && c->keep.want) {
     // Backend.applyChanges onto the state this context holds: the batch alone (replay_resident), unless it needs the general path
@@ -2062,6 +2062,7 @@ int replay_impl(am355_ctx* c) {
     }
   }
   c->keep.want = false;
+  c->graph_epoch++;   // (the applied list is made anew from here on: am355_graph.hip rebuilds its indexes instead of extending them)
   { int orc = flush_uploads(c); if (!orc) orc = upload_offsets(c); if (orc) return orc; }
   const bool trace = getenv("AM355_TRACE") != nullptr;
   auto lap = [&](const char* what) {

@@ -342,6 +342,16 @@ def _bind(path):
         L.am355_local_change_calls.argtypes = [vp, vp]
         for f in ("am355_encode_change", "am355_apply_local_change", "am355_local_change_calls"):
             getattr(L, f).restype = ctypes.c_int
+    if hasattr(L, "am355_changes_added"):   # (libraries of earlier commits, loaded for an A/B run, end before these)
+        L.am355_find_changes.argtypes = [vp, vp, u32, vp]
+        for f in ("am355_changes_since", "am355_changes_added", "am355_missing_deps"):
+            getattr(L, f).argtypes = [vp, vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32)]
+        L.am355_set_graph_probe_min.argtypes = [vp, u32]
+        L.am355_graph_query_calls.argtypes = [vp, vp]
+        L.am355_test_hash_probe.argtypes = [vp, vp, u32, vp, u32, vp]
+        for f in ("am355_find_changes", "am355_changes_since", "am355_changes_added", "am355_missing_deps", "am355_set_graph_probe_min", "am355_graph_query_calls",
+                  "am355_test_hash_probe"):
+            getattr(L, f).restype = ctypes.c_int
     L.am355_get_raw.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32)]
     L.am355_doc_changes.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_void_p)]
     L.am355_apply_changes.argtypes = [vp, vp, u64p, u32]
@@ -516,6 +526,63 @@ class Engine:
         self._check(self._L.am355_sync_bloom_probe(self._h, idx.ctypes.data if idx.size else None, idx.size, num_entries, bits_per_entry, num_probes,
                                                    bits.ctypes.data if bits.size else None, bits.size, out.ctypes.data))
         return out[:idx.size]
+
+    # ---- hash-graph queries over the applied changes (include/am355.h) -------------------------------------
+    @staticmethod
+    def _hash_rows(hashes):
+        """A list of 32-byte hashes (bytes or hex strings), or an (n, 32) array, as one contiguous (n, 32) uint8 array."""
+        if isinstance(hashes, np.ndarray):
+            a = np.ascontiguousarray(hashes, dtype=np.uint8).reshape(-1, 32)
+        else:
+            a = np.frombuffer(b"".join(bytes.fromhex(h) if isinstance(h, str) else bytes(h) for h in hashes), dtype=np.uint8).reshape(-1, 32)
+        return a
+
+    def find_changes(self, hashes):
+        """getChangeByHash for each hash: index of the applied change into the engine's list of changes, 0xffffffff where there is none."""
+        a = self._hash_rows(hashes)
+        out = np.full(a.shape[0], 0xFFFFFFFF, dtype=np.uint32)
+        self._check(self._L.am355_find_changes(self._h, a.ctypes.data if a.size else None, a.shape[0], out.ctypes.data if a.size else None))
+        return out
+
+    def _index_query(self, fn, hashes):
+        a = self._hash_rows(hashes)
+        p, n = ctypes.c_void_p(), ctypes.c_uint32()
+        self._check(fn(self._h, a.ctypes.data if a.size else None, a.shape[0], ctypes.byref(p), ctypes.byref(n)))
+        return p, n.value
+
+    def changes_since(self, have):
+        """BackendDoc.getChanges(have) as indexes into the engine's list of changes, in the reference's order."""
+        p, n = self._index_query(self._L.am355_changes_since, have)
+        return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint32)), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+
+    def changes_added(self, other):
+        """BackendDoc(this).getChangesAdded(other) as indexes; `other`: the hashes of the changes the other state has applied."""
+        p, n = self._index_query(self._L.am355_changes_added, other)
+        return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint32)), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+
+    def missing_deps(self, heads=()):
+        """BackendDoc.getMissingDeps(heads): sorted list of 32-byte hashes."""
+        p, n = self._index_query(self._L.am355_missing_deps, heads)
+        raw = ctypes.string_at(p, 32 * n) if n else b""
+        return [raw[32 * k:32 * k + 32] for k in range(n)]
+
+    def set_graph_probe_min(self, n):
+        """Fewest membership probes of a hash-graph query that go to the device; 0xffffffff: never."""
+        self._check(self._L.am355_set_graph_probe_min(self._h, int(n)))
+
+    def graph_query_calls(self):
+        """(membership tests of hash-graph queries answered on the device, by the host index)."""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self._L.am355_graph_query_calls(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def prim_hash_probe(self, table_hashes, queries):
+        """am355_test_hash_probe: index into table_hashes of every query, 0xffffffff where it is not there (table and probes on the device)."""
+        t, q = self._hash_rows(table_hashes), self._hash_rows(queries)
+        out = np.full(q.shape[0], 0x55555555, dtype=np.uint32)
+        self._check(self._L.am355_test_hash_probe(self._h, t.ctypes.data if t.size else None, t.shape[0], q.ctypes.data if q.size else None, q.shape[0],
+                                                  out.ctypes.data if q.size else None))
+        return out
 
     def apply_patch_json(self):
         """JSON.stringify of the patch the last apply_changes returned (the reference's incremental patch)."""

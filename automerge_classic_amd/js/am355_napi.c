@@ -494,6 +494,106 @@ static napi_value js_dep_graph(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* hashes packed 32 bytes each in a Uint8Array (a view is fine): the pointer and how many; 0 when the argument is no such array */
+static int get_hash_array(napi_env env, napi_value v, const uint8_t **data, uint32_t *n) {
+  bool is_ta = false;
+  if (napi_is_typedarray(env, v, &is_ta) != napi_ok || !is_ta) return 0;
+  napi_typedarray_type t; size_t len; void *d; napi_value ab; size_t off;
+  if (napi_get_typedarray_info(env, v, &t, &len, &d, &ab, &off) != napi_ok || t != napi_uint8_array || len % 32 != 0 || len / 32 > 0xffffffffu) return 0;
+  *data = (const uint8_t *)d;
+  *n = (uint32_t)(len / 32);
+  return 1;
+}
+
+/* findChanges(ctx, Uint8Array hashes) -> Uint32Array: am355_find_changes (0xffffffff: no applied change has that hash) */
+static napi_value js_find_changes(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  const uint8_t *hashes = NULL;
+  uint32_t n = 0;
+  if (argc < 2 || !get_hash_array(env, argv[1], &hashes, &n)) { napi_throw_type_error(env, NULL, "findChanges takes a Uint8Array of 32-byte hashes"); return NULL; }
+  void *data = NULL;
+  napi_value ab, ta;
+  NAPI_CALL(env, napi_create_arraybuffer(env, 4 * (size_t)(n ? n : 1), &data, &ab));
+  int rc = am355_find_changes(ctx, hashes, n, (uint32_t *)data);
+  if (rc) return throw_engine(env, ctx, rc);
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, n, ab, 0, &ta));
+  return ta;
+}
+
+/* changesSince(ctx, Uint8Array have) / changesAdded(ctx, Uint8Array other) -> Uint32Array of indexes into the context's list of changes:
+   am355_changes_since / am355_changes_added (copies) */
+static napi_value index_query(napi_env env, napi_callback_info info, int (*fn)(am355_ctx *, const uint8_t *, uint32_t, const uint32_t **, uint32_t *), const char *usage) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  const uint8_t *hashes = NULL;
+  uint32_t n = 0, n_out = 0;
+  if (argc < 2 || !get_hash_array(env, argv[1], &hashes, &n)) { napi_throw_type_error(env, NULL, usage); return NULL; }
+  const uint32_t *idx = NULL;
+  int rc = fn(ctx, hashes, n, &idx, &n_out);
+  if (rc) return throw_engine(env, ctx, rc);
+  napi_value ab = copy_to_arraybuffer(env, idx, 4 * (size_t)n_out), ta;
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, n_out, ab, 0, &ta));
+  return ta;
+}
+static napi_value js_changes_since(napi_env env, napi_callback_info info) { return index_query(env, info, am355_changes_since, "changesSince takes a Uint8Array of 32-byte hashes"); }
+static napi_value js_changes_added(napi_env env, napi_callback_info info) { return index_query(env, info, am355_changes_added, "changesAdded takes a Uint8Array of 32-byte hashes"); }
+
+/* missingDeps(ctx, Uint8Array heads) -> Uint8Array of 32-byte hashes, sorted: am355_missing_deps (copies) */
+static napi_value js_missing_deps(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  const uint8_t *heads = NULL, *out = NULL;
+  uint32_t n = 0, n_out = 0;
+  if (argc < 2 || !get_hash_array(env, argv[1], &heads, &n)) { napi_throw_type_error(env, NULL, "missingDeps takes a Uint8Array of 32-byte hashes"); return NULL; }
+  int rc = am355_missing_deps(ctx, heads, n, &out, &n_out);
+  if (rc) return throw_engine(env, ctx, rc);
+  napi_value ab = copy_to_arraybuffer(env, out, 32 * (size_t)n_out), ta;
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, 32 * (size_t)n_out, ab, 0, &ta));
+  return ta;
+}
+
+/* setGraphProbeMin(ctx, n): am355_set_graph_probe_min (0xffffffff: the membership tests of the queries above never go to the device) */
+static napi_value js_set_graph_probe_min(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  uint32_t n = 0xffffffffu;
+  if (argc > 1) NAPI_CALL(env, napi_get_value_uint32(env, argv[1], &n));
+  int rc = am355_set_graph_probe_min(ctx, n);
+  if (rc) return throw_engine(env, ctx, rc);
+  return NULL;
+}
+
+/* graphQueryCalls(ctx) -> [membership tests on the device, by the host index]: am355_graph_query_calls */
+static napi_value js_graph_query_calls(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1], out, v;
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  uint64_t w[2] = {0, 0};
+  int rc = am355_graph_query_calls(ctx, w);
+  if (rc) return throw_engine(env, ctx, rc);
+  NAPI_CALL(env, napi_create_array_with_length(env, 2, &out));
+  for (uint32_t k = 0; k < 2; k++) {
+    NAPI_CALL(env, napi_create_double(env, (double)w[k], &v));
+    NAPI_CALL(env, napi_set_element(env, out, k, v));
+  }
+  return out;
+}
+
 /* bloomBuild(ctx, Uint32Array idx) -> Uint8Array: am355_sync_bloom_build (the `bits` of the filter over those changes' hashes) */
 static napi_value js_bloom_build(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -967,6 +1067,12 @@ static napi_value init(napi_env env, napi_value exports) {
       {"setResidentCounters", NULL, js_set_resident_counters, NULL, NULL, NULL, napi_enumerable, NULL},
       {"residentCounterCalls", NULL, js_resident_counter_calls, NULL, NULL, NULL, napi_enumerable, NULL},
       {"depGraph", NULL, js_dep_graph, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"findChanges", NULL, js_find_changes, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"changesSince", NULL, js_changes_since, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"changesAdded", NULL, js_changes_added, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"missingDeps", NULL, js_missing_deps, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"setGraphProbeMin", NULL, js_set_graph_probe_min, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"graphQueryCalls", NULL, js_graph_query_calls, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomBuild", NULL, js_bloom_build, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomProbe", NULL, js_bloom_probe, NULL, NULL, NULL, napi_enumerable, NULL},
       {"fetchApplyIR", NULL, js_fetch_apply_ir, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -11,7 +11,10 @@
 //   load / save / getAllChanges after load                         (SURVEY.md a21, 8f-1, 8f-3)
 //   applyLocalChange(state, request) -> [state', patch, change]    (backend/backend.js:54-91) for the states applyChanges is served on:
 //                                                                  the change is built on the device (local_change.js, am355_apply_local_change)
-// Everything else (clone, getChangesAdded, requests the engine refuses) is delegated to the reference JS backend, onto
+//   getChanges / getChangeByHash / getMissingDeps / getChangesAdded and the sync helpers over them: index lists from the engine's
+//                                                                  hash-graph queries (am355_changes_since, am355_find_changes,
+//                                                                  am355_missing_deps, am355_changes_added; new.js:1921-2028)
+// Everything else (clone, requests the engine refuses) is delegated to the reference JS backend, onto
 // which a GPU-built state is hydrated lazily -- by replaying the retained change buffers -- the first time such a
 // call is made.  Inputs the engine rejects (AM355_E_INVALID: the reference would throw; AM355_E_UNSUPPORTED: legal
 // but outside the GPU-served subset) are re-run on the JS path so the caller sees the reference's exact exception
@@ -36,6 +39,7 @@ let addon = null, ctx = null
 const MAX_CONTEXTS = Math.max(1, parseInt(process.env.MI355X_CONTEXTS || '4'))
 const contexts = []
 let tick = 0
+let graphProbeMin = null   // _setGraphProbeMin: given to every context made later too (null: the library's default)
 if (!JS_ONLY) {
   addon = require(path.join(__dirname, 'am355_napi.node'))
   ctx = addon.create(parseInt(process.env.MI355X_DEVICE || '0'))   // throws without an MI355X
@@ -107,6 +111,7 @@ function acquireContext() {
     // and every table rebuilt (the reference adds the increment to the counter's succ list in the block it visits, new.js:1052-1290);
     // measured faster than merge_run in every case timed, profiles/counter_apply_timings.txt: on unless MI355X_COUNTERS=0
     if (COUNTERS) addon.setResidentCounters(e.ctx, true)
+    if (graphProbeMin !== null) addon.setGraphProbeMin(e.ctx, graphProbeMin)
     contexts.push(e)
   } else {
     e = contexts.reduce((a, b) => (b.used < a.used ? b : a))
@@ -122,7 +127,7 @@ function contextOf(gen) {
   if (e) { e.used = ++tick; ctx = e.ctx }
   return e || null
 }
-const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0 }   // (diagnostics: which path served the calls)
+const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, gpuChangesAdded: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0 }   // (diagnostics: which path served the calls)
 
 function isFrozenCheck(backend) {
   // reference util.js:1-10
@@ -356,6 +361,33 @@ function loadedHistory(g) {
     counters.fallbackToJs++
   }
 }
+// The engine's own hash-graph queries serve a state while its context is live -- the replay that made the state still sits in it, so
+// the context's list of changes is g.changes index for index -- and holds changes: not a state whose queue is kept out of the
+// context (heldBack), not a loaded document that sits there as a document. Otherwise the JS restatements below run (hashIndex,
+// graphOf), which build their indexes per state.
+function engineGraph(g) {
+  if (JS_ONLY || heldBack(g) || (g.doc && !g.fromChanges)) return false
+  return !!contextOf(g.generation)
+}
+const HEX64 = /^[0-9a-f]{64}$/
+// hashes given as hex strings, packed for the addon; null when one of them is not the hex of 32 bytes (the JS path then answers as
+// the reference does for such a string)
+function packHashes(list) {
+  const out = Buffer.alloc(32 * list.length)
+  for (let k = 0; k < list.length; k++) {
+    if (typeof list[k] !== 'string' || !HEX64.test(list[k])) return null
+    out.write(list[k], 32 * k, 'hex')
+  }
+  return new Uint8Array(out.buffer, out.byteOffset, out.length)
+}
+// index of the applied change with that hash, or undefined
+function indexOfHash(g, hash) {
+  if (engineGraph(g)) {
+    const one = packHashes([hash])
+    if (one) { const i = addon.findChanges(ctx, one)[0]; return i === 0xffffffff ? undefined : i }
+  }
+  return hashIndex(g).get(hash)
+}
 function hashIndex(g) {
   if (!g.byHash) {
     g.byHash = new Map()
@@ -382,7 +414,7 @@ function getChangeByHash(backend, hash) {   // new.js:1999-2002 (applied changes
   isFrozenCheck(backend)
   noteGraphQuery(backend)
   const g = gpuHistory(backend, true)
-  if (g) { const i = hashIndex(g).get(hash); return i === undefined ? undefined : g.changes[i] }
+  if (g) { const i = indexOfHash(g, hash); return i === undefined ? undefined : g.changes[i] }
   return ref().getChangeByHash(hydrate(backend), hash)
 }
 function getMissingDeps(backend, heads = []) {   // new.js:2014-2028
@@ -613,10 +645,15 @@ function ensureContext(g) {
 
 // hash graph of an engine-built state, by index into g.changes: dependencies as resolved on the device, dependents in the order the
 // reference pushes them (new.js:1853-1856: in application order, every change onto the lists of its dependencies)
+// the dependencies alone (what getChangesToSend walks among the changes it may send): no per-state map of dependents
+function depsOf(g) {
+  if (g.graph) return g.graph
+  if (!g.deps) { ensureContext(g); g.deps = addon.depGraph(ctx) }
+  return g.deps
+}
 function graphOf(g) {
   if (!g.graph) {
-    ensureContext(g)
-    const { depFirst, depIndex } = addon.depGraph(ctx)
+    const { depFirst, depIndex } = depsOf(g)
     const applied = new Uint8Array(g.changes.length)
     for (const i of g.applied) applied[i] = 1
     const dependents = new Map()
@@ -636,6 +673,15 @@ function graphOf(g) {
 // BackendDoc.getChanges(haveDeps) (new.js:1921-1976) as a list of indexes, in the order the reference returns the changes
 function changesSince(g, haveDeps) {
   if (haveDeps.length === 0) return Array.from(g.applied)
+  const packed = engineGraph(g) ? packHashes(haveDeps) : null
+  if (packed) {
+    try {
+      return Array.from(addon.changesSince(ctx, packed))
+    } catch (e) {
+      if (e.am355Code === AM355_E_INVALID && e.message.startsWith('hash not found: ')) throw new RangeError(e.message)   // new.js:1934
+      if (e.am355Code !== AM355_E_INVALID && e.am355Code !== AM355_E_UNSUPPORTED) throw e
+    }
+  }
   const idx = hashIndex(g), { depFirst, depIndex, dependents } = graphOf(g)
   let stack = [], seen = new Set(), toReturn = []
   for (const hash of haveDeps) {
@@ -675,6 +721,16 @@ function columnar() {
 // BackendDoc.getMissingDeps(heads) (new.js:2014-2028) with a queue: the dependencies of the queued changes and the given heads that
 // are neither applied nor queued
 function missingDeps(g, heads) {
+  const packed = engineGraph(g) && Array.isArray(heads) ? packHashes(heads) : null
+  if (packed) {
+    try {
+      const raw = addon.missingDeps(ctx, packed), out = []
+      for (let k = 0; k < raw.length; k += 32) out.push(Buffer.from(raw.buffer, raw.byteOffset + k, 32).toString('hex'))
+      return out
+    } catch (e) {
+      if (e.am355Code !== AM355_E_INVALID && e.am355Code !== AM355_E_UNSUPPORTED) throw e
+    }
+  }
   const idx = hashIndex(g), allDeps = new Set(heads), inQueue = new Set()
   for (const i of g.pendingIdx) {
     inQueue.add(hexOfHash(g, i))
@@ -730,7 +786,7 @@ function changesToSendGpu(backend, g, have, need) {
       filters.push({ numEntries, numBitsPerEntry, numProbes, bits: h.bloom.subarray(pos.i, pos.i + n) })
     }
   }
-  const list = changesSince(g, Object.keys(lastSyncHashes)), { depFirst, depIndex } = graphOf(g)
+  const list = changesSince(g, Object.keys(lastSyncHashes)), { depFirst, depIndex } = depsOf(g)
   ensureContext(g)
   const listArr = Uint32Array.from(list)
   const inSome = new Uint8Array(list.length)
@@ -753,9 +809,9 @@ function changesToSendGpu(backend, g, have, need) {
     const i = stack.pop()
     for (const d of dependents.get(i) || []) if (!toSend.has(d)) { toSend.add(d); stack.push(d) }
   }
-  const idx = hashIndex(g), out = []
+  const out = []
   for (const hash of need) {
-    const i = idx.get(hash)
+    const i = indexOfHash(g, hash)
     if (i !== undefined) toSend.add(i)
     if (i === undefined || !inList.has(i)) { const change = getChangeByHash(backend, hash); if (change) out.push(change) }
   }
@@ -816,12 +872,53 @@ const syncModule = () => (JS_ONLY ? ref() : boundSync())
 
 const delegate1 = name => (backend, ...args) => ref()[name](toJs(backend), ...args)
 
+// Backend.getChangesAdded(b1, b2) = BackendDoc(b2).getChangesAdded(BackendDoc(b1)) (backend.js:166-168, new.js:1979-1997; half of
+// Automerge.merge) without a BackendDoc of either: the engine walks b2's graph from its heads (am355_changes_added) and stops at the
+// hashes b1 has applied. Served when b2 is an engine state with a known history and b1 is one too -- or is empty, as Backend.init()
+// makes it: its changeIndexByHash holds nothing. The reference rebuilds the hash graph of b2 (`this`, :1980) and reads b1's index as
+// it is: a b1 that began with a loaded document whose graph the reference has not rebuilt knows only the hashes applied since, which
+// the wrapper does not track -- such a pair, a state whose queue is held back and a reference-made state keep the hydrating path.
+// null: not served.
+function gpuChangesAdded(b1, b2) {
+  if (JS_ONLY) return null
+  const g1 = b1.state instanceof GpuState ? b1.state : null
+  if (b1.frozen || b2.frozen || !(g1 ? !g1.js : isEmptyRefState(b1))) return null
+  if (g1 && g1.doc && !g1.changes && !g1.noHistory && g1.graphKnown) loadedHistory(g1)
+  if (g1 && (heldBack(g1) || !g1.hashes || !g1.applied || ((g1.doc || g1.fromDocument) && !g1.graphKnown))) return null
+  const g2 = gpuHistory(b2, true)
+  if (!g2) return null
+  let other
+  if (!g1) other = new Uint8Array(0)
+  else if (g1.applied.length * 32 === g1.hashes.length) other = g1.hashes   // (everything applied: in any order)
+  else {
+    other = new Uint8Array(32 * g1.applied.length)
+    g1.applied.forEach((i, k) => other.set(g1.hashes.subarray(32 * i, 32 * i + 32), 32 * k))
+  }
+  let idx
+  try {
+    ensureContext(g2)
+    idx = addon.changesAdded(ctx, other)
+  } catch (e) {
+    if (e.am355Code !== AM355_E_INVALID && e.am355Code !== AM355_E_UNSUPPORTED) throw e
+    return null
+  }
+  noteGraphQuery(b2)   // (new.js:1980: `this` is the state of b2)
+  counters.gpuChangesAdded++
+  return Array.from(idx, i => g2.changes[i])
+}
+function getChangesAdded(b1, b2) {
+  const served = gpuChangesAdded(b1, b2)
+  if (served) return served
+  noteGraphQuery(b1)
+  return ref().getChangesAdded(hydrate(b1), hydrate(b2))
+}
+
 module.exports = {
   init, load, loadChanges, getPatch, getHeads, free, save, getAllChanges, getChanges, getChangeByHash, getMissingDeps,
   clone: backend => { noteGraphQuery(backend); return ref().clone(hydrate(backend)) },
   applyChanges,
   applyLocalChange,
-  getChangesAdded: (b1, b2) => { noteGraphQuery(b1); return ref().getChangesAdded(hydrate(b1), hydrate(b2)) },
+  getChangesAdded,
   // sync protocol: the reference's own backend/sync.js bound to this module (boundSync above)
   generateSyncMessage: (...a) => syncModule().generateSyncMessage(...a),
   receiveSyncMessage: (...a) => syncModule().receiveSyncMessage(...a),
@@ -839,6 +936,10 @@ module.exports = {
   _residentNewObjectCalls: () => contexts.reduce((s, e) => { const w = addon.residentNewObjectCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),
   // [calls whose counter increments were written into the stored map records in place, calls where that stage declined], over all contexts
   _residentCounterCalls: () => contexts.reduce((s, e) => { const w = addon.residentCounterCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),
+  // [membership tests of hash-graph queries answered on the device, by the engine's host index], over all contexts; and the switch
+  // between the two (am355_set_graph_probe_min) for every context there is
+  _graphQueryCalls: () => contexts.reduce((s, e) => { const w = addon.graphQueryCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),
+  _setGraphProbeMin: n => { graphProbeMin = n; for (const e of contexts) addon.setGraphProbeMin(e.ctx, n) },
   _applyProfile: profile,
   _hydrate: hydrate   // (tests: the reference handle of an engine state, made the way the state came to be)
 }

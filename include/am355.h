@@ -512,7 +512,50 @@ int am355_arena_epoch(const am355_ctx *ctx, uint64_t *epoch);
 int am355_get_hashes_range(const am355_ctx *ctx, uint32_t first, uint32_t count, uint8_t *out);
 int am355_applied_in_input_order(const am355_ctx *ctx, int *yes);
 
+/*
+ * Hash-graph queries over the changes the context has APPLIED: what BackendDoc answers from changeIndexByHash, dependenciesByHash
+ * and dependentsByHash (new.js:1921-2028), without a BackendDoc. Hashes are 32 raw bytes each. Every index is an index into the
+ * context's list of changes -- the list am355_get_applied indexes --; result arrays are owned by the context and valid until the next
+ * call on it. The context must hold a replayed state of changes: a document context (am355_load_document) and a context without a
+ * replay return AM355_E_STATE, a sharded one AM355_E_UNSUPPORTED, and are left as they were. No call changes the state, the patch
+ * tables or what a following am355_apply_changes is served by. Whether the reference would have had to rebuild a loaded document's
+ * hash graph for the query stays the caller's business (am355_hash_graph_known).
+ *   am355_find_changes   getChangeByHash (new.js:1999-2002): out_idx[k] = the applied change with hash hashes[k], or 0xffffffff.
+ *                        A change that is queued for a missing dependency does not count.
+ *   am355_changes_since  getChanges(haveDeps) (new.js:1921-1976), in the order the reference returns the changes: forward over the
+ *                        dependents of `have`, or -- when that walk meets a change with a dependency it has not seen, or misses a
+ *                        head -- every applied change that is not an ancestor of `have`, in application order. n_have == 0: every
+ *                        applied change in application order. A hash that is not an applied change: AM355_E_INVALID with the
+ *                        text `hash not found: <hex>` (the first such hash of `have`).
+ *   am355_changes_added  BackendDoc(ctx).getChangesAdded(other) (new.js:1979-1997): `other` = the hashes of the changes the other
+ *                        state has applied, in any order; the result is the depth-first order from the heads through the
+ *                        dependencies, stopped at what `other` holds, reversed.
+ *   am355_missing_deps   getMissingDeps(heads) (new.js:2014-2028): the dependencies of the queued changes (read from the staged
+ *                        bytes) and the given heads that are neither applied nor queued, each once, sorted.
+ * The traversals run on the host over indexes. The membership tests -- which of these hashes are applied changes; which changes of
+ * the context are missing from `other` -- are answered by a host index, or, from am355_set_graph_probe_min probes on, on the device:
+ * a table over the context's hashes, which are in device memory already (find_changes, changes_since, missing_deps: one probe per
+ * hash given), or a table over `other` probed with every change of the context, whose answers come back as one bit per change
+ * (changes_added: probes = the context's changes). Both give the same result. The default is 65536 probes: the measured crossover of
+ * changes_added (between 32,000 and 100,000 changes, profiles/hash_graph_timings.txt) rounded up to a power of two; 0xffffffff: never
+ * on the device. am355_graph_query_calls: membership tests answered on the device
+ * (out[0]) and by the host index (out[1]); calls that needed none (empty inputs) count in neither.
+ */
+int am355_find_changes(am355_ctx *ctx, const uint8_t *hashes, uint32_t n, uint32_t *out_idx);
+int am355_changes_since(am355_ctx *ctx, const uint8_t *have, uint32_t n_have, const uint32_t **idx, uint32_t *n);
+int am355_changes_added(am355_ctx *ctx, const uint8_t *other, uint32_t n_other, const uint32_t **idx, uint32_t *n);
+int am355_missing_deps(am355_ctx *ctx, const uint8_t *heads, uint32_t n_heads, const uint8_t **hashes, uint32_t *n);
+int am355_set_graph_probe_min(am355_ctx *ctx, uint32_t n);
+int am355_graph_query_calls(const am355_ctx *ctx, uint64_t out[2]);
+
 /* ---- diagnostics: device primitives exposed for kernel-level tests ---- */
+/* The device hash table of the queries above, driven by itself: a table over table_hashes (n_table x 32 bytes) is built and
+ * queries (n_queries x 32 bytes) are probed, both on the device; out_idx[q] = index of the table hash equal to query q (the smallest,
+ * when table_hashes holds a hash more than once), or 0xffffffff. The table has S = the smallest power of two >= max(64, 2 * n_table + 64)
+ * slots; a hash starts at slot ((little-endian u64 of its first 8 bytes * 0x9e3779b97f4a7c15 mod 2^64) >> 32) & (S - 1) and takes the
+ * first free slot from there on, wrapping behind the last one; a probe walks the same way to the first empty slot and compares all 32
+ * bytes at every slot it passes. n_queries == 0 and n_table == 0 launch nothing. */
+int am355_test_hash_probe(am355_ctx *ctx, const uint8_t *table_hashes, uint32_t n_table, const uint8_t *queries, uint32_t n_queries, uint32_t *out_idx);
 int am355_test_sort(am355_ctx *ctx, uint64_t *keys, uint32_t *vals, uint32_t n, int key_bits);
 int am355_test_scan(am355_ctx *ctx, const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *total);
 /* The primitives one by one (tests/test_primitives.py). Every buffer is an IMAGE: uploaded whole, handed to the primitive at the given
