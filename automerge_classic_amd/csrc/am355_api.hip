@@ -188,6 +188,19 @@ extern "C" int am355_set_resident_counters(am355_ctx* c, int on) {
   return AM355_OK;
 }
 
+extern "C" int am355_set_local_small(am355_ctx* c, int on) {
+  if (!c) return AM355_E_ARG;
+  c->local_small = on != 0;
+  return AM355_OK;
+}
+
+extern "C" int am355_local_small_calls(const am355_ctx* c, uint64_t out[2]) {
+  if (!c || !out) return AM355_E_ARG;
+  out[0] = c->n_local_small;
+  out[1] = c->n_local_small_bulk;
+  return AM355_OK;
+}
+
 extern "C" int am355_resident_counter_calls(const am355_ctx* c, uint64_t out[2]) {
   if (!c || !out) return AM355_E_ARG;
   out[0] = c->n_counter_calls;

@@ -529,29 +529,91 @@ static int local_validate(am355_ctx* c, const am355_local_change* lc, LocalPlan&
   return AM355_OK;
 }
 
+typedef std::function<void(const char*)> LocalLap;
+
+// The twelve columns of an uploaded request by the bulk path: expand + twelve encodes on the device, the columns copied back into
+// c->h_local_out, where `parts` points afterwards.
+static int local_columns_bulk(am355_ctx* c, const LocalBufs& L, HistBufs& hb, ChangeParts& parts, const LocalLap& lap) {
+  hipStream_t st = c->stream;
+  local_expand_encode(L, hb, st);
+  size_t col_total_cap = 0;
+  for (int k = 0; k < HIST_NCOL; k++) col_total_cap += hb.col_cap[k] + 256;
+  if (!c->h_local_out.ensure(256 + col_total_cap)) return fail(c, AM355_E_NOMEM, "host allocation failed (local change)");
+  uint32_t* d_flags = c->h_local_out.as<uint32_t>();
+  uint32_t* d_col_len = d_flags + 4;
+  uint8_t* d_cols = c->h_local_out.as<uint8_t>() + 256;
+  HIPCHK(c, hipMemcpyAsync(d_flags, hb.flags, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(d_col_len, hb.col_len, 4 * HIST_NCOL, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  lap("expand + encodes (device)");
+  if (d_flags[0]) return fail(c, AM355_E_DEVICE, "internal: the request's values do not fit the arena sized for them");
+  uint8_t* q = d_cols;
+  for (int k = 0; k < HIST_NCOL; k++) {
+    if (d_col_len[k] > hb.col_cap[k]) return fail(c, AM355_E_DEVICE, "internal: encoded column larger than its bound");
+    parts.col[k] = q; parts.col_len[k] = d_col_len[k];
+    if (d_col_len[k]) HIPCHK(c, hipMemcpyAsync(q, hb.col_out[k], d_col_len[k], hipMemcpyDeviceToHost, st));
+    q += ((size_t)d_col_len[k] + 255) & ~(size_t)255;
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  lap("columns on the host");
+  return AM355_OK;
+}
+
+// The same by ONE workgroup (am355_hist.hip kl_small), for a request inside local_small_fits: one launch behind the upload and one
+// wait; the kernel itself puts columns, lengths and flag word into c->h_local_small.
+static int local_columns_small(am355_ctx* c, const LocalBufs& L, ChangeParts& parts, const LocalLap& lap) {
+  hipStream_t st = c->stream;
+  uint8_t* out = c->h_local_small.as<uint8_t>();
+  local_small_encode(L, out, st);
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  lap("one workgroup (device)");
+  const uint32_t* words = (const uint32_t*)out;
+  if (words[0]) return fail(c, AM355_E_DEVICE, "internal: the small local change does not fit the workgroup's carve");
+  size_t at = LOCAL_SMALL_HEAD;
+  for (int k = 0; k < HIST_NCOL; k++) {
+    parts.col[k] = out + at; parts.col_len[k] = words[4 + k];
+    at += words[4 + k];
+    if (at > local_small_host_bytes()) return fail(c, AM355_E_DEVICE, "internal: encoded columns larger than their bound");
+  }
+  return AM355_OK;
+}
+
 // encodeChange of a validated request with the dependencies given (sorted by the caller): the uncompressed container into
-// c->local_plain, its hash into `hash`. Upload, expand + twelve encodes on the device, columns back, header + SHA-256 on the host.
+// c->local_plain, its hash into `hash`. Upload, the twelve columns built on the device (by one workgroup when am355_set_local_small is
+// on and the request lies inside its limits, else by expand + twelve bulk encodes), header + SHA-256 on the host.
 static int local_encode(am355_ctx* c, const am355_local_change* lc, const LocalPlan& pl, const std::vector<uint8_t>& deps, uint8_t hash[32]) {
   (void)hipSetDevice(c->device);
   const bool trace = getenv("AM355_TRACE") != nullptr;
   auto t0 = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
+  const LocalLap lap = [&](const char* what) {
     if (!trace) return;
     auto now = std::chrono::steady_clock::now();
     fprintf(stderr, "local change: %-22s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t0).count());
     t0 = now;
   };
-  hipStream_t st = c->stream;
   const uint32_t M = pl.rows, P = pl.pred_rows, NA = lc->n_actors;
+  // which path, before anything is enqueued: from the plan and the request's counts alone
+  bool small = false, verify = false;
+  if (c->local_small) {
+    uint64_t key_val_bytes = pl.val_cap;
+    for (uint32_t i = 0; i < lc->n_ops; i++)
+      if (lc->ops[i].key_kind == AM355_LK_STRING) key_val_bytes += (uint64_t)lc->ops[i].key_len * lc->ops[i].multi;
+    small = local_small_fits(lc->n_ops, M, P, key_val_bytes);
+    if (small && !c->h_local_small.ensure(local_small_host_bytes())) return fail(c, AM355_E_NOMEM, "host allocation failed (local change)");
+    if (small) { const char* e = getenv("AM355_LOCAL_SMALL_VERIFY"); verify = e && *e && *e != '0'; }   // (tests; read per call)
+  }
+  const bool bulk = !small || verify;
   const size_t lbytes = local_bytes(lc->n_ops, lc->n_values, lc->n_preds, NA, M, lc->strings_len, pl.val_cap);
   const size_t hbytes = hist_bytes(M, P, 1, NA, 0, pl.key_bytes, pl.val_cap);
-  if (!c->d_local.ensure(lbytes) || !c->d_local_hist.ensure(hbytes)) return fail(c, AM355_E_NOMEM, "device allocation failed (local change)");
+  if (!c->d_local.ensure(lbytes) || (bulk && !c->d_local_hist.ensure(hbytes))) return fail(c, AM355_E_NOMEM, "device allocation failed (local change)");
   LocalBufs L, U;
   local_bind(L, c->d_local.p, lc->n_ops, lc->n_values, lc->n_preds, NA, M, P, lc->strings_len, pl.val_cap, (uint32_t)lc->start_op);
   if (!c->h_local.ensure(L.up_bytes + 256)) return fail(c, AM355_E_NOMEM, "host allocation failed (local change)");
   local_bind(U, c->h_local.p, lc->n_ops, lc->n_values, lc->n_preds, NA, M, P, lc->strings_len, pl.val_cap, (uint32_t)lc->start_op);
   HistBufs hb;
-  hist_bind(hb, c->d_local_hist.p, M, P, 1, NA, 0, pl.key_bytes, pl.val_cap);
+  if (bulk) hist_bind(hb, c->d_local_hist.p, M, P, 1, NA, 0, pl.key_bytes, pl.val_cap);
   canary_arm();
   // the request's arrays, as they are, into the pinned block; rows / pred entries per op for the device's scans
   if (lc->n_ops) memcpy(U.ops, lc->ops, sizeof(am355_local_op) * (size_t)lc->n_ops);
@@ -570,31 +632,26 @@ static int local_encode(am355_ctx* c, const am355_local_change* lc, const LocalP
   if (!rc) rc = flush_uploads(c);
   if (rc) return rc;
   lap("request staged");
-  local_expand_encode(L, hb, st);
-  size_t col_total_cap = 0;
-  for (int k = 0; k < HIST_NCOL; k++) col_total_cap += hb.col_cap[k] + 256;
-  if (!c->h_local_out.ensure(256 + col_total_cap)) return fail(c, AM355_E_NOMEM, "host allocation failed (local change)");
-  uint32_t* d_flags = c->h_local_out.as<uint32_t>();
-  uint32_t* d_col_len = d_flags + 4;
-  uint8_t* d_cols = c->h_local_out.as<uint8_t>() + 256;
-  HIPCHK(c, hipMemcpyAsync(d_flags, hb.flags, 16, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(d_col_len, hb.col_len, 4 * HIST_NCOL, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  HIPCHK(c, hipGetLastError());
-  lap("expand + encodes (device)");
-  if (d_flags[0]) return fail(c, AM355_E_DEVICE, "internal: the request's values do not fit the arena sized for them");
   ChangeParts parts;
-  {
-    uint8_t* q = d_cols;
-    for (int k = 0; k < HIST_NCOL; k++) {
-      if (d_col_len[k] > hb.col_cap[k]) return fail(c, AM355_E_DEVICE, "internal: encoded column larger than its bound");
-      parts.col[k] = q; parts.col_len[k] = d_col_len[k];
-      if (d_col_len[k]) HIPCHK(c, hipMemcpyAsync(q, hb.col_out[k], d_col_len[k], hipMemcpyDeviceToHost, st));
-      q += ((size_t)d_col_len[k] + 255) & ~(size_t)255;
+  if (small) {
+    rc = local_columns_small(c, L, parts, lap);
+    if (rc) return rc;
+    c->n_local_small++;
+    if (verify) {   // the same request by the bulk path: the twelve lengths and the column bytes must be the same
+      static const char* const col_name[HIST_NCOL] = {"objActor", "objCtr", "keyActor", "keyCtr", "keyStr", "insert", "action", "valLen", "valRaw", "predNum", "predActor", "predCtr"};
+      ChangeParts ref;
+      rc = local_columns_bulk(c, L, hb, ref, [](const char*) {});
+      if (rc) return rc;
+      for (int k = 0; k < HIST_NCOL; k++)
+        if (parts.col_len[k] != ref.col_len[k] || (ref.col_len[k] && memcmp(parts.col[k], ref.col[k], ref.col_len[k]) != 0))
+          return fail(c, AM355_E_DEVICE, "AM355_LOCAL_SMALL_VERIFY: column %d (%s) of the small path differs from the bulk path (%u against %u bytes)", k, col_name[k],
+                      (unsigned)parts.col_len[k], (unsigned)ref.col_len[k]);
     }
-    HIPCHK(c, hipStreamSynchronize(st));
+  } else {
+    if (c->local_small) c->n_local_small_bulk++;
+    rc = local_columns_bulk(c, L, hb, parts, lap);
+    if (rc) return rc;
   }
-  lap("columns on the host");
   parts.author = lc->actor_bytes + lc->actor_off[0]; parts.author_len = lc->actor_off[1] - lc->actor_off[0];
   parts.seq = lc->seq; parts.start_op = lc->start_op; parts.time = lc->time;
   parts.message = lc->message; parts.message_len = lc->message_len;

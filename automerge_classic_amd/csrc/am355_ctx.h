@@ -551,6 +551,11 @@ struct am355_ctx {
   std::vector<uint8_t> local_plain, local_out;     // the change as an uncompressed container | as encodeChange returns it
   std::vector<uint8_t> local_heads;                // `deps` of the patch of a local change: the heads without the change's own hash
   uint64_t n_local_served = 0, n_local_refused = 0;
+  // am355_set_local_small: a request inside the limits of am355_hist.h LOCAL_SMALL_* is built by ONE workgroup (kl_small), which writes
+  // the columns, their lengths and its flag word straight into h_local_small (sized once from the limits' worst case)
+  bool local_small = false;
+  HostBuf h_local_small;
+  uint64_t n_local_small = 0, n_local_small_bulk = 0;   // changes built by kl_small | requests that found the switch on, lay outside the limits and took the bulk path
   DevBuf d_map_alt, d_mapmerge;                    // the other map table | the stage's scratch
   am355_ir_map* map_alt_ptr = nullptr;             // whichever of the two map tables c->ir.map does NOT point to (null: not set up since the last carve)
   std::string resident_why;                        // why the last attempt fell back (diagnostics, AM355_TRACE)

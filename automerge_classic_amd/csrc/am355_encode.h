@@ -14,6 +14,32 @@ void enc_carve(EncWork& w, void* base, uint32_t n);
 // upper bound of the encoded size of an n-value numeric column (10 bytes per value covers a header and a 5-byte value each)
 inline size_t enc_numbers_bound(uint32_t n) { return 10 * (size_t)n + 16; }
 
+// LEB128 sizes and writers (encoding.js:389-458), shared by the bulk encoders (am355_encode.hip) and the one-workgroup encoder of a small
+// local change (am355_hist.hip kl_small)
+__device__ __forceinline__ uint32_t uleb_size(uint64_t v) {
+  uint32_t n = 1;
+  while (v >= 0x80) { v >>= 7; n++; }
+  return n;
+}
+__device__ __forceinline__ uint32_t sleb_size(int64_t v) {
+  uint32_t n = 1;
+  while (!((v >= -64) && (v < 64))) { v >>= 7; n++; }
+  return n;
+}
+__device__ __forceinline__ uint8_t* put_uleb(uint8_t* p, uint64_t v) {
+  while (v >= 0x80) { *p++ = (uint8_t)(v | 0x80); v >>= 7; }
+  *p++ = (uint8_t)v;
+  return p;
+}
+__device__ __forceinline__ uint8_t* put_sleb(uint8_t* p, int64_t v) {
+  for (;;) {
+    uint8_t b = (uint8_t)(v & 0x7f);
+    v >>= 7;  // arithmetic
+    if ((v == 0 && !(b & 0x40)) || (v == -1 && (b & 0x40))) { *p++ = b; return p; }
+    *p++ = b | 0x80;
+  }
+}
+
 // RLE of nullable numbers (encoding.js:558-783). nullmask == nullptr: NONE32 is null. is_signed: values are int32 written
 // as signed LEB128 (the delta columns), else unsigned LEB128. *d_len (device) receives the byte count.
 // `seg` (every encoder; null = the column is one segment): seg[i] = index of the first value of the segment of value i. The columns

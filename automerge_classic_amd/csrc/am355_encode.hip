@@ -24,30 +24,6 @@ void enc_carve(EncWork& w, void* base, uint32_t n) {
   w.scan_ws = take(scan_workspace_bytes(n + 2));
 }
 
-__device__ __forceinline__ uint32_t uleb_size(uint64_t v) {
-  uint32_t n = 1;
-  while (v >= 0x80) { v >>= 7; n++; }
-  return n;
-}
-__device__ __forceinline__ uint32_t sleb_size(int64_t v) {
-  uint32_t n = 1;
-  while (!((v >= -64) && (v < 64))) { v >>= 7; n++; }
-  return n;
-}
-__device__ __forceinline__ uint8_t* put_uleb(uint8_t* p, uint64_t v) {
-  while (v >= 0x80) { *p++ = (uint8_t)(v | 0x80); v >>= 7; }
-  *p++ = (uint8_t)v;
-  return p;
-}
-__device__ __forceinline__ uint8_t* put_sleb(uint8_t* p, int64_t v) {
-  for (;;) {
-    uint8_t b = (uint8_t)(v & 0x7f);
-    v >>= 7;  // arithmetic
-    if ((v == 0 && !(b & 0x40)) || (v == -1 && (b & 0x40))) { *p++ = b; return p; }
-    *p++ = b | 0x80;
-  }
-}
-
 // value sources -------------------------------------------------------------------------------------------------
 // `seg` (all sources; may be null = one segment): seg[i] = index of the first value of the segment value i belongs to. The history
 // reconstruction (am355_hist.hip) encodes the columns of ALL changes of a document in one go: a segment is one change, and what

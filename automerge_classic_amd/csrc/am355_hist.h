@@ -78,4 +78,24 @@ void local_bind(LocalBufs& L, void* block, uint32_t n_ops, uint32_t n_values, ui
 // scans, kl_expand, kl_values, the twelve encodes (enqueued on st). Afterwards h.flags / h.col_len / h.col_out are complete.
 void local_expand_encode(const LocalBufs& L, HistBufs& h, hipStream_t st);
 
+// A SMALL local change (am355_set_local_small): ONE workgroup does all of the above in LDS -- the scans, the expansion, the value bytes,
+// the twelve encodes -- and writes the columns, their lengths and the flag word straight into pinned host memory (kl_small). The limits
+// are what its LDS carve holds; a request inside all four is built that way, every other one by local_expand_encode.
+constexpr uint32_t LOCAL_SMALL_ROWS = 512;     // rows of the expanded change
+constexpr uint32_t LOCAL_SMALL_PREDS = 512;    // pred entries of the expanded change
+constexpr uint32_t LOCAL_SMALL_OPS = 256;      // ops of the request
+constexpr uint32_t LOCAL_SMALL_BYTES = 4096;   // key bytes (once per row) + value bytes (8 per number, a string's length)
+// worst case of the twelve columns together: nine numeric columns and the boolean one by enc_numbers_bound (seven and the boolean over
+// rows, two over pred entries), keyStr = a numeric column + the key bytes, valRaw = the value bytes
+constexpr size_t LOCAL_SMALL_OUT_BYTES = 9 * (10 * (size_t)LOCAL_SMALL_ROWS + 16) + 2 * (10 * (size_t)LOCAL_SMALL_PREDS + 16) + 2 * ((size_t)LOCAL_SMALL_BYTES + 16);
+constexpr size_t LOCAL_SMALL_HEAD = 256;       // in front of the column bytes: flags[4] | col_len[HIST_NCOL]
+inline size_t local_small_host_bytes() { return LOCAL_SMALL_HEAD + LOCAL_SMALL_OUT_BYTES; }
+inline bool local_small_fits(uint32_t n_ops, uint64_t rows, uint64_t pred_rows, uint64_t key_val_bytes) {
+  return n_ops <= LOCAL_SMALL_OPS && rows <= LOCAL_SMALL_ROWS && pred_rows <= LOCAL_SMALL_PREDS && key_val_bytes <= LOCAL_SMALL_BYTES;
+}
+// One launch on st. `L`: the device block the request was uploaded into (only its uploaded members are read). `host_out`: pinned,
+// local_small_host_bytes(): flags[0] != 0 when the kernel refused (a count beyond its carve); else col_len and the columns back to back
+// from LOCAL_SMALL_HEAD on, in id order.
+void local_small_encode(const LocalBufs& L, uint8_t* host_out, hipStream_t st);
+
 }  // namespace am355

@@ -21,6 +21,7 @@
 // 2 GB/s for a host core with SHA extensions; the chain stays on the host threads.
 #include "am355_hist.h"
 #include "am355_prims.h"
+#include "am355_scan.h"
 
 namespace am355 {
 
@@ -476,70 +477,67 @@ __device__ __forceinline__ uint32_t local_value_len(const am355_local_value& v) 
   }
 }
 
-// One thread per ROW of the expanded change (columnar.js:446-475): the request op that owns the row by binary search over the scan of
-// `multi`, then the row's fields as encodeOps appends them (:397-428). Row `rows` (one past the end) closes the value-length array.
-__global__ __launch_bounds__(BLOCK) void kl_expand(LocalBufs L, HistBufs h) {
-  const uint32_t row = gtid();
-  if (row > L.rows) return;
-  if (row == L.rows) { L.vlen[row] = 0; L.vidx[row] = NONE32; return; }
+// One ROW of the expanded change (columnar.js:446-475): the request op that owns the row by binary search over the scan of `multi`
+// (row_base), then the row's fields as encodeOps appends them (:397-428). Shared by kl_expand and kl_small.
+struct LocalRow {
+  uint32_t obj_actor, obj_ctr, key_actor, key_ctr, key_off, key_len, insert, action;
+  uint32_t vidx, vlen, val_tl;     // value record of the row (NONE32: none) | its bytes in valRaw | length << 4 | tag
+  uint32_t pred_at, pred_num;      // the row's entries in the pred columns
+  uint32_t k;                      // the row's place inside its op
+  bool multi_del;
+};
+__device__ __forceinline__ LocalRow local_expand_row(const LocalBufs& L, const uint32_t* row_base, const uint32_t* pred_base, uint32_t row, am355_local_op& op) {
   uint32_t lo = 0, hi = L.n_ops;   // the last op whose first row is <= row (ops without rows share their successor's first row)
   while (lo + 1 < hi) {
     const uint32_t mid = (lo + hi) >> 1;
-    if (L.row_base[mid] <= row) lo = mid; else hi = mid;
+    if (row_base[mid] <= row) lo = mid; else hi = mid;
   }
-  const am355_local_op op = L.ops[lo];
-  const uint32_t k = row - L.row_base[lo];
+  op = L.ops[lo];
+  LocalRow r;
+  r.k = row - row_base[lo];
   const bool multi_ins = op.action == 1 && (op.flags & AM355_LOP_VALUES) && (op.flags & AM355_LOP_INSERT);
-  const bool multi_del = op.action == 3 && op.multi > 1;
-  uint32_t ka = NONE32, kc = NONE32, koff = 0, klen = NONE32;
-  if (op.key_kind == AM355_LK_STRING) { koff = op.key_off; klen = op.key_len; }
-  else if (op.key_kind == AM355_LK_HEAD) kc = 0;
-  else { ka = op.elem_actor; kc = op.elem_ctr; }
-  if (multi_ins && k > 0) { ka = 0; kc = L.start_op + row - 1; }   // behind the value in front of it: the id of the row before (:457)
-  if (multi_del) kc += k;                                           // (:464)
-  h.v_obj_actor[row] = op.obj_actor;
-  h.v_obj_ctr[row] = op.obj_actor == NONE32 ? NONE32 : op.obj_ctr;
-  h.v_key_actor[row] = ka; h.v_key_ctr[row] = kc; h.v_key_off[row] = koff; h.v_key_len[row] = klen;
-  h.v_insert[row] = (op.flags & AM355_LOP_INSERT) ? 1 : 0;
-  h.v_action[row] = op.action;
-  uint32_t vi = NONE32, len = 0, tl = 0;
+  r.multi_del = op.action == 3 && op.multi > 1;
+  r.key_actor = NONE32; r.key_ctr = NONE32; r.key_off = 0; r.key_len = NONE32;
+  if (op.key_kind == AM355_LK_STRING) { r.key_off = op.key_off; r.key_len = op.key_len; }
+  else if (op.key_kind == AM355_LK_HEAD) r.key_ctr = 0;
+  else { r.key_actor = op.elem_actor; r.key_ctr = op.elem_ctr; }
+  if (multi_ins && r.k > 0) { r.key_actor = 0; r.key_ctr = L.start_op + row - 1; }   // behind the value in front of it: the id of the row before (:457)
+  if (r.multi_del) r.key_ctr += r.k;                                                  // (:464)
+  r.obj_actor = op.obj_actor;
+  r.obj_ctr = op.obj_actor == NONE32 ? NONE32 : op.obj_ctr;
+  r.insert = (op.flags & AM355_LOP_INSERT) ? 1 : 0;
+  r.action = op.action;
+  r.vidx = NONE32; r.vlen = 0; r.val_tl = 0;
   if (op.action == 1 || op.action == 5) {
-    vi = op.val_first + (multi_ins ? k : 0);
-    const am355_local_value v = L.values[vi];
-    len = local_value_len(v);
-    tl = len << 4 | v.tag;
+    r.vidx = op.val_first + (multi_ins ? r.k : 0);
+    const am355_local_value v = L.values[r.vidx];
+    r.vlen = local_value_len(v);
+    r.val_tl = r.vlen << 4 | v.tag;
   }
-  h.v_val_tl[row] = tl;
-  h.v_val_off[row] = 0;   // (kl_values, once the lengths are scanned)
-  L.vidx[row] = vi; L.vlen[row] = len;
-  // preds in (counter, actor id) order: compareParsedOpIds compares the id STRINGS, so by the table's ranks, not by local number
-  const uint32_t pb = L.pred_base[lo] + (multi_del ? k : 0), pn = multi_ins ? 0u : multi_del ? 1u : op.pred_num;
-  h.v_pred_num[row] = pn;
-  if (multi_del) { h.p_actor[pb] = L.preds[op.pred_first].actor; h.p_ctr[pb] = L.preds[op.pred_first].ctr + k; return; }   // (:465)
-  for (uint32_t i = 0; i < pn; i++) {
+  r.pred_at = pred_base[lo] + (r.multi_del ? r.k : 0);
+  r.pred_num = multi_ins ? 0u : r.multi_del ? 1u : op.pred_num;
+  return r;
+}
+
+// The row's pred entries into p_actor / p_ctr[0 .. r.pred_num), in (counter, actor id) order: compareParsedOpIds compares the id
+// STRINGS, so by the table's ranks, not by local number (:394-396, :423; a multiOp deletion: its one pred counted up, :465)
+__device__ __forceinline__ void local_row_preds(const LocalBufs& L, const am355_local_op& op, const LocalRow& r, uint32_t* p_actor, uint32_t* p_ctr) {
+  if (r.multi_del) { p_actor[0] = L.preds[op.pred_first].actor; p_ctr[0] = L.preds[op.pred_first].ctr + r.k; return; }
+  for (uint32_t i = 0; i < r.pred_num; i++) {
     const am355_local_pred pr = L.preds[op.pred_first + i];
     const unsigned long long key = (unsigned long long)pr.ctr << 32 | L.rank[pr.actor];
     uint32_t j = i;
     for (; j > 0; j--) {
-      const uint32_t qa = h.p_actor[pb + j - 1], qc = h.p_ctr[pb + j - 1];
+      const uint32_t qa = p_actor[j - 1], qc = p_ctr[j - 1];
       if (((unsigned long long)qc << 32 | L.rank[qa]) <= key) break;
-      h.p_actor[pb + j] = qa; h.p_ctr[pb + j] = qc;
+      p_actor[j] = qa; p_ctr[j] = qc;
     }
-    h.p_actor[pb + j] = pr.actor; h.p_ctr[pb + j] = pr.ctr;
+    p_actor[j] = pr.actor; p_ctr[j] = pr.ctr;
   }
 }
 
-// One thread per row: the value's bytes into the value arena at the scanned offset
-__global__ __launch_bounds__(BLOCK) void kl_values(LocalBufs L, HistBufs h) {
-  const uint32_t row = gtid();
-  if (row >= L.rows) return;
-  const uint32_t len = L.vlen[row], vi = L.vidx[row];
-  if (!len || vi == NONE32) return;
-  const uint32_t at = L.voff[row];
-  if ((unsigned long long)at + len > L.val_cap) { atomicOr(&h.flags[0], (uint32_t)HF_INVALID); return; }   // (the host sized the arena from the same values)
-  const am355_local_value v = L.values[vi];
-  uint8_t* out = L.arena + L.str_len + at;
-  h.v_val_off[row] = L.str_len + at;
+// the `len` bytes of a value as valRaw holds them (columnar.js:259-292)
+__device__ __forceinline__ void local_value_write(const LocalBufs& L, const am355_local_value& v, uint32_t len, uint8_t* out) {
   if (v.tag == AM355_LV_UTF8) {
     const uint8_t* src = L.arena + v.off;
     for (uint32_t i = 0; i < len; i++) out[i] = src[i];
@@ -552,6 +550,36 @@ __global__ __launch_bounds__(BLOCK) void kl_values(LocalBufs L, HistBufs h) {
     long long x = (long long)v.payload;
     for (uint32_t i = 0; i < len; i++) { out[i] = (uint8_t)((x & 0x7f) | (i + 1 < len ? 0x80 : 0)); x >>= 7; }
   }
+}
+
+// One thread per ROW of the expanded change. Row `rows` (one past the end) closes the value-length array.
+__global__ __launch_bounds__(BLOCK) void kl_expand(LocalBufs L, HistBufs h) {
+  const uint32_t row = gtid();
+  if (row > L.rows) return;
+  if (row == L.rows) { L.vlen[row] = 0; L.vidx[row] = NONE32; return; }
+  am355_local_op op;
+  const LocalRow r = local_expand_row(L, L.row_base, L.pred_base, row, op);
+  h.v_obj_actor[row] = r.obj_actor; h.v_obj_ctr[row] = r.obj_ctr;
+  h.v_key_actor[row] = r.key_actor; h.v_key_ctr[row] = r.key_ctr; h.v_key_off[row] = r.key_off; h.v_key_len[row] = r.key_len;
+  h.v_insert[row] = (uint8_t)r.insert;
+  h.v_action[row] = r.action;
+  h.v_val_tl[row] = r.val_tl;
+  h.v_val_off[row] = 0;   // (kl_values, once the lengths are scanned)
+  L.vidx[row] = r.vidx; L.vlen[row] = r.vlen;
+  h.v_pred_num[row] = r.pred_num;
+  local_row_preds(L, op, r, h.p_actor + r.pred_at, h.p_ctr + r.pred_at);
+}
+
+// One thread per row: the value's bytes into the value arena at the scanned offset
+__global__ __launch_bounds__(BLOCK) void kl_values(LocalBufs L, HistBufs h) {
+  const uint32_t row = gtid();
+  if (row >= L.rows) return;
+  const uint32_t len = L.vlen[row], vi = L.vidx[row];
+  if (!len || vi == NONE32) return;
+  const uint32_t at = L.voff[row];
+  if ((unsigned long long)at + len > L.val_cap) { atomicOr(&h.flags[0], (uint32_t)HF_INVALID); return; }   // (the host sized the arena from the same values)
+  h.v_val_off[row] = L.str_len + at;
+  local_value_write(L, L.values[vi], len, L.arena + L.str_len + at);
 }
 
 void local_expand_encode(const LocalBufs& L, HistBufs& h, hipStream_t st) {
@@ -567,6 +595,279 @@ void local_expand_encode(const LocalBufs& L, HistBufs& h, hipStream_t st) {
   AM355_LAUNCH_INDEPENDENT(kl_values, grid_for(M), dim3(BLOCK), st, L, h);
   h.P = L.pred_rows;
   hist_encode_columns(L.arena, h, M, st, [](int, bool, bool, uint32_t) {});
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// a SMALL local change in one workgroup (am355_set_local_small; am355_hist.h LOCAL_SMALL_*)
+// ---------------------------------------------------------------------------------------------------------
+// The bulk path above is ~115 stream commands for a typed character: launch gaps over a handful of values. Here ONE workgroup of twelve
+// wavefronts does the whole build: the two scans, the expansion (one row per thread, local_expand_row), then ONE WAVEFRONT PER COLUMN.
+// The twelve columns are independent of each other, so no column waits for another; a wavefront walks its column 64 values at a time.
+// What the reference's encoder state machine emits is a function of the value sequence alone (am355_encode.hip), and every piece of it
+// follows from three bit masks of the column, which a ballot per 64 values gives: which values are non-null, which start a run, and
+// from the two which are LONE (a run of one non-null value):
+//   a run starts where the value differs from the one before; its length = distance to the next start bit;
+//   a null run is (0, n); a run of >= 2 equal values (n, v); a maximal stretch of lone values ONE literal (-k, v1..vk), whose count k =
+//   distance to the next clear bit of the lone mask -- no look-ahead state is carried, the masks of the whole column sit in LDS;
+//   delta columns: the value in front of a non-null value = the next lower bit of the non-null mask.
+// Sizes are scanned per wavefront (six __shfl_up steps per 64 values, the carry by lane broadcast), the twelve lengths by one thread, and
+// every run writes its bytes into the column's stretch of ONE LDS byte arena, columns back to back. The arena, the twelve lengths and
+// the flag word then go to pinned host memory as plain dword stores. Each size / write rule is stated once: ls_run<false> counts,
+// ls_run<true> writes.
+constexpr uint32_t LS_THREADS = HIST_NCOL * WAVE;   // 768: a wavefront per column; >= LOCAL_SMALL_ROWS and > LOCAL_SMALL_OPS: a thread per row / per op
+constexpr uint32_t LS_MAXN = LOCAL_SMALL_ROWS > LOCAL_SMALL_PREDS ? LOCAL_SMALL_ROWS : LOCAL_SMALL_PREDS;
+constexpr uint32_t LS_WORDS = LS_MAXN / 64 + 1;     // 64-bit words of a column's masks: a bit per value and the closing bit at n
+static_assert(LOCAL_SMALL_ROWS <= LS_THREADS && LOCAL_SMALL_OPS + 1 <= LS_THREADS, "a thread per row and per op");
+static_assert(LOCAL_SMALL_OUT_BYTES % 4 == 0 && LOCAL_SMALL_HEAD >= 4 * (4 + HIST_NCOL), "pinned layout of kl_small");
+enum : uint32_t { LS_V_KEY_OFF = 4, LS_V_KEY_LEN = 5, LS_V_VIDX = 8 };   // s.v[k]: column k's values, except: 4 / 5 the key's range, 8 the value record
+enum : uint32_t { LS_NUM = 0, LS_DELTA = 1, LS_STR = 2, LS_BOOL = 3, LS_RAW = 4 };
+
+struct LsLds {
+  alignas(16) uint8_t out[LOCAL_SMALL_OUT_BYTES];     // the twelve columns back to back
+  uint32_t v[10][LOCAL_SMALL_ROWS];                    // by row
+  uint32_t p[2][LOCAL_SMALL_PREDS];                    // by pred entry: actor | counter
+  uint32_t d[2][LS_MAXN];                              // deltas of keyCtr | of predCtr
+  uint32_t off[HIST_NCOL][LS_MAXN];                    // byte offset of the run that starts at value i, inside its column
+  unsigned long long nn[HIST_NCOL][LS_WORDS], start[HIST_NCOL][LS_WORDS];
+  uint32_t row_base[LOCAL_SMALL_OPS + 1], pred_base[LOCAL_SMALL_OPS + 1];
+  uint32_t wtot[LS_THREADS / WAVE], col_len[HIST_NCOL], col_base[HIST_NCOL + 1], flag;
+  uint8_t ins[LOCAL_SMALL_ROWS];
+};
+static_assert(sizeof(LsLds) <= 132 * 1024, "LDS of kl_small: the 160 KB of a gfx950 workgroup with room to spare");
+
+// exclusive prefix of v over the LS_THREADS threads; *total = their sum. Every thread must call it.
+__device__ __forceinline__ uint32_t ls_block_scan(uint32_t v, uint32_t* wtot, uint32_t* total) {
+  const uint32_t lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+  const uint32_t incl = wave_incl_scan_u32(v, lane);
+  if (lane == WAVE - 1) wtot[w] = incl;
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+  for (uint32_t k = 0; k < LS_THREADS / WAVE; k++) {
+    const uint32_t x = wtot[k];
+    before += k < w ? x : 0;
+    all += x;
+  }
+  __syncthreads();
+  *total = all;
+  return before + incl - v;
+}
+
+// ---- the masks of one column: nw words are written; bit n (the closing start bit) lies inside them ----
+__device__ __forceinline__ bool ls_bit(const unsigned long long* m, uint32_t i) { return (m[i >> 6] >> (i & 63)) & 1; }
+// first set bit at or behind `from` (the closing bit ends the search)
+__device__ __forceinline__ uint32_t ls_next_set(const unsigned long long* m, uint32_t nw, uint32_t from) {
+  uint32_t k = from >> 6;
+  unsigned long long w = m[k] & (~0ull << (from & 63));
+  while (!w) {
+    if (++k >= nw) return nw * 64;
+    w = m[k];
+  }
+  return k * 64 + (uint32_t)__ffsll(w) - 1;
+}
+// last set bit in front of i (NONE32: none)
+__device__ __forceinline__ uint32_t ls_prev_set(const unsigned long long* m, uint32_t i) {
+  uint32_t k = i >> 6;
+  unsigned long long w = (i & 63) ? m[k] & ((1ull << (i & 63)) - 1) : 0ull;
+  while (!w) {
+    if (k == 0) return NONE32;
+    w = m[--k];
+  }
+  return k * 64 + 63 - (uint32_t)__clzll(w);
+}
+// lone values: a run starts here, the next starts right behind, and the value is not null
+__device__ __forceinline__ unsigned long long ls_lone_word(const unsigned long long* start, const unsigned long long* nn, uint32_t nw, uint32_t k) {
+  const unsigned long long behind = (start[k] >> 1) | ((k + 1 < nw ? start[k + 1] : 0ull) << 63);
+  return start[k] & nn[k] & behind;
+}
+__device__ __forceinline__ bool ls_lone(const unsigned long long* start, const unsigned long long* nn, uint32_t nw, uint32_t i) {
+  return (ls_lone_word(start, nn, nw, i >> 6) >> (i & 63)) & 1;
+}
+// first value at or behind i that is not lone (the closing position n is not)
+__device__ __forceinline__ uint32_t ls_next_not_lone(const unsigned long long* start, const unsigned long long* nn, uint32_t nw, uint32_t i) {
+  uint32_t k = i >> 6;
+  unsigned long long w = ~ls_lone_word(start, nn, nw, k) & (~0ull << (i & 63));
+  while (!w) {
+    if (++k >= nw) return nw * 64;
+    w = ~ls_lone_word(start, nn, nw, k);
+  }
+  return k * 64 + (uint32_t)__ffsll(w) - 1;
+}
+
+// counting (W = false) or writing (W = true) emitters: both return the bytes
+template <bool W> __device__ __forceinline__ uint32_t ls_uleb(uint8_t*& p, uint64_t v) {
+  const uint32_t n = uleb_size(v);
+  if (W) p = put_uleb(p, v);
+  return n;
+}
+template <bool W> __device__ __forceinline__ uint32_t ls_sleb(uint8_t*& p, int64_t v) {
+  const uint32_t n = sleb_size(v);
+  if (W) p = put_sleb(p, v);
+  return n;
+}
+
+// one column as its wavefront sees it. nul: NONE32 there = the value is null (nullptr: never null); val: what is compared and written
+struct LsCol {
+  uint32_t kind, n;
+  const uint32_t *nul, *val;
+  const uint8_t* ins;
+};
+__device__ __forceinline__ bool ls_is_null(const LsCol& q, uint32_t i) { return q.nul && q.nul[i] == NONE32; }
+// does value i (> 0) continue the run of value i - 1?
+__device__ __forceinline__ bool ls_same(const LsCol& q, const LocalBufs& L, const uint32_t* key_off, uint32_t i) {
+  if (q.kind == LS_RAW) return false;
+  if (q.kind == LS_BOOL) return (q.ins[i] != 0) == (q.ins[i - 1] != 0);
+  const bool ni = ls_is_null(q, i), nj = ls_is_null(q, i - 1);
+  if (ni != nj) return false;
+  if (ni) return true;
+  if (q.kind != LS_STR) return q.val[i] == q.val[i - 1];
+  const uint32_t len = q.nul[i];
+  if (len != q.nul[i - 1]) return false;
+  if (key_off[i] == key_off[i - 1]) return true;
+  const uint8_t *a = L.arena + key_off[i], *b = L.arena + key_off[i - 1];
+  for (uint32_t k = 0; k < len; k++)
+    if (a[k] != b[k]) return false;
+  return true;
+}
+// the value of a run, as the column writes it
+template <bool W> __device__ __forceinline__ uint32_t ls_value(const LsCol& q, const LocalBufs& L, const uint32_t* key_off, uint32_t i, uint8_t*& p) {
+  if (q.kind == LS_DELTA) return ls_sleb<W>(p, (int64_t)(int32_t)q.val[i]);
+  if (q.kind == LS_NUM) return ls_uleb<W>(p, q.val[i]);
+  const uint32_t len = q.nul[i];   // (LS_STR: the length prefix and the key's bytes)
+  const uint32_t n = ls_uleb<W>(p, len) + len;
+  if (W) {
+    const uint8_t* a = L.arena + key_off[i];
+    for (uint32_t k = 0; k < len; k++) p[k] = a[k];
+    p += len;
+  }
+  return n;
+}
+// The run that starts at value i: its bytes, counted or written at p. `any`: the column holds a value that is not null (a column of
+// nothing but nulls is empty, encoding.js:651-654).
+template <bool W>
+__device__ __forceinline__ uint32_t ls_run(const LsCol& q, const LocalBufs& L, const LsLds& s, uint32_t c, uint32_t nw, bool any, uint32_t i, uint8_t* p) {
+  const unsigned long long *start = s.start[c], *nn = s.nn[c];
+  if (q.kind == LS_RAW) {   // the value bytes of row i (raw values: no headers)
+    const uint32_t len = s.v[7][i] >> 4;
+    if (W && len) local_value_write(L, L.values[s.v[LS_V_VIDX][i]], len, p);
+    return len;
+  }
+  const uint32_t len = ls_next_set(start, nw, i + 1) - i;
+  if (q.kind == LS_BOOL) {   // alternating run lengths, the first run counts `false` (encoding.js:1061-1135)
+    uint32_t sz = 0;
+    if (i == 0 && q.ins[0]) { if (W) *p++ = 0; sz = 1; }
+    return sz + ls_uleb<W>(p, len);
+  }
+  if (!any) return 0;
+  if (ls_is_null(q, i)) {
+    if (W) *p++ = 0;
+    return 1 + ls_uleb<W>(p, len);
+  }
+  uint32_t sz = 0;
+  if (len >= 2) sz = ls_sleb<W>(p, (int64_t)len);
+  else if (i == 0 || !ls_lone(start, nn, nw, i - 1)) sz = ls_sleb<W>(p, -(int64_t)(ls_next_not_lone(start, nn, nw, i) - i));   // the literal's count
+  return sz + ls_value<W>(q, L, s.v[LS_V_KEY_OFF], i, p);
+}
+
+__global__ __launch_bounds__(LS_THREADS) void kl_small(LocalBufs L, uint8_t* host_out) {
+  __shared__ LsLds s;
+  const uint32_t t = threadIdx.x, lane = t & (WAVE - 1), c = t / WAVE;
+  const uint32_t M = L.rows, P = L.pred_rows, O = L.n_ops;
+  uint32_t* h_words = (uint32_t*)host_out;   // flags[4] | col_len[HIST_NCOL]
+  auto refuse = [&]() {   // (every thread takes the same way out)
+    if (t < 4) h_words[t] = t == 0 ? (uint32_t)HF_INVALID : 0u;
+    if (t < HIST_NCOL) h_words[4 + t] = 0;
+  };
+  if (M > LOCAL_SMALL_ROWS || P > LOCAL_SMALL_PREDS || O > LOCAL_SMALL_OPS) { refuse(); return; }   // (the host asked local_small_fits first)
+  if (t == 0) s.flag = 0;
+  // ---- the scans over `multi` and `pcnt`: first row / first pred entry of every op ----
+  uint32_t rows = 0, preds = 0;
+  const uint32_t rb = ls_block_scan(t < O ? L.multi[t] : 0u, s.wtot, &rows);
+  const uint32_t pb = ls_block_scan(t < O ? L.pcnt[t] : 0u, s.wtot, &preds);
+  if (t <= O) { s.row_base[t] = rb; s.pred_base[t] = pb; }
+  if (rows != M || preds != P) { refuse(); return; }   // the counts the host planned with are not what the ops expand to
+  __syncthreads();
+  // ---- expansion: a thread per row ----
+  if (t < M) {
+    am355_local_op op;
+    const LocalRow r = local_expand_row(L, s.row_base, s.pred_base, t, op);
+    s.v[0][t] = r.obj_actor; s.v[1][t] = r.obj_ctr; s.v[2][t] = r.key_actor; s.v[3][t] = r.key_ctr;
+    s.v[LS_V_KEY_OFF][t] = r.key_off; s.v[LS_V_KEY_LEN][t] = r.key_len;
+    s.v[6][t] = r.action; s.v[7][t] = r.val_tl; s.v[LS_V_VIDX][t] = r.vidx; s.v[9][t] = r.pred_num;
+    s.ins[t] = (uint8_t)r.insert;
+    if ((unsigned long long)r.pred_at + r.pred_num > P) atomicOr(&s.flag, (uint32_t)HF_INVALID);
+    else local_row_preds(L, op, r, s.p[0] + r.pred_at, s.p[1] + r.pred_at);
+  }
+  __syncthreads();
+  if (s.flag) { refuse(); return; }
+  // ---- a wavefront per column ----
+  LsCol q;
+  q.kind = c == 3 || c == 11 ? LS_DELTA : c == 4 ? LS_STR : c == 5 ? LS_BOOL : c == 8 ? LS_RAW : LS_NUM;
+  q.n = c >= 10 ? P : M;
+  q.nul = c == 4 ? s.v[LS_V_KEY_LEN] : c == 5 || c == 8 ? nullptr : c == 10 ? s.p[0] : c == 11 ? s.p[1] : s.v[c];
+  q.val = c == 3 ? s.d[0] : c == 11 ? s.d[1] : q.nul;
+  q.ins = s.ins;
+  const uint32_t n = q.n, nw = (M > P ? M : P) / 64 + 1;   // the same trip count for every wavefront: the barriers below are the workgroup's
+  bool any = false;
+  for (uint32_t ch = 0; ch < nw; ch++) {
+    const uint32_t i = ch * 64 + lane;
+    const unsigned long long m = __ballot(i < n && !ls_is_null(q, i));
+    if (lane == 0) s.nn[c][ch] = m;
+    any = any || m != 0;
+  }
+  __syncthreads();
+  if (q.kind == LS_DELTA) {   // successive differences of the values that are not null (encoding.js:932-948), modulo 2^32: exact int32
+    uint32_t* d = c == 3 ? s.d[0] : s.d[1];
+    for (uint32_t i = lane; i < n; i += WAVE) {
+      if (q.nul[i] == NONE32) { d[i] = 0; continue; }
+      const uint32_t j = ls_prev_set(s.nn[c], i);
+      d[i] = q.nul[i] - (j != NONE32 ? q.nul[j] : 0u);
+    }
+  }
+  __syncthreads();
+  for (uint32_t ch = 0; ch < nw; ch++) {
+    const uint32_t i = ch * 64 + lane;
+    const unsigned long long m = __ballot(i < n ? (i == 0 || !ls_same(q, L, s.v[LS_V_KEY_OFF], i)) : i == n);
+    if (lane == 0) s.start[c][ch] = m;
+  }
+  __syncthreads();
+  uint32_t carry = 0;
+  for (uint32_t ch = 0; ch < nw; ch++) {
+    const uint32_t i = ch * 64 + lane;
+    const uint32_t sz = i < n && ls_bit(s.start[c], i) ? ls_run<false>(q, L, s, c, nw, any, i, nullptr) : 0u;
+    const uint32_t incl = wave_incl_scan_u32(sz, lane);
+    if (i < n) s.off[c][i] = carry + incl - sz;
+    carry += __shfl(incl, WAVE - 1);
+  }
+  if (lane == 0) s.col_len[c] = carry;
+  __syncthreads();
+  if (t == 0) {
+    uint32_t at = 0;
+    for (uint32_t k = 0; k < HIST_NCOL; k++) { s.col_base[k] = at; at += s.col_len[k]; }
+    s.col_base[HIST_NCOL] = at;
+    if (at > LOCAL_SMALL_OUT_BYTES) s.flag = HF_INVALID;   // (cannot be for a request inside the limits: the arena is their worst case)
+  }
+  __syncthreads();
+  if (s.flag) { refuse(); return; }
+  for (uint32_t i = lane; i < n; i += WAVE) {
+    if (!ls_bit(s.start[c], i)) continue;
+    // the run's stretch: up to where the next run starts, inside the column's stretch, inside the arena
+    const uint32_t j = ls_next_set(s.start[c], nw, i + 1), end = j < n ? s.off[c][j] : s.col_len[c];
+    if (s.off[c][i] > end || (size_t)s.col_base[c] + end > LOCAL_SMALL_OUT_BYTES) { atomicOr(&s.flag, (uint32_t)HF_INVALID); continue; }
+    if (end > s.off[c][i]) (void)ls_run<true>(q, L, s, c, nw, any, i, s.out + s.col_base[c] + s.off[c][i]);
+  }
+  __syncthreads();
+  if (s.flag) { refuse(); return; }
+  // ---- to the host: the bytes as dwords, the lengths, the flag word ----
+  const uint32_t words = (s.col_base[HIST_NCOL] + 3) / 4;
+  uint32_t* dst = (uint32_t*)(host_out + LOCAL_SMALL_HEAD);
+  const uint32_t* src = (const uint32_t*)s.out;
+  for (uint32_t w = t; w < words; w += LS_THREADS) dst[w] = src[w];
+  if (t < HIST_NCOL) h_words[4 + t] = s.col_len[t];
+  if (t < 4) h_words[t] = 0;
+}
+
+void local_small_encode(const LocalBufs& L, uint8_t* host_out, hipStream_t st) {
+  hipLaunchKernelGGL(kl_small, dim3(1), dim3(LS_THREADS), 0, st, L, host_out);
 }
 
 }  // namespace am355

@@ -342,6 +342,11 @@ def _bind(path):
         L.am355_local_change_calls.argtypes = [vp, vp]
         for f in ("am355_encode_change", "am355_apply_local_change", "am355_local_change_calls"):
             getattr(L, f).restype = ctypes.c_int
+    if hasattr(L, "am355_set_local_small"):   # (libraries of earlier commits, loaded for an A/B run, end before these)
+        L.am355_set_local_small.argtypes = [vp, ctypes.c_int]
+        L.am355_set_local_small.restype = ctypes.c_int
+        L.am355_local_small_calls.argtypes = [vp, vp]
+        L.am355_local_small_calls.restype = ctypes.c_int
     if hasattr(L, "am355_changes_added"):   # (libraries of earlier commits, loaded for an A/B run, end before these)
         L.am355_find_changes.argtypes = [vp, vp, u32, vp]
         for f in ("am355_changes_since", "am355_changes_added", "am355_missing_deps"):
@@ -472,6 +477,17 @@ class Engine:
         """(requests apply_local_change served, requests it refused)."""
         out = (ctypes.c_uint64 * 2)()
         self._check(self._L.am355_local_change_calls(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def set_local_small(self, on):
+        """am355_set_local_small: a change request inside the limits of csrc/am355_hist.h LOCAL_SMALL_* (a keystroke, a pasted line) is
+        built by one workgroup in one launch instead of by the bulk encoders (off by default)."""
+        self._check(self._L.am355_set_local_small(self._h, 1 if on else 0))
+
+    def local_small_calls(self):
+        """(changes the one workgroup built, requests that found the switch on but lay outside its limits and took the bulk path)."""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self._L.am355_local_small_calls(self._h, out))
         return int(out[0]), int(out[1])
 
     def reset(self):

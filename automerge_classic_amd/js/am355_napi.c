@@ -1038,6 +1038,37 @@ static napi_value js_local_change_calls(napi_env env, napi_callback_info info) {
   return arr;
 }
 
+/* setLocalSmall(ctx, on): am355_set_local_small (a change request inside the limits of the path -- a keystroke, a pasted line -- is built
+   by one workgroup in one launch instead of by the bulk encoders) */
+static napi_value js_set_local_small(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  bool on = true;
+  if (argc > 1) NAPI_CALL(env, napi_get_value_bool(env, argv[1], &on));
+  int rc = am355_set_local_small(ctx, on ? 1 : 0);
+  if (rc) return throw_engine(env, ctx, rc);
+  return NULL;
+}
+
+/* localSmallCalls(ctx) -> [built by the one workgroup, switch on but outside the limits: bulk path] = am355_local_small_calls */
+static napi_value js_local_small_calls(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  uint64_t out[2] = {0, 0};
+  int rc = am355_local_small_calls(ctx, out);
+  if (rc) return throw_engine(env, ctx, rc);
+  napi_value arr, v;
+  NAPI_CALL(env, napi_create_array_with_length(env, 2, &arr));
+  for (uint32_t k = 0; k < 2; k++) { napi_create_double(env, (double)out[k], &v); napi_set_element(env, arr, k, v); }
+  return arr;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"create", NULL, js_create, NULL, NULL, NULL, napi_enumerable, NULL},
@@ -1079,6 +1110,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"encodeChange", NULL, js_encode_change, NULL, NULL, NULL, napi_enumerable, NULL},
       {"applyLocalChange", NULL, js_apply_local_change, NULL, NULL, NULL, napi_enumerable, NULL},
       {"localChangeCalls", NULL, js_local_change_calls, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"setLocalSmall", NULL, js_set_local_small, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"localSmallCalls", NULL, js_local_small_calls, NULL, NULL, NULL, napi_enumerable, NULL},
       {"shardUniqueId", NULL, js_shard_unique_id, NULL, NULL, NULL, napi_enumerable, NULL},
       {"shardInit", NULL, js_shard_init, NULL, NULL, NULL, napi_enumerable, NULL},
       {"shardedReplay", NULL, js_sharded_replay, NULL, NULL, NULL, napi_enumerable, NULL},

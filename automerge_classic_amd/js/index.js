@@ -28,6 +28,7 @@ const HYDRATE_FROM_DOC = process.env.MI355X_HYDRATE === 'doc'
 const MAP_MERGE = process.env.MI355X_MAP_MERGE === '1'   // am355_set_resident_map_merge for every context of this module
 const NEW_OBJECTS = process.env.MI355X_NEW_OBJECTS !== '0'   // am355_set_resident_new_objects for every context of this module (MI355X_NEW_OBJECTS=0: off, for A/B)
 const COUNTERS = process.env.MI355X_COUNTERS !== '0'   // am355_set_resident_counters for every context of this module (MI355X_COUNTERS=0: off, for A/B)
+const LOCAL_SMALL = process.env.MI355X_LOCAL_SMALL !== '0'   // am355_set_local_small for every context of this module (MI355X_LOCAL_SMALL=0: off, for A/B)
 const PATCH_VIA_JSON = process.env.MI355X_PATCH_VIA_JSON === '1'   // A/B: JSON text rendered by the engine + JSON.parse
 const LOCAL_CHANGE = process.env.MI355X_LOCAL_CHANGE !== '0'   // applyLocalChange on the engine (MI355X_LOCAL_CHANGE=0: the reference path, for A/B)
 const { materialize } = require('./materialize.js')
@@ -46,6 +47,7 @@ if (!JS_ONLY) {
   if (MAP_MERGE) addon.setResidentMapMerge(ctx, true)   // (as for every context acquireContext makes, see there)
   if (NEW_OBJECTS) addon.setResidentNewObjects(ctx, true)
   if (COUNTERS) addon.setResidentCounters(ctx, true)
+  if (LOCAL_SMALL) addon.setLocalSmall(ctx, true)
   contexts.push({ ctx, generation: 0, used: 0 })
 }
 
@@ -111,6 +113,10 @@ function acquireContext() {
     // and every table rebuilt (the reference adds the increment to the counter's succ list in the block it visits, new.js:1052-1290);
     // measured faster than merge_run in every case timed, profiles/counter_apply_timings.txt: on unless MI355X_COUNTERS=0
     if (COUNTERS) addon.setResidentCounters(e.ctx, true)
+    // a keystroke (a change request of a few hundred rows at most) is built by one workgroup in one launch instead of by the bulk column
+    // encoders (~115 stream commands); measured 0.18 against 0.54-0.62 ms for a typed character, 0.23-0.27 against 0.59-0.65 for 200, a paste beyond
+    // the limits unchanged, profiles/local_small_timings.txt: on unless MI355X_LOCAL_SMALL=0
+    if (LOCAL_SMALL) addon.setLocalSmall(e.ctx, true)
     if (graphProbeMin !== null) addon.setGraphProbeMin(e.ctx, graphProbeMin)
     contexts.push(e)
   } else {
@@ -936,6 +942,8 @@ module.exports = {
   _residentNewObjectCalls: () => contexts.reduce((s, e) => { const w = addon.residentNewObjectCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),
   // [calls whose counter increments were written into the stored map records in place, calls where that stage declined], over all contexts
   _residentCounterCalls: () => contexts.reduce((s, e) => { const w = addon.residentCounterCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),
+  // [local changes built by one workgroup, requests that found the switch on but lay outside its limits: bulk path], over all contexts
+  _localSmallCalls: () => contexts.reduce((s, e) => { const w = addon.localSmallCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),
   // [membership tests of hash-graph queries answered on the device, by the engine's host index], over all contexts; and the switch
   // between the two (am355_set_graph_probe_min) for every context there is
   _graphQueryCalls: () => contexts.reduce((s, e) => { const w = addon.graphQueryCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),

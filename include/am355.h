@@ -356,6 +356,22 @@ typedef struct {
 int am355_encode_change(am355_ctx *ctx, const am355_local_change *request, const uint8_t **bytes, size_t *len, uint8_t hash[32]);
 int am355_apply_local_change(am355_ctx *ctx, const am355_local_change *request, const uint8_t **change, size_t *len);
 int am355_local_change_calls(const am355_ctx *ctx, uint64_t out[2]);
+/*
+ * am355_set_local_small (off by default; with it off both calls above enqueue what they did before the switch existed): on != 0: a
+ * request of at most 256 ops that expands to at most 512 rows and 512 pred entries and holds at most 4096 key + value bytes (a key once
+ * per row it stands on, 8 bytes per number, a string's UTF-8 length) -- a keystroke, a pasted line -- is built by ONE workgroup: scans,
+ * expansion, value bytes and the twelve column encodes in LDS, the columns, their lengths and a flag word written straight into pinned
+ * host memory (the upload, one launch, one wait, against ~115 stream commands). The limits are compile-time constants
+ * (csrc/am355_hist.h LOCAL_SMALL_OPS / _ROWS / _PREDS / _BYTES) and are checked before anything is enqueued; a request beyond any of them
+ * takes the bulk path exactly as with the switch off. Which requests are refused, the change bytes, the hash and the apply half of
+ * am355_apply_local_change do not depend on the switch.
+ * am355_local_small_calls: out[0] changes the one workgroup built (am355_encode_change counts here too), out[1] requests that found the
+ * switch on but lay outside the limits and took the bulk path. Both stay 0 with the switch off.
+ * AM355_LOCAL_SMALL_VERIFY=1 in the environment (tests; read per call): after a small build the same request is built again by the bulk
+ * path and the twelve lengths and column bytes are compared; a difference is AM355_E_DEVICE with the column named in am355_last_error.
+ */
+int am355_set_local_small(am355_ctx *ctx, int on);
+int am355_local_small_calls(const am355_ctx *ctx, uint64_t out[2]);
 /* What the patch of am355_apply_local_change carries beyond the record tables of am355_fetch_apply_ir (whose layout stays as it is):
  * `actor` and `seq` behind `diffs` (new.js:1874-1877). The tables' `heads` are already without the new change's own hash
  * (backend.js:88-89). is_local == 0 when the last patch came from am355_apply_changes. Valid when am355_fetch_apply_ir is. */

@@ -8,7 +8,11 @@ Text behind its first element:
     (b) 200 characters per change                     (8 calls)
     (c) a paste of 100,000 characters, one op         (3 calls)
 
-    python tools/time_local_change.py [--lib libam355.so] [--scale 1.0] [--remote] [--label text] [--trace]
+    python tools/time_local_change.py [--lib libam355.so] [--scale 1.0] [--remote] [--small] [--label text] [--trace]
+
+--small: am355_set_local_small on (a library that has the switch): the changes of (a) and (b) are built by one workgroup (kl_small), the
+paste of (c) lies beyond its limits and takes the bulk path; local_small_calls is printed. profiles/local_small_timings.txt is three
+runs alternating in one session, two rounds: the parent commit's library, this one with the switch off, this one with --small.
 
 --remote: the changes are encoded first (am355_encode_change of the shipped library, deps chained by hand) and applied with
 am355_apply_changes of --lib. --trace: AM355_TRACE=1 for the timed calls, whose laps (request staged / expand + encodes / columns on the
@@ -47,6 +51,7 @@ def main():
     ap.add_argument("--lib", default=engine.DEFAULT_LIB)
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--remote", action="store_true")
+    ap.add_argument("--small", action="store_true")
     ap.add_argument("--label", default="")
     ap.add_argument("--trace", action="store_true")
     a = ap.parse_args()
@@ -55,6 +60,8 @@ def main():
     for sw in ("set_resident_new_actors", "set_resident_new_objects", "set_resident_counters"):
         if hasattr(eng._L, "am355_" + sw):
             getattr(eng, sw)(True)
+    if a.small:
+        eng.set_local_small(True)
     eng.apply_changes(log)
     st = eng.stats()
     whole = json.loads(eng.patch_json())
@@ -107,7 +114,8 @@ def main():
     for name, ts in times.items():
         print(f"{name:32s} calls {len(ts):2d}  median {statistics.median(ts):8.3f} ms  max {max(ts):8.3f} ms   [{' '.join(f'{t:.3f}' for t in ts)}]")
     print("resident counters (served, fell back, in place) added:", tuple(x - y for x, y in zip(after, before)),
-          "" if a.remote else f"local_change_calls {eng.local_change_calls()}")
+          "" if a.remote else f"local_change_calls {eng.local_change_calls()}",
+          f"local_small_calls {eng.local_small_calls()}" if hasattr(eng._L, "am355_local_small_calls") else "")
     eng.close()
 
 
