@@ -50,7 +50,6 @@ static bool ctx_init(am355_ctx* c) {
   if (!c->h_sig.ensure(sizeof(HostSignals))) return false;
   memset(c->h_sig.p, 0, sizeof(HostSignals));
   if (const char* e = getenv("AM355_PHASE_EVENTS")) c->phase_events = strcmp(e, "0") != 0;
-  if (const char* e = getenv("AM355_STAGE1_FILLS")) c->inline_fills = strcmp(e, "stream") != 0;
   return true;
 }
 

@@ -1,7 +1,8 @@
 // Context of the C ABI (include/am355.h) and what its translation units share: device / pinned buffers, the host thread pool, struct
-// am355_ctx, error helpers. am355_api.hip: entry points; am355_stage.hip: staging; am355_replay.hip: scheduler, plan, orchestration of
-// the device stages; am355_calls.hip: patch IR, applyChanges, dependency graph, Bloom filters -- and, included at its end,
-// am355_graph.hip: the hash-graph queries; am355_save.hip: save + history after load; am355_shard.hip: objectId sharding.
+// am355_ctx, error helpers, the AM355_TRACE lap type. am355_api.hip: entry points; am355_stage.hip: staging; am355_replay.hip: host
+// scheduler, plan, device buffers, and the two sequences of named phases that orchestrate the device stages -- the full replay
+// (replay_impl over a Stage1) and the resident applyChanges (replay_resident over a ResidentBatch); am355_calls.hip: patch IR,
+// applyChanges, dependency graph, Bloom filters -- and, included at its end, am355_graph.hip: the hash-graph queries; am355_save.hip: save + history after load; am355_shard.hip: objectId sharding.
 #pragma once
 #include "../../include/am355.h"
 #include "am355_decode.h"
@@ -28,6 +29,7 @@
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
@@ -293,6 +295,25 @@ class AsyncLane {
   std::thread t_;  // (last member: the thread starts with everything above constructed)
 };
 
+// AM355_TRACE (read per call): a call's milestones on stderr, each with the time since the call began, under the call's prefix in a
+// column of the call's width ("replay:", 28).
+struct TraceLap {
+  bool on;
+  const char* prefix;
+  int width;
+  std::chrono::steady_clock::time_point t0;
+  TraceLap(const char* prefix_, int width_, std::chrono::steady_clock::time_point t0_ = std::chrono::steady_clock::now())
+      : on(getenv("AM355_TRACE") != nullptr), prefix(prefix_), width(width_), t0(t0_) {}
+  void operator()(const char* what) const {
+    if (on) fprintf(stderr, "%s %-*s +%8.3f ms\n", prefix, width, what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  }
+};
+
+struct LaneJoin {   // (whatever way its scope is left, the helper thread is not running the posted job any more)
+  AsyncLane* l = nullptr;
+  ~LaneJoin() { if (l) l->wait(); }
+};
+
 struct Hash32 {
   uint8_t b[32];
   bool operator==(const Hash32& o) const { return memcmp(b, o.b, 32) == 0; }
@@ -357,7 +378,6 @@ struct am355_ctx {
   // AM355_PHASE_EVENTS=1: HIP events between the phases of a change replay (am355_stats.ms_parse / ms_decode / ms_merge / ms_order). Off by
   // default: every event record between two kernels of the main stream is a packet of its own in front of the next dispatch.
   bool phase_events = false;
-  bool inline_fills = true;  // AM355_STAGE1_FILLS=stream: the fills of stage 1 as memsets on stream3 (round-2 form) instead of inside k_parse_changes
   DevBuf d_big, d_bigvals, d_ks;     // document load: token / record index, column values, keyStr run table
   HostBuf h_biginfo;
   BigColDesc doc_cols{};
@@ -653,7 +673,7 @@ int upload_offsets(am355_ctx* c);   // the staged changes' offsets table to HBM,
 int load_document_impl(am355_ctx* c, const uint8_t* doc, size_t len, bool defer_checksum = false);
 int backend_load_impl(am355_ctx* c, const uint8_t* doc, size_t len);
 int ir_copy_enqueue(am355_ctx* c, bool with_edits);
-// replay: host scheduler / plan, device buffers, orchestration of the device stages (am355_replay.hip)
+// replay: host scheduler / plan, device buffers, the phases of the full replay and of the resident applyChanges (am355_replay.hip)
 int setup_buffers(am355_ctx* c, uint32_t NA);
 int replay_impl(am355_ctx* c);
 int ensure_ir_fresh(am355_ctx* c);   // rebuilds the whole-document patch tables when a resident call left them stale (ir_stale)

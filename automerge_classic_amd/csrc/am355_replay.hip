@@ -1,41 +1,127 @@
-// am355_replay of the C ABI (include/am355.h): host scheduler (fallback of the device scheduler am355_sched.hip), host half of the plan,
-// device buffers, orchestration of the device stages for change logs (replay_impl) and saved documents (replay_document). See am355_ctx.h.
+// am355_replay of the C ABI (include/am355.h), in this order: the helpers every path shares (set_heads, build_actor_spans); the host
+// scheduler (schedule, with schedule_lineage: fallback of the device scheduler am355_sched.hip); the host half of the plan (plan_fast);
+// device buffers (carve_cols, setup_buffers); decode + merge (run_device, run_device_planned); saved documents (replay_document);
+// Backend.applyChanges onto the kept state (replay_resident: phases over a ResidentBatch); the full replay of a change log (replay_impl:
+// phases over a Stage1). DESIGN.md has the phase tables of the last two. See am355_ctx.h.
 #include "am355_ctx.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // host scheduler
 // ---------------------------------------------------------------------------------------------------------
 
-// Open-addressing set of 32-byte hashes (keyed by their first 8 bytes, verified by full comparison).
-struct HashSet {
-  std::vector<const uint8_t*> slot;
-  size_t mask = 0;
-  void init(size_t n) {
-    size_t cap = 16;
-    while (cap < n * 2 + 2) cap <<= 1;
-    slot.assign(cap, nullptr);
-    mask = cap - 1;
+// c->heads from the hashes (c->h_hashes) of the changes i < n with is_head(i): the list of their hash pointers, sorted bytewise
+// (new.js:1582-1583, 1593), then copied.
+template <class IsHead>
+static void set_heads(am355_ctx* c, uint32_t n, IsHead is_head) {
+  std::vector<const uint8_t*> hs;
+  for (uint32_t i = 0; i < n; i++)
+    if (is_head(i)) hs.push_back(c->h_hashes.as<uint8_t>() + 32 * (size_t)i);
+  std::sort(hs.begin(), hs.end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; });
+  c->heads.resize(hs.size() * 32);
+  for (size_t i = 0; i < hs.size(); i++) memcpy(&c->heads[32 * i], hs[i], 32);
+}
+
+// Per-actor tables of (start_op, n_ops, op_base) over c->plans (application order) into c->spans / c->actor_tab_off: counting layout
+// (no allocation in steady state: `cnt` holds the spans per author on entry, na + 1 words), then every actor's table is verified
+// ascending -- sorted when it is not -- and disjoint. span_of(plan): start_op and n_ops of the plan's change.
+template <class SpanOf>
+static int build_actor_spans(am355_ctx* c, uint32_t na, std::vector<uint32_t>& cnt, SpanOf span_of) {
+  c->actor_tab_off.assign(na + 1, 0);
+  for (uint32_t a = 0; a < na; a++) c->actor_tab_off[a + 1] = c->actor_tab_off[a] + cnt[a];
+  c->spans.resize(c->actor_tab_off[na]);
+  for (uint32_t a = 0; a < na; a++) cnt[a] = c->actor_tab_off[a];
+  for (const ChangePlan& pl : c->plans) { ActorSpan s = span_of(pl); s.op_base = pl.op_base; c->spans[cnt[pl.author]++] = s; }
+  for (uint32_t a = 0; a < na; a++) {
+    ActorSpan* v = c->spans.data() + c->actor_tab_off[a];
+    size_t k_n = c->actor_tab_off[a + 1] - c->actor_tab_off[a];
+    bool sorted = true;
+    for (size_t k = 1; k < k_n; k++) sorted = sorted && v[k - 1].start_op <= v[k].start_op;
+    if (!sorted) std::sort(v, v + k_n, [](const ActorSpan& x, const ActorSpan& y) { return x.start_op < y.start_op; });
+    for (size_t k = 1; k < k_n; k++)
+      if ((uint64_t)v[k - 1].start_op + v[k - 1].n_ops > v[k].start_op) {
+        c->flags |= AM355_F_DUP_OPID;
+        return fail(c, AM355_E_INVALID, "overlapping op id ranges for one actor (duplicate operation ID)");
+      }
   }
-  static uint64_t key(const uint8_t* h) { uint64_t v; memcpy(&v, h, 8); return v * 0x9e3779b97f4a7c15ull; }
-  const uint8_t** find(const uint8_t* h) {
-    size_t i = (size_t)(key(h) >> 20) & mask;
-    while (slot[i]) {
-      if (slot[i] != (const uint8_t*)1 && memcmp(slot[i], h, 32) == 0) return &slot[i];
-      i = (i + 1) & mask;
-    }
-    return nullptr;
-  }
-  bool has(const uint8_t* h) { return find(h) != nullptr; }
-  void add(const uint8_t* h) {
-    size_t i = (size_t)(key(h) >> 20) & mask;
-    while (slot[i] && slot[i] != (const uint8_t*)1) i = (i + 1) & mask;
-    slot[i] = h;
-  }
-  void del(const uint8_t* h) {
-    const uint8_t** p = find(h);
-    if (p) *p = (const uint8_t*)1;  // tombstone
-  }
+  return AM355_OK;
+}
+
+// pass numbers of the host scheduler: not computed yet | never applied | on the walk's stack
+static constexpr uint32_t UNSET = 0xffffffffu, NEVER = 0xfffffffeu, BUSY = 0xfffffffdu;
+
+// The host scheduler for a lineage that began with Backend.load (see am355_ctx.h graph_mode): the reference's retry loop itself, round
+// by round. What it reads of the batch and of the context, as schedule() has it: the first na0 changes are the applied prefix, the first
+// nd of them came with the document; self / dep_*: stream B's indexes; rank[local_ids[local_off[ci]]]: the author's rank.
+struct LineageInput {
+  uint32_t n, na, na0, nd;
+  bool doc_head_index_known;
+  const ChangeMeta* metas;
+  const uint32_t *self, *dep_idx, *dep_first, *dep_count, *rank, *local_ids, *local_off;
+  std::vector<uint8_t> doc_has_dependent;   // per change of the document: another change of the document depends on it
 };
+struct LineageOutcome { std::vector<uint32_t> pass, gpass, gpos; bool graph_after = true; uint32_t flags = 0; };
+// graph_known: the reference had the hash graph of the loaded document (computeHashGraph) when the call began
+static LineageOutcome schedule_lineage(const LineageInput& in, bool graph_known) {
+  const uint32_t n = in.n, na0 = in.na0, nd = in.nd;
+  const ChangeMeta* metas = in.metas;
+  LineageOutcome o;
+  auto author_of = [&](uint32_t ci) { return in.rank[in.local_ids[in.local_off[ci]]]; };
+  auto group_of = [&](uint32_t ci) { return in.self[ci] < n ? in.self[ci] : ci; };
+  o.pass.assign(n, NEVER); o.gpass.assign(n, NEVER); o.gpos.assign(n, 0);
+  std::vector<uint8_t> vis_dep(n, 0), vis_dup(n, 0), in_round(n, 0);  // by group: satisfies a dependency / makes a copy a duplicate
+  std::vector<uint64_t> clk(in.na, 0);
+  for (uint32_t i = 0; i < na0; i++) { clk[author_of(i)] = metas[i].seq; o.pass[i] = 0; o.gpass[group_of(i)] = 0; o.gpos[group_of(i)] = i; }
+  auto all_prior = [&]() {
+    std::fill(vis_dep.begin(), vis_dep.end(), 0); std::fill(vis_dup.begin(), vis_dup.end(), 0);
+    for (uint32_t i = 0; i < na0; i++) vis_dep[group_of(i)] = vis_dup[group_of(i)] = 1;
+  };
+  if (graph_known) all_prior();
+  else {
+    for (uint32_t i = nd; i < na0; i++) vis_dep[group_of(i)] = vis_dup[group_of(i)] = 1;
+    for (uint32_t i = 0; i < nd; i++)
+      if (!in.doc_has_dependent[i]) { vis_dup[i] = 1; vis_dep[i] = in.doc_head_index_known ? 1 : 0; }  // (a head without index: -1, new.js:1727-1729, 1563)
+  }
+  std::vector<uint32_t> queue, app, enq;
+  for (uint32_t ci = na0; ci < n; ci++) queue.push_back(ci);
+  bool graph = graph_known;
+  uint32_t round_pass = 0;
+  while (!queue.empty()) {
+    app.clear(); enq.clear();
+    std::vector<uint64_t> clk2 = clk;
+    bool aborted = false;
+    for (uint32_t ci : queue) {
+      const uint32_t F = group_of(ci);
+      if (vis_dup[F] || in_round[F]) continue;  // (new.js:1566)
+      bool ready = true;
+      for (uint32_t k = 0; k < in.dep_count[ci] && ready; k++) { const uint32_t dd = in.dep_idx[in.dep_first[ci] + k]; ready = dd < n && (vis_dep[dd] || in_round[dd]); }
+      const uint32_t a = author_of(ci);
+      const uint64_t expected = clk2[a] + 1;
+      if (!ready) enq.push_back(ci);
+      else if (metas[ci].seq < expected) {
+        if (graph) { o.flags |= AM355_F_BAD_SEQ; return o; }  // "Reuse of sequence number"
+        aborted = true;  // (new.js:1581: nothing of this round is applied, the whole queue waits for the hash graph)
+        break;
+      } else if (metas[ci].seq > expected) { o.flags |= AM355_F_BAD_SEQ; return o; }
+      else { clk2[a] = metas[ci].seq; in_round[F] = 1; app.push_back(ci); }
+    }
+    for (uint32_t ci : app) in_round[group_of(ci)] = 0;
+    if (aborted) { app.clear(); enq = queue; }
+    if (!app.empty()) {
+      for (uint32_t ci : app) { const uint32_t F = group_of(ci); o.pass[ci] = round_pass; o.gpass[F] = round_pass; o.gpos[F] = ci; vis_dep[F] = vis_dup[F] = 1; }
+      clk = clk2;
+      round_pass++;
+    }
+    queue = enq;
+    if (queue.empty()) break;
+    if (app.empty()) {
+      if (graph) break;
+      graph = true;  // computeHashGraph: the index is rebuilt from the document as it was BEFORE this call -- what the call applied so far is not in it
+      all_prior();
+    }
+  }
+  o.graph_after = graph;
+  return o;
+}
 
 // General scheduler: exact restatement of the reference's retry loop for any delivery order, duplicates and
 // missing dependencies. Used when the device-side checks cannot prove the in-order fast path.
@@ -44,7 +130,6 @@ static uint32_t rank_device_actors(am355_ctx* c, std::vector<uint32_t>& slot_ran
 static int schedule(am355_ctx* c, const uint32_t* dev_amap, const uint32_t* dev_amap_base) {
   auto T0 = std::chrono::steady_clock::now();
   const ChangeMeta* metas = c->h_metas.as<ChangeMeta>();
-  const uint8_t* hashes = c->h_hashes.as<uint8_t>();
   uint32_t n = c->n_changes;
   const uint8_t* raw = c->raw.data();
   uint32_t dev_flags = 0;
@@ -121,7 +206,6 @@ static int schedule(am355_ctx* c, const uint32_t* dev_amap, const uint32_t* dev_
   local_ids = local_ids_v.data();
   }
   auto T1 = std::chrono::steady_clock::now();
-
   auto T2 = std::chrono::steady_clock::now();
   // ---- causal scheduling (new.js:1550-1597 inside the retry loop of :1822-1841) ----
   // The device has resolved every hash to an index (k_deps_resolve): self[ci] = first change of the batch with ci's hash (ci itself
@@ -142,7 +226,6 @@ static int schedule(am355_ctx* c, const uint32_t* dev_amap, const uint32_t* dev_
   std::vector<uint32_t> applied_all, applied_pass;
   uint32_t sched_flags = 0, n_pending = 0;
   {
-    constexpr uint32_t UNSET = 0xffffffffu, NEVER = 0xfffffffeu, BUSY = 0xfffffffdu;
     // Copies of one change (the same hash several times in the queue) form a group named by its first copy (self[]): every copy is
     // ready as soon as ITS position allows -- a copy standing behind the dependencies its first copy stands in front of is ready a
     // pass earlier -- and the reference applies whichever copy becomes ready first, (pass, position) minimal, dropping the others as
@@ -163,79 +246,21 @@ static int schedule(am355_ctx* c, const uint32_t* dev_amap, const uint32_t* dev_
     const bool lineage = c->in_apply && c->graph_mode != 0 && c->sched_prefix <= n;
     if (lineage) {
       // ---- a lineage that began with Backend.load: the retry loop itself, round by round (see am355_ctx.h graph_mode) ----
-      const uint32_t na0 = c->sched_prefix, nd = std::min(c->doc_n_changes, na0);
-      auto author_of = [&](uint32_t ci) { return rank[local_ids[local_off[ci]]]; };
-      auto group_of = [&](uint32_t ci) { return self[ci] < n ? self[ci] : ci; };
-      std::vector<uint8_t> doc_has_dependent(nd, 0);
-      for (uint32_t j = 0; j < nd; j++)
-        for (uint32_t k = 0; k < dep_count[j]; k++) { uint32_t dd = dep_of(j, k); if (dd < nd) doc_has_dependent[dd] = 1; }
-      struct Outcome { std::vector<uint32_t> pass, gpass, gpos; bool graph_after = true; uint32_t flags = 0; };
-      auto simulate = [&](bool graph_known, Outcome& o) {
-        o.pass.assign(n, NEVER); o.gpass.assign(n, NEVER); o.gpos.assign(n, 0); o.flags = 0;
-        std::vector<uint8_t> vis_dep(n, 0), vis_dup(n, 0), in_round(n, 0);  // by group: satisfies a dependency / makes a copy a duplicate
-        std::vector<uint64_t> clk(na, 0);
-        for (uint32_t i = 0; i < na0; i++) { clk[author_of(i)] = metas[i].seq; o.pass[i] = 0; o.gpass[group_of(i)] = 0; o.gpos[group_of(i)] = i; }
-        auto all_prior = [&]() {
-          std::fill(vis_dep.begin(), vis_dep.end(), 0); std::fill(vis_dup.begin(), vis_dup.end(), 0);
-          for (uint32_t i = 0; i < na0; i++) vis_dep[group_of(i)] = vis_dup[group_of(i)] = 1;
-        };
-        if (graph_known) all_prior();
-        else {
-          for (uint32_t i = nd; i < na0; i++) vis_dep[group_of(i)] = vis_dup[group_of(i)] = 1;
-          for (uint32_t i = 0; i < nd; i++)
-            if (!doc_has_dependent[i]) { vis_dup[i] = 1; vis_dep[i] = c->doc_head_index_known ? 1 : 0; }  // (a head without index: -1, new.js:1727-1729, 1563)
-        }
-        std::vector<uint32_t> queue, app, enq;
-        for (uint32_t ci = na0; ci < n; ci++) queue.push_back(ci);
-        bool graph = graph_known;
-        uint32_t round_pass = 0;
-        while (!queue.empty()) {
-          app.clear(); enq.clear();
-          std::vector<uint64_t> clk2 = clk;
-          bool aborted = false;
-          for (uint32_t ci : queue) {
-            const uint32_t F = group_of(ci);
-            if (vis_dup[F] || in_round[F]) continue;  // (new.js:1566)
-            bool ready = true;
-            for (uint32_t k = 0; k < dep_count[ci] && ready; k++) { const uint32_t dd = dep_of(ci, k); ready = dd < n && (vis_dep[dd] || in_round[dd]); }
-            const uint32_t a = author_of(ci);
-            const uint64_t expected = clk2[a] + 1;
-            if (!ready) enq.push_back(ci);
-            else if (metas[ci].seq < expected) {
-              if (graph) { o.flags |= AM355_F_BAD_SEQ; return; }  // "Reuse of sequence number"
-              aborted = true;  // (new.js:1581: nothing of this round is applied, the whole queue waits for the hash graph)
-              break;
-            } else if (metas[ci].seq > expected) { o.flags |= AM355_F_BAD_SEQ; return; }
-            else { clk2[a] = metas[ci].seq; in_round[F] = 1; app.push_back(ci); }
-          }
-          for (uint32_t ci : app) in_round[group_of(ci)] = 0;
-          if (aborted) { app.clear(); enq = queue; }
-          if (!app.empty()) {
-            for (uint32_t ci : app) { const uint32_t F = group_of(ci); o.pass[ci] = round_pass; o.gpass[F] = round_pass; o.gpos[F] = ci; vis_dep[F] = vis_dup[F] = 1; }
-            clk = clk2;
-            round_pass++;
-          }
-          queue = enq;
-          if (queue.empty()) break;
-          if (app.empty()) {
-            if (graph) break;
-            graph = true;  // computeHashGraph: the index is rebuilt from the document as it was BEFORE this call -- what the call applied so far is not in it
-            all_prior();
-          }
-        }
-        o.graph_after = graph;
-      };
-      Outcome a, b;
-      simulate(c->graph_mode != 1, a);
+      LineageInput in{n, na, c->sched_prefix, std::min(c->doc_n_changes, c->sched_prefix), c->doc_head_index_known, metas, self, dep_idx, dep_first.data(),
+                      dep_count.data(), rank.data(), local_ids, local_off, {}};
+      in.doc_has_dependent.assign(in.nd, 0);
+      for (uint32_t j = 0; j < in.nd; j++)
+        for (uint32_t k = 0; k < dep_count[j]; k++) { uint32_t dd = dep_of(j, k); if (dd < in.nd) in.doc_has_dependent[dd] = 1; }
+      LineageOutcome a = schedule_lineage(in, c->graph_mode != 1);
       if (c->graph_mode == 2) {
-        simulate(false, b);
+        const LineageOutcome b = schedule_lineage(in, false);
         if (a.flags != b.flags || a.pass != b.pass || a.gpass != b.gpass) {
           c->flags |= AM355_F_UNSUPPORTED;
           return fail(c, AM355_E_UNSUPPORTED, "the schedule depends on whether the reference had rebuilt the loaded document's hash graph, which the replayed state does not tell (JS path)");
         }
       }
       if (a.flags) sched_flags |= a.flags;
-      pass = a.pass; gpass = a.gpass; gpos = a.gpos;
+      pass.swap(a.pass); gpass.swap(a.gpass); gpos.swap(a.gpos);
       c->sched_graph_after = a.graph_after;
     }
     for (uint32_t root = 0; root < n && !lineage; root++) {
@@ -322,14 +347,7 @@ static int schedule(am355_ctx* c, const uint32_t* dev_amap, const uint32_t* dev_
   c->n_pending = n_pending;
   c->clock_seq.clear();
   for (uint32_t a : c->clock_actor) c->clock_seq.push_back(clock[a]);
-  {
-    std::vector<const uint8_t*> hs;
-    for (uint32_t ci : applied_all)
-      if (is_head[ci]) hs.push_back(hashes + 32 * (size_t)ci);
-    std::sort(hs.begin(), hs.end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; });
-    c->heads.resize(hs.size() * 32);
-    for (size_t i = 0; i < hs.size(); i++) memcpy(&c->heads[32 * i], hs[i], 32);
-  }
+  set_heads(c, n, [&](uint32_t ci) { return is_head[ci] != 0; });   // (marked in application order above: applied changes only)
 
   auto T3 = std::chrono::steady_clock::now();
   // ---- launch plan for the decode kernels, op-id -> row tables ----
@@ -337,7 +355,7 @@ static int schedule(am355_ctx* c, const uint32_t* dev_amap, const uint32_t* dev_
   c->amap.clear();
   c->amap.reserve(local_off[n]);
   uint64_t ops = 0, preds = 0, max_op = 0;
-  std::vector<std::vector<ActorSpan>> per_actor(na);
+  std::vector<uint32_t> span_cnt(na + 1, 0);
   c->applied_change.clear();
   c->applied_op_base.clear();
   c->pass_first_row.clear();
@@ -356,7 +374,7 @@ static int schedule(am355_ctx* c, const uint32_t* dev_amap, const uint32_t* dev_
     pl.n_actors = local_off[ci + 1] - local_off[ci];
     for (uint32_t k = local_off[ci]; k < local_off[ci + 1]; k++) c->amap.push_back(rank[local_ids[k]]);
     if (m.n_ops) {
-      per_actor[pl.author].push_back(ActorSpan{(uint32_t)m.start_op, m.n_ops, pl.op_base});
+      span_cnt[pl.author]++;
       max_op = std::max<uint64_t>(max_op, m.start_op + m.n_ops - 1);
       c->plans.push_back(pl);
     }
@@ -367,20 +385,7 @@ static int schedule(am355_ctx* c, const uint32_t* dev_amap, const uint32_t* dev_
   c->n_ops = ops;
   c->n_preds = preds;
   c->max_op = max_op;
-  c->spans.clear();
-  c->actor_tab_off.assign(na + 1, 0);
-  for (uint32_t a = 0; a < na; a++) {
-    auto& v = per_actor[a];
-    std::sort(v.begin(), v.end(), [](const ActorSpan& x, const ActorSpan& y) { return x.start_op < y.start_op; });
-    for (size_t k = 1; k < v.size(); k++)
-      if ((uint64_t)v[k - 1].start_op + v[k - 1].n_ops > v[k].start_op) {
-        c->flags |= AM355_F_DUP_OPID;
-        return fail(c, AM355_E_INVALID, "overlapping op id ranges for one actor (duplicate operation ID)");
-      }
-    c->actor_tab_off[a] = (uint32_t)c->spans.size();
-    c->spans.insert(c->spans.end(), v.begin(), v.end());
-  }
-  c->actor_tab_off[na] = (uint32_t)c->spans.size();
+  { int src = build_actor_spans(c, na, span_cnt, [&](const ChangePlan& pl) { return ActorSpan{(uint32_t)metas[pl.change].start_op, metas[pl.change].n_ops, 0}; }); if (src) return src; }
   if (getenv("AM355_DEBUG_TIMING")) {
     auto T4 = std::chrono::steady_clock::now();
     auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -392,9 +397,6 @@ static int schedule(am355_ctx* c, const uint32_t* dev_amap, const uint32_t* dev_
 // ---------------------------------------------------------------------------------------------------------
 // replay
 // ---------------------------------------------------------------------------------------------------------
-
-
-
 
 // distinct actor ids as interned by the device (k_actor_intern) -> lexicographic ranks (hex-string order == byte order, new.js:65):
 // fills slot_rank[slot] and c->actors (by rank). Returns the number of actors.
@@ -474,32 +476,13 @@ static int plan_fast(am355_ctx* c, std::vector<uint32_t>& slot_rank, const uint3
   c->max_op = max_op;
   c->clock_seq.clear();
   for (uint32_t a : c->clock_actor) c->clock_seq.push_back(clock[a]);
-  // per-actor tables of (start_op, n_ops, op_base): counting layout, then verify ascending and disjoint
-  c->actor_tab_off.assign(na + 1, 0);
-  for (uint32_t a = 0; a < na; a++) c->actor_tab_off[a + 1] = c->actor_tab_off[a] + span_cnt[a];
-  c->spans.resize(c->actor_tab_off[na]);
-  for (uint32_t a = 0; a < na; a++) span_cnt[a] = c->actor_tab_off[a];
-  for (const ChangePlan& pl : c->plans) c->spans[span_cnt[pl.author]++] = ActorSpan{br[pl.change].start_op, br[pl.change].n_ops, pl.op_base};
-  for (uint32_t a = 0; a < na; a++) {
-    ActorSpan* v = c->spans.data() + c->actor_tab_off[a];
-    size_t k_n = c->actor_tab_off[a + 1] - c->actor_tab_off[a];
-    bool sorted = true;
-    for (size_t k = 1; k < k_n; k++) sorted = sorted && v[k - 1].start_op <= v[k].start_op;
-    if (!sorted) std::sort(v, v + k_n, [](const ActorSpan& x, const ActorSpan& y) { return x.start_op < y.start_op; });
-    for (size_t k = 1; k < k_n; k++)
-      if ((uint64_t)v[k - 1].start_op + v[k - 1].n_ops > v[k].start_op) {
-        c->flags |= AM355_F_DUP_OPID;
-        return fail(c, AM355_E_INVALID, "overlapping op id ranges for one actor (duplicate operation ID)");
-      }
-  }
-  return AM355_OK;
+  return build_actor_spans(c, na, span_cnt, [&](const ChangePlan& pl) { return ActorSpan{br[pl.change].start_op, br[pl.change].n_ops, 0}; });
 }
 
 // The op rows (13 word columns + the insert byte) and the flattened pred lists, for N rows / P preds.
 static int carve_cols(am355_ctx* c, uint32_t N, uint32_t P, bool estimate = false) {
   canary_scope("replay buffers (carve_cols: op rows, preds)");
-  static const bool no_cap = getenv("AM355_NO_ROW_CAP") != nullptr;   // (A/B: rows carved exactly, as in rounds 1-5; no resident state then)
-  if (c->in_apply && !no_cap && !estimate) {   // (estimate: N, P are the speculative launch's upper estimate already, several times the rows)
+  if (c->in_apply && !estimate) {   // (estimate: N, P are the speculative launch's upper estimate already, several times the rows)
     // am355_apply_changes: room for the document to grow without the rows moving (replay_resident appends to them)
     N = (uint32_t)std::min<uint64_t>((uint64_t)N + N / 4 + 65536, 0x7ffffff0u);
     P = (uint32_t)std::min<uint64_t>((uint64_t)P + P / 4 + 65536, 0xfffffff0u);
@@ -523,8 +506,6 @@ static int carve_cols(am355_ctx* c, uint32_t N, uint32_t P, bool estimate = fals
   return AM355_OK;
 }
 
-// Device buffers for N op rows / P preds, decode, merge, patch IR. `slot_rank` != null: actor tables are the
-// device-interned slots (fast path); null: c->amap holds ranks (general path).
 // Device buffers for N op rows / P preds (op rows, merge scratch, sort scratch, patch IR), carved from a few arenas.
 int setup_buffers(am355_ctx* c, uint32_t NA) {
   uint32_t N = (uint32_t)c->n_ops, P = (uint32_t)c->n_preds;
@@ -546,8 +527,7 @@ int setup_buffers(am355_ctx* c, uint32_t NA) {
   canary_scope("replay buffers (setup_buffers: merge scratch, sort scratch, patch IR)");
   // am355_apply_changes: the per-row arrays of the merge stage are carved with the stride of the op rows' capacity, so that the kept
   // rows' results stay where they are from call to call (replay_resident); their fills go by N (merge_prepare)
-  static const bool no_cap = getenv("AM355_NO_ROW_CAP") != nullptr;
-  const bool by_cap = c->in_apply && c->cols_cap_ops >= N && !no_cap;
+  const bool by_cap = c->in_apply && c->cols_cap_ops >= N;
   // (the op rows of a speculative launch are carved for several times N; the merge arrays take a quarter more than N: ~1.3 x the exact size)
   if (by_cap) Nc = std::min<size_t>(c->cols_cap_ops, (size_t)N + N / 4 + 65536) + 1;
   {
@@ -571,8 +551,7 @@ int setup_buffers(am355_ctx* c, uint32_t NA) {
     b.actor_tab_off = c->p_tab_off;
     b.spans = c->p_spans;
     b.bits_ctr = (uint32_t)bits_ctr; b.bits_actor = (uint32_t)bits_actor;
-    static const bool fill_kernel = getenv("AM355_FILL_KERNEL") != nullptr;   // (A/B: the fused fill launch with exactly carved rows too)
-    b.first_row = 0; b.seed_list_inc = 0; b.row_stride = (by_cap || fill_kernel) ? (uint32_t)Nc : 0u;
+    b.first_row = 0; b.seed_list_inc = 0; b.row_stride = by_cap ? (uint32_t)Nc : 0u;
     b.zero_base = p;
     b.succ_cnt = carve<uint32_t>(p, Nc); b.inc_cnt = carve<uint32_t>(p, Nc); b.val_cnt = carve<uint32_t>(p, Nc);
     b.inc_sum = carve<unsigned long long>(p, Nc); b.last_inc = carve<unsigned long long>(p, Nc);
@@ -614,12 +593,35 @@ int setup_buffers(am355_ctx* c, uint32_t NA) {
   return AM355_OK;
 }
 
+static void take_counts(am355_ctx* c, const Counts* hc) { c->counts = *hc; c->counts.n_objects += 1; }   // (+ _root)
+
+// Stage 2 of a full replay, behind the decode on the main stream: merge (the decode flags land in the same counter block and are read
+// with the first counters), ev[5] behind it, the verdict of its flags, the counts.
+static int merge_and_take_counts(am355_ctx* c) {
+  Counts* hc = c->h_counts.as<Counts>();
+  merge_run(c->mb, c->ir, hc, c->stream, (c->phase_events || !c->mb.sig) ? c->ev_counts.h : nullptr, c->ev_runs);
+  HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+  if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
+  take_counts(c, hc);
+  return AM355_OK;
+}
+
+// What every replay reports of the state it leaves: the counts, heads, ops and the bytes of the patch tables. The callers add what
+// differs between them: the timings, fast_path.
+static void fill_stats_of_state(am355_ctx* c) {
+  am355_stats& s = c->stats;
+  s.n_changes = c->n_changes; s.n_applied = c->n_applied; s.n_pending = c->n_pending; s.n_actors = (uint32_t)c->actors.size(); s.n_objects = c->counts.n_objects;
+  s.n_heads = (uint32_t)(c->heads.size() / 32); s.n_ops = c->n_ops; s.max_op = c->max_op; s.raw_bytes = c->raw.size();
+  s.n_map_values = c->counts.n_map_emit; s.n_list_elems = c->counts.n_list_ins; s.n_edits = c->counts.n_edits;
+  s.ir_bytes = (uint64_t)c->counts.n_objects * sizeof(am355_ir_object) + (uint64_t)c->counts.n_map_emit * sizeof(am355_ir_map) +
+               ((uint64_t)c->counts.n_erecs + 1) * sizeof(am355_ir_edit);
+}
+
 // Decode + merge + patch IR for the planned changes. `slot_rank` != null: actor tables are the device-interned slots
 // (fast path); null: c->amap holds ranks (general path).
 static int run_device(am355_ctx* c, const std::vector<uint32_t>* slot_rank) {
   hipStream_t st = c->stream;
   size_t np = c->plans.size();
-  uint32_t NA = (uint32_t)c->actors.size();
   // the host-built tables (plans, actor spans, span offsets, slot ranks or actor translation tables) live in one device block so
   // that they travel in ONE host-to-device copy from the pinned staging buffer
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -684,15 +686,7 @@ static int run_device(am355_ctx* c, const std::vector<uint32_t>* slot_rank) {
   HIPCHK(c, hipEventRecord(c->ev[3], st));
   HIPCHK(c, hipEventRecord(c->ev_join, c->stream3));
   HIPCHK(c, hipStreamWaitEvent(st, c->ev_join, 0));
-
-  // ---- stage 2: merge (the decode flags land in the same counter block and are read with the first counters) ----
-  Counts* hc = c->h_counts.as<Counts>();
-  merge_run(c->mb, c->ir, hc, st, (c->phase_events || !c->mb.sig) ? c->ev_counts.h : nullptr, c->ev_runs);
-  HIPCHK(c, hipEventRecord(c->ev[5], st));
-  if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
-  c->counts = *hc;
-  c->counts.n_objects += 1;  // + _root
-  return AM355_OK;
+  return merge_and_take_counts(c);
 }
 
 // In-order fast path with the device-side plan (k_plan): the decode kernels are launched from the device-built plans as soon as
@@ -703,11 +697,8 @@ static int run_device(am355_ctx* c, const std::vector<uint32_t>* slot_rank) {
 struct GeneralOrder { const uint32_t* order; const uint32_t* pass; uint32_t n_applied; hipEvent_t ready; };
 static int run_device_planned(am355_ctx* c, const PlanTotals& tot, uint32_t n_distinct, float* ms_host_plan, const GeneralOrder* go = nullptr) {
   hipStream_t st = c->stream;
-  const bool trace = getenv("AM355_TRACE") != nullptr;
-  auto t_begin = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (trace) fprintf(stderr, "  planned: %-26s +%8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-  };
+  const TraceLap lap("  planned:", 26);
+  const bool trace = lap.on;
   uint32_t n = c->n_changes;
   c->n_ops = tot.n_ops;
   c->n_preds = tot.n_preds;
@@ -808,23 +799,14 @@ static int run_device_planned(am355_ctx* c, const PlanTotals& tot, uint32_t n_di
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_tables, 0));
   }
   lap("tables enqueued");
-  Counts* hc = c->h_counts.as<Counts>();
-  merge_run(c->mb, c->ir, hc, st, (c->phase_events || !c->mb.sig) ? c->ev_counts.h : nullptr, c->ev_runs);
-  HIPCHK(c, hipEventRecord(c->ev[5], st));
-  if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
-  c->counts = *hc;
-  c->counts.n_objects += 1;  // + _root
-  return AM355_OK;
+  return merge_and_take_counts(c);
 }
 
 // Backend.load(bytes) + getPatch: device decode of the document's op columns, then the whole-document patch of the
 // (already canonical) rows. new.js:1695-1750, 1604-1635.
 static int replay_document_stages(am355_ctx* c) {
   auto t_begin = std::chrono::steady_clock::now();
-  const bool trace = getenv("AM355_TRACE") != nullptr;
-  auto lap = [&](const char* what) {
-    if (trace) fprintf(stderr, "replay_document: %-28s +%8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-  };
+  const TraceLap lap("replay_document:", 28, t_begin);
   hipStream_t st = c->stream;
   uint32_t NA = (uint32_t)c->actors.size();
   if (!c->d_plans.ensure(sizeof(ChangePlan)) || !c->d_amap.ensure(4 * (size_t)std::max(NA, 1u)) || !c->d_words.ensure(4 * W_NUM) || !c->h_words.ensure(4 * W_NUM))
@@ -947,15 +929,10 @@ static int replay_document_stages(am355_ctx* c) {
   if (!c->doc_serial && c->h_words.as<uint32_t>()[W_FLAGS_B]) return error_for_flags(c, c->h_words.as<uint32_t>()[W_FLAGS_B], "malformed key column");
   if (hc->flags) return error_for_flags(c, hc->flags, "document rejected");
   c->max_op = c->h_words.as<uint32_t>()[0];
-  c->counts = *hc;
-  c->counts.n_objects += 1;  // + _root
+  take_counts(c, hc);
   auto t_end = std::chrono::steady_clock::now();
   am355_stats& s = c->stats;
-  s.n_changes = c->n_changes; s.n_applied = c->n_changes; s.n_pending = 0; s.n_actors = NA; s.n_objects = c->counts.n_objects;
-  s.n_heads = (uint32_t)(c->heads.size() / 32); s.n_ops = c->n_ops; s.max_op = c->max_op; s.raw_bytes = c->raw.size();
-  s.n_map_values = c->counts.n_map_emit; s.n_list_elems = c->counts.n_list_ins; s.n_edits = c->counts.n_edits;
-  s.ir_bytes = (uint64_t)c->counts.n_objects * sizeof(am355_ir_object) + (uint64_t)c->counts.n_map_emit * sizeof(am355_ir_map) +
-               ((uint64_t)c->counts.n_erecs + 1) * sizeof(am355_ir_edit);
+  fill_stats_of_state(c);
   (void)hipEventElapsedTime(&s.ms_parse, c->ev[0], c->ev[1]);
   (void)hipEventElapsedTime(&s.ms_decode, c->ev[2], c->ev[3]);
   (void)hipEventElapsedTime(&s.ms_merge, c->ev[3], c->ev[4]);
@@ -1063,14 +1040,6 @@ static inline uint64_t key_of_actor(const uint8_t* a, size_t len) {
 static uint32_t rank_of(const am355_ctx* c, const uint8_t* a, size_t len) {
   return table_find(c->res_rank_of, key_of_actor(a, len), [&](uint32_t r) { return c->actors[r].size() == len && memcmp(c->actors[r].data(), a, len) == 0; });
 }
-
-struct ResidentLap {   // AM355_TRACE: the call's milestones on stderr
-  bool on;
-  std::chrono::steady_clock::time_point t0;
-  void operator()(const char* what) const {
-    if (on) fprintf(stderr, "resident: %-30s +%8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  }
-};
 
 // The batch goes to the full replay instead. `fallback` leaves the hash index as it is -- for the sites in front of the first
 // hash_index_add --; `fallback_dirty` drops it: once changes of the batch have entered the hash index it no longer describes the
@@ -1562,7 +1531,7 @@ static int resident_map_verify(am355_ctx* c, uint32_t n_obj, uint32_t n_after, b
 // in front of the host's hashing and says itself whether every row is a plain map row; a batch with other rows is no attempt), its
 // words, and -- unless it declines -- the second half. served: the stored table is the merged one. Writes the context's map table
 // pointers, map counts and counters; runs behind the commit.
-static int resident_map_rows_in_place(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const ResidentLap& lap, bool own_look, bool& served) {
+static int resident_map_rows_in_place(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const TraceLap& lap, bool own_look, bool& served) {
   hipStream_t st = c->stream;
   MergeBufs& b = c->mb;
   MapMergeBufs& mm = rs.mm;
@@ -1611,7 +1580,7 @@ static int resident_map_rows_in_place(am355_ctx* c, const ResidentBatch& rb, Res
 // the context's object count grows and the call is counted.
 // incs: the batch holds counter rows (am355_set_resident_counters): the stored map records take no increments either -- k_mm_rows looks at
 // plain map rows only -- and are declined the same way.
-static int resident_map_half(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const ResidentLap& lap, uint32_t made = 0, bool incs = false) {
+static int resident_map_half(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const TraceLap& lap, uint32_t made = 0, bool incs = false) {
   bool in_place = false;
   if ((made || incs) && rs.map_merge_on) {
     c->n_map_merge_declined++;
@@ -1696,7 +1665,6 @@ static const char* resident_hashes_and_dependencies(am355_ctx* c, ResidentBatch&
 // swap (plans_dev, spans_new, tab_new, actors_new) or copy (amap); rb is spent behind it but for its sizes and flags.
 static void resident_commit(am355_ctx* c, ResidentBatch& rb) {
   const uint32_t K = rb.K, n = rb.n, nb = rb.nb;
-  const uint8_t* hs = c->h_hashes.as<uint8_t>();
   c->hash_index_n = n;
   if (rb.grow) {
     // every host table that is indexed by a rank or holds one: the actors, the clock's actors (below: the clock itself and the span
@@ -1719,15 +1687,7 @@ static void resident_commit(am355_ctx* c, ResidentBatch& rb) {
   for (uint32_t a : rb.new_clock_actors) c->clock_actor.push_back(a);
   c->clock_seq.clear();
   for (uint32_t a : c->clock_actor) c->clock_seq.push_back(rb.clock[a]);
-  {
-    std::vector<const uint8_t*> hv;
-    for (uint32_t i = 0; i < n; i++)
-      if (rb.is_head[i]) hv.push_back(hs + 32 * (size_t)i);
-    std::sort(hv.begin(), hv.end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; });
-    std::vector<uint8_t> heads_new(hv.size() * 32);
-    for (size_t k = 0; k < hv.size(); k++) memcpy(&heads_new[32 * k], hv[k], 32);
-    c->heads.swap(heads_new);
-  }
+  set_heads(c, n, [&](uint32_t i) { return rb.is_head[i] != 0; });
   c->spans.swap(rb.spans_new);
   c->actor_tab_off.swap(rb.tab_new);
   for (uint32_t i = 0; i < nb; i++) { c->applied_change.push_back(K + i); c->applied_op_base.push_back(rb.op_base[i]); }
@@ -1749,7 +1709,7 @@ static void resident_commit(am355_ctx* c, ResidentBatch& rb) {
 // dispatches and their wait otherwise), and what follows from it: the order merged in place (with the map half behind it when plain
 // map rows came beside the list edits), plain map rows only, or neither. Writes the context's order pointers, counts, patch-table
 // flags and counters; sets merged_in_place / maps_only. AM355_OK or an error.
-static int resident_list_verdict(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const ResidentLap& lap, bool& merged_in_place, bool& maps_only) {
+static int resident_list_verdict(am355_ctx* c, const ResidentBatch& rb, ResidentStages& rs, const TraceLap& lap, bool& merged_in_place, bool& maps_only) {
   hipStream_t st = c->stream;
   MergeBufs& b = c->mb;
   uint32_t* hw = c->h_resorder.as<uint32_t>();
@@ -1850,7 +1810,7 @@ static int resident_list_verdict(am355_ctx* c, const ResidentBatch& rb, Resident
 // resident_valid drops before the first write to kept arrays; hashing starts behind the last enqueue and in front of the first
 // wait; the hash index is dropped once changes of the batch have entered it and the batch fails.
 static int replay_resident(am355_ctx* c) {
-  const ResidentLap lap{getenv("AM355_TRACE") != nullptr, std::chrono::steady_clock::now()};
+  const TraceLap lap("resident:", 30);
   const bool trace = lap.on;
   hipStream_t st = c->stream;
   MergeBufs& b = c->mb;
@@ -1934,8 +1894,7 @@ static int replay_resident(am355_ctx* c) {
     merge_run(b, c->ir, hc, st, nullptr, c->ev_runs, true);
     lap("merge_run done");
     if (hc->flags) return error_for_flags(c, hc->flags, "op set rejected");
-    c->counts = *hc;
-    c->counts.n_objects += 1;  // + _root
+    take_counts(c, hc);
     c->pos_valid = false;
     c->ir_stale = false;
   }
@@ -1984,8 +1943,7 @@ int ensure_ir_fresh(am355_ctx* c) {
   Counts* hc = c->h_counts.as<Counts>();
   merge_run(b, c->ir, hc, st, nullptr, c->ev_runs);
   if (hc->flags) { c->staged = c->replayed = false; return error_for_flags(c, hc->flags, "op set rejected"); }
-  c->counts = *hc;
-  c->counts.n_objects += 1;
+  take_counts(c, hc);
   c->ir_stale = false;
   c->ir_fetched = false;
   c->ir_copy_enqueued = 0;
@@ -2022,55 +1980,71 @@ int ensure_ir_fresh(am355_ctx* c) {
   return AM355_OK;
 }
 
-int replay_impl(am355_ctx* c) {
-  if (!c) return AM355_E_ARG;
-  if (!c->staged) return fail(c, AM355_E_STATE, "am355_load_changes must be called first");
-  (void)hipSetDevice(c->device);
-  c->replayed = c->ir_fetched = false;
-  c->ir_copy_enqueued = 0;
-  c->dep_graph_ready = false;
-  c->flags = 0;
-  c->spec_launched = false;
-  c->batch_list_only = false;
-  c->h_tables_were_current = c->h_tables_current;   // (of the state before this replay: replay_resident may find them unchanged)
-  c->h_tables_current = false;
-  if (c->is_document) { c->graph_epoch++; return replay_document(c); }
-  auto t_begin = std::chrono::steady_clock::now();
-  if (c->in_apply && c->keep.want) {
-    // Backend.applyChanges onto the state this context holds: the batch alone (replay_resident), unless it needs the general path
-    c->keep.want = false;
-    const int rr = replay_resident(c);
-    if (rr != RESIDENT_FALLBACK) {
-      if (rr != AM355_OK) return rr;
-      am355_stats& s = c->stats;
-      s.n_changes = c->n_changes; s.n_applied = c->n_applied; s.n_pending = 0; s.n_actors = (uint32_t)c->actors.size(); s.n_objects = c->counts.n_objects;
-      s.n_heads = (uint32_t)(c->heads.size() / 32); s.n_ops = c->n_ops; s.max_op = c->max_op; s.raw_bytes = c->raw.size();
-      s.n_map_values = c->counts.n_map_emit; s.n_list_elems = c->counts.n_list_ins; s.n_edits = c->counts.n_edits;
-      s.ir_bytes = (uint64_t)c->counts.n_objects * sizeof(am355_ir_object) + (uint64_t)c->counts.n_map_emit * sizeof(am355_ir_map) +
-                   ((uint64_t)c->counts.n_erecs + 1) * sizeof(am355_ir_edit);
-      // (no wait here: what the call goes on with -- the delta stage, a fetch -- is enqueued behind the batch on the same stream)
-      s.ms_parse = s.ms_decode = s.ms_merge = s.ms_order = s.ms_hash_stream = s.ms_host_schedule = 0;
-      s.fast_path = 1;
-      s.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-      c->used_fast_path = true;
-      c->device_scheduled = false;
-      c->replayed = true;
-      c->seed_list_inc = c->counts.n_list_inc;
-      resident_mark(c);
-      c->resident_valid = true;
-      return AM355_OK;
-    }
-  }
-  c->keep.want = false;
-  c->graph_epoch++;   // (the applied list is made anew from here on: am355_graph.hip rebuilds its indexes instead of extending them)
-  { int orc = flush_uploads(c); if (!orc) orc = upload_offsets(c); if (orc) return orc; }
-  const bool trace = getenv("AM355_TRACE") != nullptr;
-  auto lap = [&](const char* what) {
-    if (trace) fprintf(stderr, "replay: %-28s +%8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-  };
-  hipStream_t sa = c->stream, sb = c->stream2;
-  uint32_t n = c->n_changes;
-  size_t n1 = std::max<size_t>(n, 1);
+// ---------------------------------------------------------------------------------------------------------
+// Full replay of the staged change log (am355_replay, and am355_apply_changes when the resident path does not serve the batch):
+// replay_impl at the end of this file is the sequence of the phases below, in this order. What stage 1 finds lives in one Stage1 on
+// the stack of the call, handed on by reference (what each phase reads and writes). A phase returns AM355_OK or the error.
+// ---------------------------------------------------------------------------------------------------------
+static constexpr size_t S1_DISTINCT = 64;   // offset of the distinct list in d_s1 / h_s1, behind the flag words
+
+// Each group is written by the phase named above it and read by the later ones.
+// MEMBER ORDER: the closure posted to c->lane (replay_post_hash_stream) runs replay_enqueue_hash_stream on the helper thread: it reads
+// n, n1, d_words, h_words of this struct and the context, and writes lane_rc. `lane_join` is the LAST member, so its destructor -- the
+// wait for the helper -- runs FIRST, in front of the destruction of every other member; replay_impl declares the Stage1 behind
+// everything else the phases use, and every phase reports failure by returning to replay_impl, so on every way out the helper has
+// finished before anything it touches dies. Keep lane_join last, and add nothing the closure touches outside this struct.
+struct Stage1 {
+  // replay_stage1_buffers
+  uint32_t n = 0;
+  size_t n1 = 1;                                     // max(n, 1)
+  uint32_t *d_wa = nullptr, *d_distinct = nullptr;   // carved from d_s1: W_FLAGS_A, W_FAST_A, W_TOTAL_ENTRIES | the distinct actor ids |
+  ChangeBrief* d_briefs = nullptr;                   // one brief per change (their host mirror in h_s1: c->hp_distinct, c->hp_briefs)
+  uint32_t *d_words = nullptr, *h_words = nullptr;   // stream B's words (W_FLAGS_B, W_FAST_B)
+  HostSignals* sig = nullptr;
+  // replay_parse: the merge stage's counter block as sized from the staged bytes, whether the parse kernel clears it
+  size_t counts_bytes = 0;
+  bool counts_cleared = false, fat_changes = false;
+  // replay_intern_and_plan (hash_enqueued: set by replay_post_hash_stream when the helper thread does it; tot: read back through HostSignals)
+  bool hash_enqueued = false, spec_possible = false;
+  PlanTotals tot{};
+  // replay_stage1_verdict (fast: completed by replay_join_hash_stream; ms_host: host planning / scheduling time, stats ms_host_schedule)
+  bool fast = false, planned = false, lineage_schedule = false;
+  std::chrono::steady_clock::time_point t_host0;
+  float ms_host = 0;
+  // replay_optimistic: the run's error, kept until the hash stream confirms or discards the run
+  int opt_rc = AM355_OK;
+  uint32_t opt_flags = 0;
+  std::string opt_err;
+  // replay_post_hash_stream
+  std::atomic<int> lane_rc{AM355_OK};
+  LaneJoin lane_join;   // LAST (see above)
+};
+
+// Backend.applyChanges onto the state this context holds: the batch alone (replay_resident), then the call's statistics and the
+// resident mark. RESIDENT_FALLBACK: the batch needs the full replay.
+static int replay_on_resident_state(am355_ctx* c, std::chrono::steady_clock::time_point t_begin) {
+  const int rr = replay_resident(c);
+  if (rr != AM355_OK) return rr;
+  am355_stats& s = c->stats;
+  fill_stats_of_state(c);
+  // (no wait here: what the call goes on with -- the delta stage, a fetch -- is enqueued behind the batch on the same stream)
+  s.ms_parse = s.ms_decode = s.ms_merge = s.ms_order = s.ms_hash_stream = s.ms_host_schedule = 0;
+  s.fast_path = 1;
+  s.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  c->used_fast_path = true;
+  c->device_scheduled = false;
+  c->replayed = true;
+  c->seed_list_inc = c->counts.n_list_inc;
+  resident_mark(c);
+  c->resident_valid = true;
+  return AM355_OK;
+}
+
+// Phase 1, the buffers of stage 1 and their carve. Reads the staged sizes; grows the context's stage-1 buffers, sets slot_mask /
+// hash_mask / amap_cap / hp_distinct / hp_briefs, fills the pointers of `s`.
+static int replay_stage1_buffers(am355_ctx* c, Stage1& s) {
+  const uint32_t n = s.n = c->n_changes;
+  const size_t n1 = s.n1 = std::max<size_t>(n, 1);
   c->slot_mask = pow2_at_least(4 * (uint64_t)n + 64) - 1;
   c->hash_mask = pow2_at_least(2 * (uint64_t)n + 64) - 1;
   if (c->amap_cap < 16 * n1 + 1024) c->amap_cap = (uint32_t)(16 * n1 + 1024);
@@ -2085,131 +2059,122 @@ int replay_impl(am355_ctx* c) {
   c->have_host_metas = false;
   // what the host reads after stage 1 -- a few flag words, the distinct actor ids, one brief per change -- sits in one device
   // block: one memset clears the words and the distinct counter, one copy brings everything back
-  const size_t s1_distinct = 64, s1_briefs = s1_distinct + ((12 * (size_t)distinct_capacity() + 16 + 63) & ~(size_t)63);
+  const size_t s1_briefs = S1_DISTINCT + ((12 * (size_t)distinct_capacity() + 16 + 63) & ~(size_t)63);
   const size_t s1_bytes = s1_briefs + sizeof(ChangeBrief) * n1;
   if (!c->d_s1.ensure(s1_bytes) || !c->h_s1.ensure(s1_bytes)) return fail(c, AM355_E_NOMEM, "device allocation failed (stage 1)");
-  uint32_t* d_wa = c->d_s1.as<uint32_t>();                        // W_FLAGS_A, W_FAST_A, W_TOTAL_ENTRIES
-  uint32_t* d_distinct = (uint32_t*)(c->d_s1.as<uint8_t>() + s1_distinct);
-  ChangeBrief* d_briefs = (ChangeBrief*)(c->d_s1.as<uint8_t>() + s1_briefs);
-  const uint32_t* h_wa = c->h_s1.as<uint32_t>();
-  c->hp_distinct = (uint32_t*)(c->h_s1.as<uint8_t>() + s1_distinct);
+  s.d_wa = c->d_s1.as<uint32_t>();
+  s.d_distinct = (uint32_t*)(c->d_s1.as<uint8_t>() + S1_DISTINCT);
+  s.d_briefs = (ChangeBrief*)(c->d_s1.as<uint8_t>() + s1_briefs);
+  c->hp_distinct = (uint32_t*)(c->h_s1.as<uint8_t>() + S1_DISTINCT);
   c->hp_briefs = (ChangeBrief*)(c->h_s1.as<uint8_t>() + s1_briefs);
-  uint32_t* d_words = c->d_words.as<uint32_t>();  // stream B's words (W_FLAGS_B, W_FAST_B)
-  uint32_t* h_words = c->h_words.as<uint32_t>();
-  HostSignals* sig = c->h_sig.as<HostSignals>();
-  PlanTotals tot{};
-  static const bool hash_after_parse = []() { const char* e = getenv("AM355_HASH_START"); return !(e && !strcmp(e, "intern")); }();
+  s.d_words = c->d_words.as<uint32_t>();
+  s.h_words = c->h_words.as<uint32_t>();
+  s.sig = c->h_sig.as<HostSignals>();
+  return AM355_OK;
+}
 
-  // ---- stream A: parse. The fills of stage 1 (flag words, actor hash table) depend on nothing of this replay: they run on stream3
-  //      beside the parse kernel instead of in front of the kernels that need them ----
+// Phase 2, stream A: the parse kernel with the fills of stage 1. The fills (flag words, actor hash table) depend on nothing of this
+// replay: the parse kernel's workgroups clear them on their way in -- no second stream, no event wait in front of the next kernel
+// (as memsets on stream3: measured and removed, profiles/r03_ab_stage1.txt). Records ev[0] and ev_parse.
+static int replay_parse(am355_ctx* c, Stage1& s) {
+  hipStream_t sa = c->stream;
   HIPCHK(c, hipEventRecord(c->ev[0], sa));
   // the merge stage's counter block too: its size follows from the op count, which is at most one op per encoded byte for any
   // batch worth hurrying (a run length may claim more: the planned path then clears it in front of the decode as before)
-  const size_t cb = merge_counts_bytes((uint32_t)std::min<size_t>(c->raw.size(), 0x7ffffff0u));
+  s.counts_bytes = merge_counts_bytes((uint32_t)std::min<size_t>(c->raw.size(), 0x7ffffff0u));
   c->counts_zeroed_at = nullptr;
-  const bool counts_too = c->d_counts.ensure(cb);
+  s.counts_cleared = c->d_counts.ensure(s.counts_bytes);
   // (more than 4 KB per change on average: the parse kernel with the wavefront-parallel row / pred counts, k_parse_changes<true>; the
   // headline log's 3.2 KB changes keep the lean kernel -- 20 us against 36 with the bigger LDS footprint, profiles/r05_kernel_table_fat_parse.txt)
-  const bool fat_changes = n && c->raw.size() / n > 4096 && !getenv("AM355_PARSE_LEAN");
-  if (c->inline_fills) {
-    // (cleared by the parse kernel's workgroups on their way in: no second stream, no event wait in front of the next kernel)
-    ParseFills f{};
-    auto add = [&](void* q, size_t bytes, uint32_t v) { f.p[f.n] = (uint32_t*)q; f.n_words[f.n] = (bytes + 3) / 4; f.value[f.n] = v; f.n++; };
-    add(d_words, 4 * W_NUM, 0);
-    add(d_wa, s1_distinct + 16, 0);
-    add(c->d_slots.p, 8 * (size_t)(c->slot_mask + 1), 0);
-    add(c->d_first_idx.p, 4 * (size_t)(c->slot_mask + 1), 0xffffffffu);
-    if (counts_too) add(c->d_counts.p, cb, 0);
-    launch_parse_changes(c->d_arena.as<uint8_t>(), c->d_offsets.as<uint64_t>(), n, c->d_metas.as<ChangeMeta>(), c->d_entries.as<uint32_t>(), f, sa, fat_changes);
-    HIPCHK(c, hipEventRecord(c->ev_parse, sa));
-  } else {
-    launch_parse_changes(c->d_arena.as<uint8_t>(), c->d_offsets.as<uint64_t>(), n, c->d_metas.as<ChangeMeta>(), c->d_entries.as<uint32_t>(), ParseFills{}, sa, fat_changes);
-    HIPCHK(c, hipEventRecord(c->ev_parse, sa));
-    HIPCHK(c, hipMemsetAsync(d_words, 0, 4 * W_NUM, c->stream3));
-    HIPCHK(c, hipMemsetAsync(d_wa, 0, s1_distinct + 16, c->stream3));
-    HIPCHK(c, hipMemsetAsync(c->d_slots.p, 0, 8 * (size_t)(c->slot_mask + 1), c->stream3));
-    HIPCHK(c, hipMemsetAsync(c->d_first_idx.p, 0xff, 4 * (size_t)(c->slot_mask + 1), c->stream3));
-    if (counts_too) HIPCHK(c, hipMemsetAsync(c->d_counts.p, 0, cb, c->stream3));
-    HIPCHK(c, hipEventRecord(c->ev_join, c->stream3));
-    HIPCHK(c, hipStreamWaitEvent(sa, c->ev_join, 0));
-  }
-  if (counts_too) {
+  s.fat_changes = s.n && c->raw.size() / s.n > 4096 && !getenv("AM355_PARSE_LEAN");
+  ParseFills f{};
+  auto add = [&](void* q, size_t bytes, uint32_t v) { f.p[f.n] = (uint32_t*)q; f.n_words[f.n] = (bytes + 3) / 4; f.value[f.n] = v; f.n++; };
+  add(s.d_words, 4 * W_NUM, 0);
+  add(s.d_wa, S1_DISTINCT + 16, 0);
+  add(c->d_slots.p, 8 * (size_t)(c->slot_mask + 1), 0);
+  add(c->d_first_idx.p, 4 * (size_t)(c->slot_mask + 1), 0xffffffffu);
+  if (s.counts_cleared) add(c->d_counts.p, s.counts_bytes, 0);
+  launch_parse_changes(c->d_arena.as<uint8_t>(), c->d_offsets.as<uint64_t>(), s.n, c->d_metas.as<ChangeMeta>(), c->d_entries.as<uint32_t>(), f, sa, s.fat_changes);
+  HIPCHK(c, hipEventRecord(c->ev_parse, sa));
+  if (s.counts_cleared) {
     c->counts_zeroed_at = c->d_counts.p;
-    c->counts_zeroed = cb;
+    c->counts_zeroed = s.counts_bytes;
   }
+  return AM355_OK;
+}
 
-  // ---- stream B: SHA-256 of every change, hash table, dependency resolution; joined at the very end. Its commands are enqueued
-  //      behind the stage-1 kernels of stream A. AM355_HASH_ENQUEUE=early enqueues them right behind the parse launch, which starts
-  //      the SHA kernel ~35 us sooner; measured on the same box (profiles/r03_ab_hash_enqueue.txt) that costs the replay 0.14 ms:
-  //      the kernels between decode and the compaction take 0.25 instead of 0.10 ms with stream B's commands queued first ----
-  auto enqueue_stream_b = [&]() -> int {
-    // (it starts after the parse kernel -- AM355_HASH_START=intern: after the actor kernels --: those grids are as small as the hash
-    // grid, one wave per 64 changes, and the ALU-dense SHA waves would otherwise share their SIMDs and slow them down)
-    HIPCHK(c, hipStreamWaitEvent(sb, hash_after_parse ? c->ev_parse : c->ev[1], 0));
-    if (!c->inline_fills) HIPCHK(c, hipStreamWaitEvent(sb, c->ev_join, 0));  // (its flag words are cleared on stream3)
-    HIPCHK(c, hipEventRecord(c->ev_b0, sb));
-    HIPCHK(c, hipMemsetAsync(c->d_hash_tab.p, 0, 4 * (size_t)(c->hash_mask + 1), sb));
-    HIPCHK(c, hipMemsetAsync(c->d_has_dep.p, 0, n1, sb));
-    launch_hash_changes(c->d_arena.as<uint8_t>(), c->d_offsets.as<uint64_t>(), n, c->d_hashes.as<uint8_t>(), c->d_min_idx.as<uint32_t>(),
-                    c->d_hash_tab.as<uint32_t>(), c->hash_mask, d_words + W_FLAGS_B, sb);
-    launch_deps_resolve(c->d_arena.as<uint8_t>(), c->d_metas.as<ChangeMeta>(), c->d_hashes.as<uint8_t>(), n, c->d_hash_tab.as<uint32_t>(), c->hash_mask,
-                    c->d_min_idx.as<uint32_t>(), c->d_has_dep.as<uint8_t>(), d_words + W_FAST_B, c->d_dep_idx.as<uint32_t>(), c->d_self_idx.as<uint32_t>(), sb);
-    HIPCHK(c, hipMemcpyAsync(c->h_hashes.p, c->d_hashes.p, 32 * (size_t)n, hipMemcpyDeviceToHost, sb));
-    HIPCHK(c, hipMemcpyAsync(c->h_has_dep.p, c->d_has_dep.p, n, hipMemcpyDeviceToHost, sb));
-    HIPCHK(c, hipMemcpyAsync(h_words + W_FLAGS_B, d_words + W_FLAGS_B, 8, hipMemcpyDeviceToHost, sb));
-    HIPCHK(c, hipEventRecord(c->ev_b1, sb));
-    return AM355_OK;
-  };
-  static const bool enqueue_early = []() { const char* e = getenv("AM355_HASH_ENQUEUE"); return e && !strcmp(e, "early"); }();
-  // AM355_HASH_ENQUEUE=main: by the calling thread, behind the stage-1 launches (rounds 2-4). Default: by the helper thread, beside them.
-  static const bool enqueue_thread = AM355_STREAMS_ORDER_ACROSS_THREADS && []() { const char* e = getenv("AM355_HASH_ENQUEUE"); return !e || !strcmp(e, "thread"); }();
-  std::atomic<int> lane_rc{AM355_OK};
-  struct LaneJoin {   // (whatever way this function is left, the helper is not enqueueing into the context any more)
-    AsyncLane* l = nullptr;
-    ~LaneJoin() { if (l) l->wait(); }
-  } lane_join;
-  bool b_enqueued = false;
-  if (hash_after_parse && enqueue_early) { int rb = enqueue_stream_b(); if (rb) return rb; b_enqueued = true; }
-  else if (hash_after_parse && enqueue_thread && n >= 512) {
-    if (!c->lane) c->lane.reset(new AsyncLane);
-    c->lane->post([&]() { (void)hipSetDevice(c->device); lane_rc.store(enqueue_stream_b()); });
-    lane_join.l = c->lane.get();
-    b_enqueued = true;
-  }
-  exclusive_scan_u32(c->d_entries.as<uint32_t>(), c->d_amap_base.as<uint32_t>(), n, d_wa + W_TOTAL_ENTRIES, c->d_scan1.p, sa);
-  // (AM355_SPEC_DECODE=0: the decode kernels wait for the host to read the totals, as in rounds 2-4)
-  static const bool spec_env = []() { const char* e = getenv("AM355_SPEC_DECODE"); return !(e && *e == '0'); }();
-  const bool spec_possible = spec_env && n && c->inline_fills && counts_too && hash_after_parse && !getenv("AM355_HOST_PLAN") && !(c->in_apply && c->graph_mode != 0) &&
-                             c->d_plan_totals.ensure(sizeof(PlanTotals));
+// Phase 3, stream B: SHA-256 of every change, hash table, dependency resolution; joined by replay_join_hash_stream. Its commands are
+// enqueued behind the stage-1 launches of stream A, by the calling thread or beside them by the helper thread (replay_post_hash_stream).
+// Right behind the parse launch instead starts the SHA kernel ~35 us sooner and costs the replay 0.14 ms: the kernels between decode
+// and the compaction take 0.25 instead of 0.10 ms with stream B's commands queued first (measured and removed,
+// profiles/r03_ab_hash_enqueue.txt). Reads of `s` only what replay_stage1_buffers wrote.
+static int replay_enqueue_hash_stream(am355_ctx* c, const Stage1& s) {
+  hipStream_t sb = c->stream2;
+  const uint32_t n = s.n;
+  // (it starts after the parse kernel -- after the actor kernels: 0.03 ms slower, profiles/r03_ab_hash_enqueue.txt --: those grids are as
+  // small as the hash grid, one wave per 64 changes, and the ALU-dense SHA waves would otherwise share their SIMDs and slow them down)
+  HIPCHK(c, hipStreamWaitEvent(sb, c->ev_parse, 0));
+  HIPCHK(c, hipEventRecord(c->ev_b0, sb));
+  HIPCHK(c, hipMemsetAsync(c->d_hash_tab.p, 0, 4 * (size_t)(c->hash_mask + 1), sb));
+  HIPCHK(c, hipMemsetAsync(c->d_has_dep.p, 0, s.n1, sb));
+  launch_hash_changes(c->d_arena.as<uint8_t>(), c->d_offsets.as<uint64_t>(), n, c->d_hashes.as<uint8_t>(), c->d_min_idx.as<uint32_t>(),
+                  c->d_hash_tab.as<uint32_t>(), c->hash_mask, s.d_words + W_FLAGS_B, sb);
+  launch_deps_resolve(c->d_arena.as<uint8_t>(), c->d_metas.as<ChangeMeta>(), c->d_hashes.as<uint8_t>(), n, c->d_hash_tab.as<uint32_t>(), c->hash_mask,
+                  c->d_min_idx.as<uint32_t>(), c->d_has_dep.as<uint8_t>(), s.d_words + W_FAST_B, c->d_dep_idx.as<uint32_t>(), c->d_self_idx.as<uint32_t>(), sb);
+  HIPCHK(c, hipMemcpyAsync(c->h_hashes.p, c->d_hashes.p, 32 * (size_t)n, hipMemcpyDeviceToHost, sb));
+  HIPCHK(c, hipMemcpyAsync(c->h_has_dep.p, c->d_has_dep.p, n, hipMemcpyDeviceToHost, sb));
+  HIPCHK(c, hipMemcpyAsync(s.h_words + W_FLAGS_B, s.d_words + W_FLAGS_B, 8, hipMemcpyDeviceToHost, sb));
+  HIPCHK(c, hipEventRecord(c->ev_b1, sb));
+  return AM355_OK;
+}
+
+// From 512 changes on, where streams keep their order across threads (the device, not the emulator), the helper thread makes stream
+// B's calls beside the calling thread's stage-1 launches; otherwise replay_intern_and_plan makes them behind its own launches.
+static void replay_post_hash_stream(am355_ctx* c, Stage1& s) {
+  if (!(AM355_STREAMS_ORDER_ACROSS_THREADS && s.n >= 512)) return;
+  if (!c->lane) c->lane.reset(new AsyncLane);
+  c->lane->post([c, &s]() { (void)hipSetDevice(c->device); s.lane_rc.store(replay_enqueue_hash_stream(c, s)); });
+  s.lane_join.l = c->lane.get();
+  s.hash_enqueued = true;
+}
+
+// Phase 4, stream A: entry scan, actor interning, the device half of the plan and, behind the plan kernel, the speculative decode;
+// then the wait for the plan's totals. Once more from the interning when the staging buffer for actor tables was too small.
+static int replay_intern_and_plan(am355_ctx* c, Stage1& s, const TraceLap& lap) {
+  hipStream_t sa = c->stream;
+  const uint32_t n = s.n;
+  exclusive_scan_u32(c->d_entries.as<uint32_t>(), c->d_amap_base.as<uint32_t>(), n, s.d_wa + W_TOTAL_ENTRIES, c->d_scan1.p, sa);
+  s.spec_possible = n && s.counts_cleared && !getenv("AM355_HOST_PLAN") && !(c->in_apply && c->graph_mode != 0) && c->d_plan_totals.ensure(sizeof(PlanTotals));
   for (int attempt = 0;; attempt++) {
     if (attempt) {
       HIPCHK(c, hipMemsetAsync(c->d_slots.p, 0, 8 * (size_t)(c->slot_mask + 1), sa));
       HIPCHK(c, hipMemsetAsync(c->d_first_idx.p, 0xff, 4 * (size_t)(c->slot_mask + 1), sa));
-      HIPCHK(c, hipMemsetAsync(d_distinct, 0, 4, sa));
+      HIPCHK(c, hipMemsetAsync(s.d_distinct, 0, 4, sa));
     }
     launch_actor_intern(c->d_arena.as<uint8_t>(), c->d_metas.as<ChangeMeta>(), n, c->d_amap_base.as<uint32_t>(), c->d_amap_prov.as<uint32_t>(), c->amap_cap,
-                        c->d_slots.as<unsigned long long>(), c->slot_mask, c->d_first_idx.as<uint32_t>(), d_wa + W_FLAGS_A, d_wa + W_FAST_A,
-                        d_distinct, c->d_rank_ids.p, d_briefs, c->d_slot_rank.as<uint32_t>(), c->d_plan_sums.as<unsigned long long>(), d_wa + 8, sa, c->hp_briefs);
+                        c->d_slots.as<unsigned long long>(), c->slot_mask, c->d_first_idx.as<uint32_t>(), s.d_wa + W_FLAGS_A, s.d_wa + W_FAST_A,
+                        s.d_distinct, c->d_rank_ids.p, s.d_briefs, c->d_slot_rank.as<uint32_t>(), c->d_plan_sums.as<unsigned long long>(), s.d_wa + 8, sa, c->hp_briefs);
     // device half of the in-order plan (actor ranks, per-change bases, decoder classes): the decode kernels start from it
     // (its totals, and the stage-1 words the host decides on, reach the host through HostSignals: no copy, no blocking wait)
     c->sig_seq++;
-    launch_plan(d_briefs, n, d_distinct, c->d_slot_rank.as<uint32_t>(), c->slot_mask, c->d_plan_sums.as<unsigned long long>(), c->d_plans.as<ChangePlan>(),
-                c->d_plans.as<ChangePlan>() + n1, d_wa, d_wa + 8, sig, c->sig_seq, sa, spec_possible ? c->d_plan_totals.as<PlanTotals>() : nullptr,
+    launch_plan(s.d_briefs, n, s.d_distinct, c->d_slot_rank.as<uint32_t>(), c->slot_mask, c->d_plan_sums.as<unsigned long long>(), c->d_plans.as<ChangePlan>(),
+                c->d_plans.as<ChangePlan>() + s.n1, s.d_wa, s.d_wa + 8, s.sig, c->sig_seq, sa, s.spec_possible ? c->d_plan_totals.as<PlanTotals>() : nullptr,
                 c->h_s1.as<uint32_t>());
     // the host's own half of the plan needs a 32-byte digest per change and the handful of distinct actor ids: k_actor_check and
     // k_plan_apply write them into the host's pinned mirror themselves (rounds 2-4: an event record in this stream, a copy on
     // stream4 and a blocking wait for it -- the wait was the longest item between the plan and k_resolve)
-    const bool want_large_spec = spec_possible && attempt == 0 && c->hint_large != 0;
+    const bool want_large_spec = s.spec_possible && attempt == 0 && c->hint_large != 0;
     if (want_large_spec) HIPCHK(c, hipEventRecord(c->ev_plan, sa));  // (the large class decodes on stream3, ordered behind the plan kernel)
-    if (spec_possible && attempt == 0) {
+    if (s.spec_possible && attempt == 0) {
       // the decode kernels of the wave classes right behind the plan kernel, before the host knows the totals (decode_gate_open,
-      // am355_internal.h): rows carved for a capacity -- the context's previous in-order replay, or one row per four encoded bytes
+      // am355_internal.h): rows carved for a capacity -- the context's previous in-order replay, or one row per two encoded bytes
+      // (the decode kernels waiting for the host to read the totals, as in rounds 2-4: measured and removed, profiles/r05_ab_libs.txt)
       const uint64_t est = c->raw.size() / 2 + 1024;
       c->spec_cap_ops = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c->hint_ops, est), 0x7ffffff0u);
       c->spec_cap_preds = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c->hint_preds, est), 0x7ffffff0u);
       // (the merge stage's counter block, cleared by the parse kernel above, must not move when the real totals arrive)
-      if (trace) fprintf(stderr, "replay: speculative decode: cap %u ops / %u preds (counter block %zu of %zu bytes)\n", c->spec_cap_ops, c->spec_cap_preds, merge_counts_bytes(c->spec_cap_ops), cb);
-      if (merge_counts_bytes(c->spec_cap_ops) <= cb && carve_cols(c, c->spec_cap_ops, c->spec_cap_preds, true) == AM355_OK) {
+      if (lap.on) fprintf(stderr, "replay: speculative decode: cap %u ops / %u preds (counter block %zu of %zu bytes)\n", c->spec_cap_ops, c->spec_cap_preds, merge_counts_bytes(c->spec_cap_ops), s.counts_bytes);
+      if (merge_counts_bytes(c->spec_cap_ops) <= s.counts_bytes && carve_cols(c, c->spec_cap_ops, c->spec_cap_preds, true) == AM355_OK) {
         canary_arm();
         if (c->phase_events) { HIPCHK(c, hipEventRecord(c->ev[1], sa)); HIPCHK(c, hipEventRecord(c->ev[2], sa)); }
         if (want_large_spec) HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_plan, 0));
@@ -2221,232 +2186,266 @@ int replay_impl(am355_ctx* c) {
         c->spec_launched = true;
       }
     }
-    if ((c->phase_events && !c->spec_launched) || !hash_after_parse) HIPCHK(c, hipEventRecord(c->ev[1], sa));
-    if (attempt == 0 && !b_enqueued) { int rb = enqueue_stream_b(); if (rb) return rb; b_enqueued = true; }
+    if (c->phase_events && !c->spec_launched) HIPCHK(c, hipEventRecord(c->ev[1], sa));
+    if (attempt == 0 && !s.hash_enqueued) { int rb = replay_enqueue_hash_stream(c, s); if (rb) return rb; s.hash_enqueued = true; }
     lap("stage 1 enqueued");
-    if (!wait_host_signal(&sig->plan_seq, c->sig_seq, sa)) {
-      (void)hipStreamSynchronize(sb);
+    if (!wait_host_signal(&s.sig->plan_seq, c->sig_seq, sa)) {
+      (void)hipStreamSynchronize(c->stream2);
       (void)hipStreamSynchronize(c->stream3);
       return fail(c, AM355_E_DEVICE, "the device did not report the plan of this replay (%s)", hipGetErrorString(hipGetLastError()));
     }
-    memcpy(&tot, (const void*)&sig->plan, sizeof tot);
+    memcpy(&s.tot, (const void*)&s.sig->plan, sizeof s.tot);
     lap("stage 1 totals read");
-    if (!(tot.fast_a & FF_CAPACITY) || attempt) break;
+    if (!(s.tot.fast_a & FF_CAPACITY) || attempt) break;
     c->spec_launched = false;  // (the decode kernels behind the first plan saw its capacity flag and did nothing; the second plan gets an ordinary launch)
     // the staging buffer for actor tables was too small: grow to the measured total and redo the interning
-    c->amap_cap = tot.total_entries + 1024;
+    c->amap_cap = s.tot.total_entries + 1024;
     if (!c->d_amap_prov.ensure(4 * (size_t)c->amap_cap)) return fail(c, AM355_E_NOMEM, "device allocation failed (actor tables)");
-    HIPCHK(c, hipMemsetAsync(d_wa + W_FAST_A, 0, 4, sa));
-    HIPCHK(c, hipMemsetAsync(d_wa + 8, 0, 32, sa));  // (plan words)
-  }
-
-  // ---- host: flags, in-order plan ----
-  auto t_h0 = std::chrono::steady_clock::now();
-  float ms_host = 0;
-  int rc = AM355_OK;
-  // (tot.flags_a: validity flags of the stage-1 kernels OR'ed with those of every change; k_plan saw all the digests)
-  if (tot.flags_a) { (void)hipStreamSynchronize(sa); (void)hipStreamSynchronize(sb); return error_for_flags(c, tot.flags_a, "malformed change"); }
-  c->has_unknown_cols = tot.reserved[0] != 0;
-  bool fast = tot.fast_a == 0;
-  const bool lineage_schedule = c->in_apply && c->graph_mode != 0;  // (a lineage that began with Backend.load: the host's round-by-round scheduler, see schedule())
-  if (lineage_schedule) fast = false;
-  if (tot.n_distinct > distinct_capacity()) fast = false;  // thousands of actors: the general path interns them on the host
-  const bool planned = !tot.fallback && !getenv("AM355_HOST_PLAN");
-  std::vector<uint32_t> slot_rank;
-  int opt_rc = AM355_OK;
-  uint32_t opt_flags = 0;
-  std::string opt_err;
-  if (fast && planned) {
-    float ms_plan = 0;
-    opt_rc = run_device_planned(c, tot, tot.n_distinct, &ms_plan);  // optimistic: confirmed (or discarded) when stream B is joined
-    ms_host += ms_plan;  // (host planning time; it runs beside the decode kernels)
-    // (measured and taken out again, profiles/r05_ab_libs.txt: starting the copy of the record tables to the host right here, beside the
-    // join of the hash stream, instead of in am355_fetch_ir -- no gain for the host-to-host time within the spread of the runs, and a
-    // caller that replays without fetching pays 0.1 ms for 5 MB it did not ask for)
-    lap("run_device (device plan) done");
-    opt_flags = c->flags;
-    opt_err = c->err;
-  } else {
-    if (tot.fallback) {  // (k_plan stopped before it looked at the changes: their flags come from the digests)
-      const ChangeBrief* br = c->hp_briefs;
-      uint32_t dev_flags = 0;
-      c->has_unknown_cols = false;
-      for (uint32_t i = 0; i < n; i++) {
-        dev_flags |= br[i].flags_fits & 0x1fffffffu;
-        if (br[i].flags_fits & 0x20000000u) c->has_unknown_cols = true;
-      }
-      if (dev_flags) { (void)hipStreamSynchronize(sa); (void)hipStreamSynchronize(sb); return error_for_flags(c, dev_flags, "malformed change"); }
-    }
-    if (fast) {
-      opt_rc = plan_fast(c, slot_rank);
-      ms_host += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_h0).count();
-      lap("plan_fast done");
-      if (opt_rc == AM355_OK) opt_rc = run_device(c, &slot_rank);  // optimistic: confirmed (or discarded) when stream B is joined
-      lap("run_device done");
-      opt_flags = c->flags;
-      opt_err = c->err;
-    }
-  }
-  // ---- join stream B ----
-  if (lane_join.l) { lane_join.l->wait(); lane_join.l = nullptr; if (lane_rc.load()) return lane_rc.load(); }
-  HIPCHK(c, hipEventSynchronize(c->ev_b1));
-  lap("hash stream joined");
-  if (h_words[W_FLAGS_B]) return error_for_flags(c, h_words[W_FLAGS_B], "checksum does not match data");
-  if (fast && h_words[W_FAST_B]) fast = false;
-  if (fast) {
-    if (opt_rc != AM355_OK) { c->flags = opt_flags; c->err = opt_err; return opt_rc; }
-    // heads: changes nobody depends on, sorted (new.js:1582-1583, 1593)
-    auto t0 = std::chrono::steady_clock::now();
-    const uint8_t* hs = c->h_hashes.as<uint8_t>();
-    const uint8_t* dep = c->h_has_dep.as<uint8_t>();
-    std::vector<const uint8_t*> heads;
-    for (uint32_t i = 0; i < n; i++)
-      if (!dep[i]) heads.push_back(hs + 32 * (size_t)i);
-    std::sort(heads.begin(), heads.end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; });
-    c->heads.resize(heads.size() * 32);
-    for (size_t i = 0; i < heads.size(); i++) memcpy(&c->heads[32 * i], heads[i], 32);
-    ms_host += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  } else {
-    // ---- general path (any delivery order, duplicates, missing dependencies) ----
-    c->flags = 0;
-    c->ir_copy_enqueued = 0;   // (tables of a discarded optimistic run may be on their way: what am355_fetch_ir hands out is enqueued behind the new ones)
-    // the device's actor tables, when its list of distinct ids holds them all (else the host interns)
-    const bool dev_actors = tot.n_distinct <= distinct_capacity() && !(tot.fast_a & FF_CAPACITY) && tot.total_entries <= c->amap_cap;
-    bool served = false;
-    const bool host_schedule = getenv("AM355_HOST_SCHEDULE") != nullptr || lineage_schedule;  // (A/B and tests: the host's scheduler for every batch)
-    if (dev_actors && planned && !host_schedule && n > 0) {
-      // The scheduler runs on the device (am355_sched.hip): pass numbers by relaxation over the dependency indexes stream B resolved,
-      // application order by a stable sort, the decode plans in that order. The host reads the totals from the pinned words, launches
-      // the decode kernels from the device-built plans and does its own half (sequence numbers, clock, span tables) beside them, as
-      // on the in-order path.
-      if (!c->d_sched.ensure(sched_bytes(n, c->slot_mask)) || !c->h_sched.ensure(13 * (size_t)n1 + 64)) return fail(c, AM355_E_NOMEM, "device allocation failed (scheduler)");
-      SchedBufs sbuf;
-      sched_bind(sbuf, c->d_sched.p, n, c->slot_mask);
-      canary_arm();
-      c->sig_seq++;
-      uint32_t* d_order = nullptr;
-      launch_sched_general(c->d_metas.as<ChangeMeta>(), d_briefs, n, c->d_dep_idx.as<uint32_t>(), c->d_self_idx.as<uint32_t>(), c->d_amap_prov.as<uint32_t>(),
-                           c->d_amap_base.as<uint32_t>(), c->amap_cap, c->d_slot_rank.as<uint32_t>(), c->slot_mask, sbuf, &d_order, c->d_plans.as<ChangePlan>(),
-                           c->d_plans.as<ChangePlan>() + n1, d_wa, d_distinct, sig, c->sig_seq, sa);
-      // what the host's half needs: order | pass | first copies | head marks -- on the copy stream, behind the scheduler
-      uint32_t* h_order = c->h_sched.as<uint32_t>();
-      uint32_t *h_pass = h_order + n1, *h_self = h_pass + n1;
-      uint8_t* h_is_head = (uint8_t*)(h_self + n1);
-      HIPCHK(c, hipEventRecord(c->ev_plan, sa));
-      HIPCHK(c, hipStreamWaitEvent(c->stream4, c->ev_plan, 0));
-      HIPCHK(c, hipMemcpyAsync(h_order, d_order, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream4));
-      HIPCHK(c, hipMemcpyAsync(h_pass, sbuf.pass, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream4));
-      HIPCHK(c, hipMemcpyAsync(h_self, c->d_self_idx.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream4));
-      HIPCHK(c, hipMemcpyAsync(h_is_head, sbuf.is_head, (size_t)n, hipMemcpyDeviceToHost, c->stream4));
-      HIPCHK(c, hipEventRecord(c->ev_sched, c->stream4));
-      if (!wait_host_signal(&sig->plan_seq, c->sig_seq, sa)) {
-        (void)hipStreamSynchronize(c->stream4);
-        return fail(c, AM355_E_DEVICE, "the device did not report the schedule of this replay (%s)", hipGetErrorString(hipGetLastError()));
-      }
-      PlanTotals gen{};
-      memcpy(&gen, (const void*)&sig->plan, sizeof gen);
-      lap("device schedule read");
-      // the relaxation ran out of sweeps, sums beyond 32 bits, or an actor named before its first change: the host's scheduler decides
-      // (and raises the exact flags of an invalid batch)
-      if (!gen.reserved[3] && !gen.flags_a && !gen.fallback) {
-        GeneralOrder go{h_order, h_pass, gen.reserved[1], c->ev_sched};
-        float ms_plan = 0;
-        rc = run_device_planned(c, gen, tot.n_distinct, &ms_plan, &go);
-        ms_host += ms_plan;
-        if (rc) return rc;
-        auto t0 = std::chrono::steady_clock::now();
-        // what stays queued: the changes of which no copy is ever applied (new.js:1566, 1866)
-        // (copies of one change: whichever copy became ready first was applied, the others were dropped as duplicates then)
-        c->pending_change.clear();
-        std::vector<uint8_t> group_applied(n, 0);
-        for (uint32_t ci = 0; ci < n; ci++)
-          if (h_pass[ci] != SCHED_NEVER) group_applied[h_self[ci] < n ? h_self[ci] : ci] = 1;
-        for (uint32_t ci = 0; ci < n; ci++)
-          if (!group_applied[h_self[ci] < n ? h_self[ci] : ci]) c->pending_change.push_back(ci);
-        c->n_pending = (uint32_t)c->pending_change.size();
-        const uint8_t* hs = c->h_hashes.as<uint8_t>();
-        std::vector<const uint8_t*> heads;
-        for (uint32_t i = 0; i < n; i++)
-          if (h_is_head[i]) heads.push_back(hs + 32 * (size_t)i);
-        std::sort(heads.begin(), heads.end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; });
-        c->heads.resize(heads.size() * 32);
-        for (size_t i = 0; i < heads.size(); i++) memcpy(&c->heads[32 * i], heads[i], 32);
-        ms_host += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        served = true;
-      } else {
-        (void)hipStreamSynchronize(c->stream4);
-      }
-    }
-    if (!served) {
-      // exact scheduling on the host (thousands of actors, pathological dependency chains, and every batch the reference rejects:
-      // the flags it raises are the host's), then decode / merge of exactly the applied changes
-      size_t dep_words = c->raw.size() / 32 + 2;
-      if (!c->h_dep_idx.ensure(4 * dep_words) || !c->h_self_idx.ensure(4 * n1)) return fail(c, AM355_E_NOMEM, "host allocation failed");
-      HIPCHK(c, hipMemcpyAsync(c->h_metas.p, c->d_metas.p, sizeof(ChangeMeta) * n, hipMemcpyDeviceToHost, sa));
-      HIPCHK(c, hipMemcpyAsync(c->h_dep_idx.p, c->d_dep_idx.p, 4 * dep_words, hipMemcpyDeviceToHost, sa));  // (stream B has been joined)
-      HIPCHK(c, hipMemcpyAsync(c->h_self_idx.p, c->d_self_idx.p, 4 * (size_t)n, hipMemcpyDeviceToHost, sa));
-      if (dev_actors) {
-        if (!c->h_amap.ensure(4 * ((size_t)tot.total_entries + 1)) || !c->h_amap_base.ensure(4 * (n1 + 1))) return fail(c, AM355_E_NOMEM, "host allocation failed");
-        HIPCHK(c, hipMemcpyAsync(c->h_amap.p, c->d_amap_prov.p, 4 * (size_t)tot.total_entries, hipMemcpyDeviceToHost, sa));
-        HIPCHK(c, hipMemcpyAsync(c->h_amap_base.p, c->d_amap_base.p, 4 * (size_t)n, hipMemcpyDeviceToHost, sa));
-      }
-      HIPCHK(c, hipStreamSynchronize(sa));
-      if (dev_actors) c->h_amap_base.as<uint32_t>()[n] = tot.total_entries;
-      auto t0 = std::chrono::steady_clock::now();
-      rc = schedule(c, dev_actors ? c->h_amap.as<uint32_t>() : nullptr, dev_actors ? c->h_amap_base.as<uint32_t>() : nullptr);
-      ms_host += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      if (rc) return rc;
-      rc = run_device(c, nullptr);
-      if (rc) return rc;
-    }
-    c->device_scheduled = served;
-  }
-  c->used_fast_path = fast;
-  lap("end");
-  auto t_end = std::chrono::steady_clock::now();
-
-  am355_stats& s = c->stats;
-  uint32_t NA = (uint32_t)c->actors.size();
-  s.n_changes = n; s.n_applied = c->n_applied; s.n_pending = c->n_pending; s.n_actors = NA; s.n_objects = c->counts.n_objects;
-  s.n_heads = (uint32_t)(c->heads.size() / 32); s.n_ops = c->n_ops; s.max_op = c->max_op; s.raw_bytes = c->raw.size();
-  s.n_map_values = c->counts.n_map_emit; s.n_list_elems = c->counts.n_list_ins; s.n_edits = c->counts.n_edits;
-  s.ir_bytes = (uint64_t)c->counts.n_objects * sizeof(am355_ir_object) + (uint64_t)c->counts.n_map_emit * sizeof(am355_ir_map) +
-               ((uint64_t)c->counts.n_erecs + 1) * sizeof(am355_ir_edit);
-  // (the last kernel has signalled its counters; its remaining workgroups retire within microseconds: poll, do not block)
-  while (hipEventQuery(c->ev[5]) == hipErrorNotReady) {}
-  s.ms_parse = s.ms_decode = s.ms_merge = s.ms_order = 0;
-  if (c->phase_events) {
-    (void)hipEventElapsedTime(&s.ms_parse, c->ev[0], c->ev[1]);
-    (void)hipEventElapsedTime(&s.ms_decode, c->ev[2], c->ev[3]);
-  }
-  if (c->n_ops && c->phase_events) {  // (ev_counts: after resolve / emit / compaction, before the ordering kernels)
-    (void)hipEventElapsedTime(&s.ms_merge, c->ev[3], c->ev_counts);
-    (void)hipEventElapsedTime(&s.ms_order, c->ev_counts, c->ev[5]);
-  }
-  (void)hipEventElapsedTime(&s.ms_hash_stream, c->ev_b0, c->ev_b1);  // hash stream (SHA-256 + dependency resolution), overlapped
-  s.ms_host_schedule = ms_host;
-  s.fast_path = fast ? 1 : (c->device_scheduled ? 2 : 0);
-  s.ms_total = std::chrono::duration<float, std::milli>(t_end - t_begin).count();
-  c->replayed = true;
-  // what a later am355_apply_changes may keep (replay_resident): every staged change applied, in staged order, rows carved for a capacity
-  c->seed_list_inc = c->counts.n_list_inc;
-  c->res_dep_base = n;
-  c->res_dep_first.clear();
-  c->res_dep_index.clear();
-  c->hash_index_n = 0;
-  c->res_rank_of.clear();
-  c->res_rank_n = 0;
-  c->res_actor_memo.clear();
-  c->resident_valid = fast && c->in_apply && c->shard_world == 1 && c->mb.row_stride != 0 && !c->has_unknown_cols;
-  if (c->resident_valid) resident_mark(c);
-  if (!c->in_apply) {  // (one call of Backend.loadChanges: its scheduling passes are the op streams)
-    c->stream_breaks = c->pass_first_row;
-    c->breaks_exact = true;
-    c->children_hazard = false;
-    c->no_history = false;
-    c->doc_rows_known = false;
-    c->graph_mode = 0;
+    HIPCHK(c, hipMemsetAsync(s.d_wa + W_FAST_A, 0, 4, sa));
+    HIPCHK(c, hipMemsetAsync(s.d_wa + 8, 0, 32, sa));  // (plan words)
   }
   return AM355_OK;
 }
 
+// Phase 5, the verdict of stage 1 on the host: the validity flags, whether the in-order run may be tried (fast), whether the device's
+// plan serves (planned), whether the lineage needs the host's round-by-round scheduler.
+static int replay_stage1_verdict(am355_ctx* c, Stage1& s) {
+  const PlanTotals& tot = s.tot;
+  s.t_host0 = std::chrono::steady_clock::now();
+  // (tot.flags_a: validity flags of the stage-1 kernels OR'ed with those of every change; k_plan saw all the digests)
+  if (tot.flags_a) { (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->stream2); return error_for_flags(c, tot.flags_a, "malformed change"); }
+  c->has_unknown_cols = tot.reserved[0] != 0;
+  s.fast = tot.fast_a == 0;
+  s.lineage_schedule = c->in_apply && c->graph_mode != 0;  // (a lineage that began with Backend.load: the host's round-by-round scheduler, see schedule())
+  if (s.lineage_schedule) s.fast = false;
+  if (tot.n_distinct > distinct_capacity()) s.fast = false;  // thousands of actors: the general path interns them on the host
+  s.planned = !tot.fallback && !getenv("AM355_HOST_PLAN");
+  if (tot.fallback) {  // (k_plan stopped before it looked at the changes: their flags come from the digests)
+    const ChangeBrief* br = c->hp_briefs;
+    uint32_t dev_flags = 0;
+    c->has_unknown_cols = false;
+    for (uint32_t i = 0; i < s.n; i++) {
+      dev_flags |= br[i].flags_fits & 0x1fffffffu;
+      if (br[i].flags_fits & 0x20000000u) c->has_unknown_cols = true;
+    }
+    if (dev_flags) { (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->stream2); return error_for_flags(c, dev_flags, "malformed change"); }
+  }
+  return AM355_OK;
+}
+
+// Phase 6, the optimistic in-order run, when stage 1 allows it: decode + merge from the device's plan (run_device_planned) or from the
+// host's (plan_fast, run_device). Confirmed or discarded when stream B is joined; an error is kept in `s` until then.
+static void replay_optimistic(am355_ctx* c, Stage1& s, const TraceLap& lap) {
+  if (!s.fast) return;
+  if (s.planned) {
+    float ms_plan = 0;
+    s.opt_rc = run_device_planned(c, s.tot, s.tot.n_distinct, &ms_plan);
+    s.ms_host += ms_plan;  // (host planning time; it runs beside the decode kernels)
+    // (measured and taken out again, profiles/r05_ab_libs.txt: starting the copy of the record tables to the host right here, beside the
+    // join of the hash stream, instead of in am355_fetch_ir -- no gain for the host-to-host time within the spread of the runs, and a
+    // caller that replays without fetching pays 0.1 ms for 5 MB it did not ask for)
+    lap("run_device (device plan) done");
+  } else {
+    std::vector<uint32_t> slot_rank;
+    s.opt_rc = plan_fast(c, slot_rank);
+    s.ms_host += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - s.t_host0).count();
+    lap("plan_fast done");
+    if (s.opt_rc == AM355_OK) s.opt_rc = run_device(c, &slot_rank);
+    lap("run_device done");
+  }
+  s.opt_flags = c->flags;
+  s.opt_err = c->err;
+}
+
+// Phase 7, the join of the hash stream: the helper thread first, then the stream's last event. Its words decide the checksum verdict
+// and whether the in-order run stands (no late or missing dependency, no duplicate).
+static int replay_join_hash_stream(am355_ctx* c, Stage1& s, const TraceLap& lap) {
+  if (s.lane_join.l) { s.lane_join.l->wait(); s.lane_join.l = nullptr; if (s.lane_rc.load()) return s.lane_rc.load(); }
+  HIPCHK(c, hipEventSynchronize(c->ev_b1));
+  lap("hash stream joined");
+  if (s.h_words[W_FLAGS_B]) return error_for_flags(c, s.h_words[W_FLAGS_B], "checksum does not match data");
+  if (s.fast && s.h_words[W_FAST_B]) s.fast = false;
+  return AM355_OK;
+}
+
+// The in-order run stands: its error, if it had one, is the call's; the heads are the changes nobody depends on.
+static int replay_confirm_in_order(am355_ctx* c, Stage1& s) {
+  if (s.opt_rc != AM355_OK) { c->flags = s.opt_flags; c->err = s.opt_err; return s.opt_rc; }
+  auto t0 = std::chrono::steady_clock::now();
+  const uint8_t* dep = c->h_has_dep.as<uint8_t>();
+  set_heads(c, s.n, [&](uint32_t i) { return !dep[i]; });
+  s.ms_host += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return AM355_OK;
+}
+
+// Phase 8, the general path with the scheduler on the device (am355_sched.hip): pass numbers by relaxation over the dependency
+// indexes stream B resolved, application order by a stable sort, the decode plans in that order. The host reads the totals from the
+// pinned words, launches the decode kernels from the device-built plans and does its own half (sequence numbers, clock, span tables)
+// beside them, as on the in-order path. `served` stays false when the device declines: the host's scheduler decides then.
+static int replay_general_on_device(am355_ctx* c, Stage1& s, const TraceLap& lap, bool& served) {
+  hipStream_t sa = c->stream;
+  const uint32_t n = s.n;
+  const size_t n1 = s.n1;
+  if (!c->d_sched.ensure(sched_bytes(n, c->slot_mask)) || !c->h_sched.ensure(13 * (size_t)n1 + 64)) return fail(c, AM355_E_NOMEM, "device allocation failed (scheduler)");
+  SchedBufs sbuf;
+  sched_bind(sbuf, c->d_sched.p, n, c->slot_mask);
+  canary_arm();
+  c->sig_seq++;
+  uint32_t* d_order = nullptr;
+  launch_sched_general(c->d_metas.as<ChangeMeta>(), s.d_briefs, n, c->d_dep_idx.as<uint32_t>(), c->d_self_idx.as<uint32_t>(), c->d_amap_prov.as<uint32_t>(),
+                       c->d_amap_base.as<uint32_t>(), c->amap_cap, c->d_slot_rank.as<uint32_t>(), c->slot_mask, sbuf, &d_order, c->d_plans.as<ChangePlan>(),
+                       c->d_plans.as<ChangePlan>() + n1, s.d_wa, s.d_distinct, s.sig, c->sig_seq, sa);
+  // what the host's half needs: order | pass | first copies | head marks -- on the copy stream, behind the scheduler
+  uint32_t* h_order = c->h_sched.as<uint32_t>();
+  uint32_t *h_pass = h_order + n1, *h_self = h_pass + n1;
+  uint8_t* h_is_head = (uint8_t*)(h_self + n1);
+  HIPCHK(c, hipEventRecord(c->ev_plan, sa));
+  HIPCHK(c, hipStreamWaitEvent(c->stream4, c->ev_plan, 0));
+  HIPCHK(c, hipMemcpyAsync(h_order, d_order, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream4));
+  HIPCHK(c, hipMemcpyAsync(h_pass, sbuf.pass, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream4));
+  HIPCHK(c, hipMemcpyAsync(h_self, c->d_self_idx.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream4));
+  HIPCHK(c, hipMemcpyAsync(h_is_head, sbuf.is_head, (size_t)n, hipMemcpyDeviceToHost, c->stream4));
+  HIPCHK(c, hipEventRecord(c->ev_sched, c->stream4));
+  if (!wait_host_signal(&s.sig->plan_seq, c->sig_seq, sa)) {
+    (void)hipStreamSynchronize(c->stream4);
+    return fail(c, AM355_E_DEVICE, "the device did not report the schedule of this replay (%s)", hipGetErrorString(hipGetLastError()));
+  }
+  PlanTotals gen{};
+  memcpy(&gen, (const void*)&s.sig->plan, sizeof gen);
+  lap("device schedule read");
+  // the relaxation ran out of sweeps, sums beyond 32 bits, or an actor named before its first change: the host's scheduler decides
+  // (and raises the exact flags of an invalid batch)
+  if (gen.reserved[3] || gen.flags_a || gen.fallback) { (void)hipStreamSynchronize(c->stream4); return AM355_OK; }
+  GeneralOrder go{h_order, h_pass, gen.reserved[1], c->ev_sched};
+  float ms_plan = 0;
+  int rc = run_device_planned(c, gen, s.tot.n_distinct, &ms_plan, &go);
+  s.ms_host += ms_plan;
+  if (rc) return rc;
+  auto t0 = std::chrono::steady_clock::now();
+  // what stays queued: the changes of which no copy is ever applied (new.js:1566, 1866)
+  // (copies of one change: whichever copy became ready first was applied, the others were dropped as duplicates then)
+  c->pending_change.clear();
+  std::vector<uint8_t> group_applied(n, 0);
+  for (uint32_t ci = 0; ci < n; ci++)
+    if (h_pass[ci] != SCHED_NEVER) group_applied[h_self[ci] < n ? h_self[ci] : ci] = 1;
+  for (uint32_t ci = 0; ci < n; ci++)
+    if (!group_applied[h_self[ci] < n ? h_self[ci] : ci]) c->pending_change.push_back(ci);
+  c->n_pending = (uint32_t)c->pending_change.size();
+  set_heads(c, n, [&](uint32_t i) { return h_is_head[i] != 0; });
+  s.ms_host += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  served = true;
+  return AM355_OK;
+}
+
+// Phase 9, the general path with the host's scheduler: exact scheduling on the host (thousands of actors, pathological dependency
+// chains, and every batch the reference rejects: the flags it raises are the host's), then decode / merge of exactly the applied
+// changes. dev_actors: the device's actor tables serve (its list of distinct ids holds them all); else the host interns.
+static int replay_general_on_host(am355_ctx* c, Stage1& s, bool dev_actors) {
+  hipStream_t sa = c->stream;
+  const uint32_t n = s.n;
+  const size_t n1 = s.n1, dep_words = c->raw.size() / 32 + 2;
+  if (!c->h_dep_idx.ensure(4 * dep_words) || !c->h_self_idx.ensure(4 * n1)) return fail(c, AM355_E_NOMEM, "host allocation failed");
+  HIPCHK(c, hipMemcpyAsync(c->h_metas.p, c->d_metas.p, sizeof(ChangeMeta) * n, hipMemcpyDeviceToHost, sa));
+  HIPCHK(c, hipMemcpyAsync(c->h_dep_idx.p, c->d_dep_idx.p, 4 * dep_words, hipMemcpyDeviceToHost, sa));  // (stream B has been joined)
+  HIPCHK(c, hipMemcpyAsync(c->h_self_idx.p, c->d_self_idx.p, 4 * (size_t)n, hipMemcpyDeviceToHost, sa));
+  if (dev_actors) {
+    if (!c->h_amap.ensure(4 * ((size_t)s.tot.total_entries + 1)) || !c->h_amap_base.ensure(4 * (n1 + 1))) return fail(c, AM355_E_NOMEM, "host allocation failed");
+    HIPCHK(c, hipMemcpyAsync(c->h_amap.p, c->d_amap_prov.p, 4 * (size_t)s.tot.total_entries, hipMemcpyDeviceToHost, sa));
+    HIPCHK(c, hipMemcpyAsync(c->h_amap_base.p, c->d_amap_base.p, 4 * (size_t)n, hipMemcpyDeviceToHost, sa));
+  }
+  HIPCHK(c, hipStreamSynchronize(sa));
+  if (dev_actors) c->h_amap_base.as<uint32_t>()[n] = s.tot.total_entries;
+  auto t0 = std::chrono::steady_clock::now();
+  int rc = schedule(c, dev_actors ? c->h_amap.as<uint32_t>() : nullptr, dev_actors ? c->h_amap_base.as<uint32_t>() : nullptr);
+  s.ms_host += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (rc) return rc;
+  return run_device(c, nullptr);
+}
+
+// The general path (any delivery order, duplicates, missing dependencies): the optimistic run, if there was one, is discarded.
+static int replay_general(am355_ctx* c, Stage1& s, const TraceLap& lap) {
+  c->flags = 0;
+  c->ir_copy_enqueued = 0;   // (tables of a discarded optimistic run may be on their way: what am355_fetch_ir hands out is enqueued behind the new ones)
+  // the device's actor tables, when its list of distinct ids holds them all (else the host interns)
+  const bool dev_actors = s.tot.n_distinct <= distinct_capacity() && !(s.tot.fast_a & FF_CAPACITY) && s.tot.total_entries <= c->amap_cap;
+  const bool host_schedule = getenv("AM355_HOST_SCHEDULE") != nullptr || s.lineage_schedule;  // (A/B and tests: the host's scheduler for every batch)
+  bool served = false;
+  int rc = AM355_OK;
+  if (dev_actors && s.planned && !host_schedule && s.n > 0) rc = replay_general_on_device(c, s, lap, served);
+  if (!rc && !served) rc = replay_general_on_host(c, s, dev_actors);
+  if (rc) return rc;
+  c->device_scheduled = served;
+  return AM355_OK;
+}
+
+// Phase 10, the finish: statistics and phase timings, what a later am355_apply_changes may keep (the resident mark), and the
+// bookkeeping of a call that was one Backend.loadChanges.
+static void replay_finish(am355_ctx* c, const Stage1& s, std::chrono::steady_clock::time_point t_begin, std::chrono::steady_clock::time_point t_end) {
+  am355_stats& st = c->stats;
+  fill_stats_of_state(c);
+  // (the last kernel has signalled its counters; its remaining workgroups retire within microseconds: poll, do not block)
+  while (hipEventQuery(c->ev[5]) == hipErrorNotReady) {}
+  st.ms_parse = st.ms_decode = st.ms_merge = st.ms_order = 0;
+  if (c->phase_events) {
+    (void)hipEventElapsedTime(&st.ms_parse, c->ev[0], c->ev[1]);
+    (void)hipEventElapsedTime(&st.ms_decode, c->ev[2], c->ev[3]);
+  }
+  if (c->n_ops && c->phase_events) {  // (ev_counts: after resolve / emit / compaction, before the ordering kernels)
+    (void)hipEventElapsedTime(&st.ms_merge, c->ev[3], c->ev_counts);
+    (void)hipEventElapsedTime(&st.ms_order, c->ev_counts, c->ev[5]);
+  }
+  (void)hipEventElapsedTime(&st.ms_hash_stream, c->ev_b0, c->ev_b1);  // hash stream (SHA-256 + dependency resolution), overlapped
+  st.ms_host_schedule = s.ms_host;
+  st.fast_path = s.fast ? 1 : (c->device_scheduled ? 2 : 0);
+  st.ms_total = std::chrono::duration<float, std::milli>(t_end - t_begin).count();
+  c->replayed = true;
+  // what a later am355_apply_changes may keep (replay_resident): every staged change applied, in staged order, rows carved for a capacity
+  c->seed_list_inc = c->counts.n_list_inc;
+  c->res_dep_base = s.n;
+  c->res_dep_first.clear(); c->res_dep_index.clear(); c->res_rank_of.clear(); c->res_actor_memo.clear();
+  c->hash_index_n = c->res_rank_n = 0;
+  c->resident_valid = s.fast && c->in_apply && c->shard_world == 1 && c->mb.row_stride != 0 && !c->has_unknown_cols;
+  if (c->resident_valid) resident_mark(c);
+  if (!c->in_apply) {  // (one call of Backend.loadChanges: its scheduling passes are the op streams)
+    c->stream_breaks = c->pass_first_row;
+    c->breaks_exact = true;
+    c->children_hazard = c->no_history = c->doc_rows_known = false;
+    c->graph_mode = 0;
+  }
+}
+
+int replay_impl(am355_ctx* c) {
+  if (!c) return AM355_E_ARG;
+  if (!c->staged) return fail(c, AM355_E_STATE, "am355_load_changes must be called first");
+  (void)hipSetDevice(c->device);
+  c->replayed = c->ir_fetched = false;
+  c->ir_copy_enqueued = 0;
+  c->dep_graph_ready = false;
+  c->flags = 0;
+  c->spec_launched = false;
+  c->batch_list_only = false;
+  c->h_tables_were_current = c->h_tables_current;   // (of the state before this replay: replay_resident may find them unchanged)
+  c->h_tables_current = false;
+  if (c->is_document) { c->graph_epoch++; return replay_document(c); }
+  const auto t_begin = std::chrono::steady_clock::now();
+  const bool try_resident = c->in_apply && c->keep.want;   // (unless the batch needs the general path)
+  c->keep.want = false;
+  if (try_resident) { const int rr = replay_on_resident_state(c, t_begin); if (rr != RESIDENT_FALLBACK) return rr; }
+  c->graph_epoch++;   // (the applied list is made anew from here on: am355_graph.hip rebuilds its indexes instead of extending them)
+  { int orc = flush_uploads(c); if (!orc) orc = upload_offsets(c); if (orc) return orc; }
+  const TraceLap lap("replay:", 28, t_begin);
+  int rc;
+  Stage1 s;   // (the last local: its lane_join waits for the helper thread in front of everything else that dies with the call)
+  if ((rc = replay_stage1_buffers(c, s))) return rc;
+  if ((rc = replay_parse(c, s))) return rc;
+  replay_post_hash_stream(c, s);
+  if ((rc = replay_intern_and_plan(c, s, lap))) return rc;
+  if ((rc = replay_stage1_verdict(c, s))) return rc;
+  replay_optimistic(c, s, lap);
+  if ((rc = replay_join_hash_stream(c, s, lap))) return rc;
+  if ((rc = s.fast ? replay_confirm_in_order(c, s) : replay_general(c, s, lap))) return rc;
+  c->used_fast_path = s.fast;
+  lap("end");
+  replay_finish(c, s, t_begin, std::chrono::steady_clock::now());
+  return AM355_OK;
+}

@@ -144,6 +144,53 @@ def defect_fixture():
     return fx
 
 
+# Branches of the full replay (am355_replay.hip replay_impl) beside the ones the other tests take: (id, log, shuffled, environment,
+# stats().fast_path). text: 37 changes of 12 actors; map_1100: more actors than the 1024 ids the device ranks, so the plan kernel declines
+# and the host plans (plan_fast, run_device with slot ranks); map_4200: more than the 4096-entry distinct list, so the host interns and
+# schedules. AM355_HOST_PLAN=1 in order: the host's plan; shuffled: the host's scheduler.
+FULL_REPLAY_PATH_CASES = [
+    ("text-in_order", "text", False, {}, 1),
+    ("text-in_order-host_plan", "text", False, {"AM355_HOST_PLAN": "1"}, 1),
+    ("text-shuffled", "text", True, {}, 2),
+    ("text-shuffled-host_plan", "text", True, {"AM355_HOST_PLAN": "1"}, 0),
+    ("map_1100_actors-in_order", "map_1100", False, {}, 1),
+    ("map_4200_actors-in_order", "map_4200", False, {}, 0),
+]
+_full_replay_logs = {}
+
+
+def _full_replay_log(name, shuffled):
+    """(log, the oracle's patch text): generated and replayed by the oracle once, shared by the cases and by both test files."""
+    import numpy as np
+    import oracle_lib
+    from automerge_classic_amd import loggen
+    if (name, shuffled) not in _full_replay_logs:
+        if name == "text":
+            log = loggen.generate(loggen.KIND_TEXT_CONCURRENT, seed=21, n_actors=12, n_rounds=3, ins_per_change=7, del_per_change=2, n_objects=2)
+        else:
+            log = loggen.generate(loggen.KIND_MAP_LWW, seed=3, n_actors=int(name[4:]), n_rounds=1, n_keys=2 if name == "map_1100" else 1)
+        if shuffled:
+            log = log.reordered(np.random.default_rng(5).permutation(log.n_changes))
+        _full_replay_logs[(name, shuffled)] = (log, oracle_lib.OracleDoc(log).patch_json())
+    return _full_replay_logs[(name, shuffled)]
+
+
+def check_full_replay_path(eng, monkeypatch, case):
+    """One case of FULL_REPLAY_PATH_CASES on `eng`: the oracle's patch, by the path the table names, every change applied."""
+    _, name, shuffled, env, fast_path = case
+    log, want = _full_replay_log(name, shuffled)
+    for k in ("AM355_HOST_PLAN", "AM355_HOST_SCHEDULE"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    eng.load_changes(log)
+    eng.replay()
+    assert eng.patch_json() == want
+    st = eng.stats()
+    assert st.fast_path == fast_path
+    assert st.n_applied == st.n_changes == log.n_changes and st.n_pending == 0
+
+
 def headline_pin_cases():
     """tests/golden/headline_pin.json (oracle/make_headline_pin.py): digests of the BLOCK-SIZE-PATCHED reference's getPatch / save on the
     headline shape at 124,801 ops (c4_text_single x0.125), in the generator's delivery order and in bench.py's shuffled one.

@@ -163,6 +163,13 @@ def test_general_scheduler_on_the_device_equals_host_and_oracle(eng, name, log):
         assert seen["device"][2] > 0
 
 
+@pytest.mark.parametrize("case", golden_util.FULL_REPLAY_PATH_CASES, ids=lambda c: c[0])
+def test_full_replay_paths_give_the_oracles_patch(eng, monkeypatch, case):
+    """The branches of replay_impl the other tests do not reach: the host's plan in order, the host's scheduler under AM355_HOST_PLAN, a
+    plan the device declines (1100 actors) and actor tables the host interns (4200 actors)."""
+    golden_util.check_full_replay_path(eng, monkeypatch, case)
+
+
 def test_empty_batch_and_single_change(eng):
     empty = loggen.ChangeLog.from_changes([])
     assert emu_patch(eng, empty) == oracle_lib.OracleDoc(empty).patch_json()

@@ -159,6 +159,12 @@ def test_general_scheduler_on_the_device_equals_host_and_oracle(eng, name, log):
         assert seen["device_out_of_sweeps"][0] == 0
 
 
+@pytest.mark.parametrize("case", golden_util.FULL_REPLAY_PATH_CASES, ids=lambda c: c[0])
+def test_full_replay_paths_give_the_oracles_patch(eng, monkeypatch, case):
+    """The branches of replay_impl the other tests do not reach, on the GPU (the cases and the check are the emulator test's)."""
+    golden_util.check_full_replay_path(eng, monkeypatch, case)
+
+
 def test_full_size_headline_log_in_shuffled_delivery(eng):
     """The 1,020,801-op headline log delivered in random order: scheduled on the device (fast_path 2), same patch as the oracle, same
     document as the in-order delivery."""

@@ -1,5 +1,5 @@
 """A/B of engine knobs read at context creation: median am355_replay wall time of the headline log under each environment.
-   python tools/ab_replay.py 'AM355_HASH_CUS=16' 'AM355_HASH_START=intern' ...   (each argument: space-separated VAR=value pairs, '' = defaults)"""
+   python tools/ab_replay.py 'AM355_HASH_CUS=16' 'AM355_PHASE_EVENTS=1' ...   (each argument: space-separated VAR=value pairs, '' = defaults)"""
 import os
 import statistics
 import subprocess
