@@ -988,3 +988,8 @@ int sync_bloom_impl(am355_ctx* c, const uint32_t* idx, uint32_t n, uint32_t num_
 // the product build and of the CPU test harness stay as they are)
 // ---------------------------------------------------------------------------------------------------------
 #include "am355_graph.hip"
+
+// ---------------------------------------------------------------------------------------------------------
+// the string of a Text object gathered from the edit records (am355_object_text): likewise a file of its own in this translation unit
+// ---------------------------------------------------------------------------------------------------------
+#include "am355_text.hip"

@@ -38,6 +38,11 @@ class Stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TextInfo(ctypes.Structure):
+    """am355_text_info: list length of the Text, elements that are strings, bytes of the string."""
+    _fields_ = [("n_elements", ctypes.c_uint32), ("n_strings", ctypes.c_uint32), ("bytes", ctypes.c_uint64)]
+
+
 class EngineError(RuntimeError):
     def __init__(self, code, message, flags=0):
         names = [n for b, n in FLAG_NAMES.items() if flags & b]
@@ -357,6 +362,13 @@ def _bind(path):
         for f in ("am355_find_changes", "am355_changes_since", "am355_changes_added", "am355_missing_deps", "am355_set_graph_probe_min", "am355_graph_query_calls",
                   "am355_test_hash_probe"):
             getattr(L, f).restype = ctypes.c_int
+    if hasattr(L, "am355_object_text"):   # (libraries of earlier commits, loaded for an A/B run, end before these)
+        L.am355_object_text.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(TextInfo)]
+        L.am355_object_text_calls.argtypes = [vp, vp]
+        L.am355_set_text_pinned_max.argtypes = [vp, ctypes.c_uint64]
+        L.am355_text_limits.argtypes = [vp]
+        for f in ("am355_object_text", "am355_object_text_calls", "am355_set_text_pinned_max", "am355_text_limits"):
+            getattr(L, f).restype = ctypes.c_int
     L.am355_get_raw.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32)]
     L.am355_doc_changes.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_void_p)]
     L.am355_apply_changes.argtypes = [vp, vp, u64p, u32]
@@ -591,6 +603,37 @@ class Engine:
         out = (ctypes.c_uint64 * 2)()
         self._check(self._L.am355_graph_query_calls(self._h, out))
         return int(out[0]), int(out[1])
+
+    def object_text(self, object_id):
+        """The string of a Text object read on the device (am355_object_text): (utf-8 bytes, TextInfo). object_id: "ctr@actorhex" as in the
+        patch. EngineError with code AM355_E_ARG: no such object / not a Text object."""
+        if object_id == "_root":
+            ctr, actor = 0, b""
+        else:
+            c, _, a = str(object_id).partition("@")
+            if not c.isdigit() or not a or len(a) % 2:
+                raise ValueError(f"not an object id: {object_id!r}")
+            ctr, actor = int(c), bytes.fromhex(a)
+        buf = (ctypes.c_uint8 * max(len(actor), 1)).from_buffer_copy(actor or b"\0")
+        p, n, info = ctypes.c_void_p(), ctypes.c_size_t(), TextInfo()
+        self._check(self._L.am355_object_text(self._h, ctr, ctypes.cast(buf, ctypes.c_void_p), len(actor), ctypes.byref(p), ctypes.byref(n), ctypes.byref(info)))
+        return (ctypes.string_at(p, n.value) if n.value else b""), info
+
+    def object_text_calls(self):
+        """(object_text calls served, kernel launches they made)."""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self._L.am355_object_text_calls(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def text_limits(self):
+        """(output bytes one gather workgroup owns, records per workgroup of the size pass, U+FEFF values looked at inline, walked at most)."""
+        out = (ctypes.c_uint32 * 4)()
+        self._check(self._L.am355_text_limits(out))
+        return tuple(int(x) for x in out)
+
+    def set_text_pinned_max(self, n_bytes):
+        """Strings of up to n_bytes are gathered straight into pinned memory by object_text (measurement switch; 0: never)."""
+        self._check(self._L.am355_set_text_pinned_max(self._h, int(n_bytes)))
 
     def prim_hash_probe(self, table_hashes, queries):
         """am355_test_hash_probe: index into table_hashes of every query, 0xffffffff where it is not there (table and probes on the device)."""

@@ -594,6 +594,40 @@ static napi_value js_graph_query_calls(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* objectText(ctx, ctr, Uint8Array actor) -> {text, length, strings}: am355_object_text (the string of a Text object read on the device;
+ * text: the pinned bytes as a JS string, length: the object's list length, strings: its elements that are strings) */
+static napi_value js_object_text(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3], out, v;
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  double ctr = -1;
+  bool is_ta = false;
+  if (argc < 3 || napi_get_value_double(env, argv[1], &ctr) != napi_ok || napi_is_typedarray(env, argv[2], &is_ta) != napi_ok || !is_ta || ctr < 0 || ctr > 4294967295.0) {
+    napi_throw_type_error(env, NULL, "objectText takes a counter and the actor's bytes");
+    return NULL;
+  }
+  napi_typedarray_type t;
+  size_t n = 0;
+  void *actor = NULL;
+  NAPI_CALL(env, napi_get_typedarray_info(env, argv[2], &t, &n, &actor, NULL, NULL));
+  if (t != napi_uint8_array) { napi_throw_type_error(env, NULL, "objectText takes a counter and the actor's bytes"); return NULL; }
+  const uint8_t *utf8 = NULL;
+  size_t len = 0;
+  am355_text_info ti;
+  int rc = am355_object_text(ctx, (uint64_t)ctr, (const uint8_t *)actor, n, &utf8, &len, &ti);
+  if (rc) return throw_engine(env, ctx, rc);
+  NAPI_CALL(env, napi_create_object(env, &out));
+  NAPI_CALL(env, napi_create_string_utf8(env, len ? (const char *)utf8 : "", len, &v));
+  NAPI_CALL(env, napi_set_named_property(env, out, "text", v));
+  NAPI_CALL(env, napi_create_uint32(env, ti.n_elements, &v));
+  NAPI_CALL(env, napi_set_named_property(env, out, "length", v));
+  NAPI_CALL(env, napi_create_uint32(env, ti.n_strings, &v));
+  NAPI_CALL(env, napi_set_named_property(env, out, "strings", v));
+  return out;
+}
+
 /* bloomBuild(ctx, Uint32Array idx) -> Uint8Array: am355_sync_bloom_build (the `bits` of the filter over those changes' hashes) */
 static napi_value js_bloom_build(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -1104,6 +1138,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"missingDeps", NULL, js_missing_deps, NULL, NULL, NULL, napi_enumerable, NULL},
       {"setGraphProbeMin", NULL, js_set_graph_probe_min, NULL, NULL, NULL, napi_enumerable, NULL},
       {"graphQueryCalls", NULL, js_graph_query_calls, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"objectText", NULL, js_object_text, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomBuild", NULL, js_bloom_build, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomProbe", NULL, js_bloom_probe, NULL, NULL, NULL, napi_enumerable, NULL},
       {"fetchApplyIR", NULL, js_fetch_apply_ir, NULL, NULL, NULL, napi_enumerable, NULL},

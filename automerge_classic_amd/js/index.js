@@ -11,6 +11,8 @@
 //   load / save / getAllChanges after load                         (SURVEY.md a21, 8f-1, 8f-3)
 //   applyLocalChange(state, request) -> [state', patch, change]    (backend/backend.js:54-91) for the states applyChanges is served on:
 //                                                                  the change is built on the device (local_change.js, am355_apply_local_change)
+//   getText(state, objectId) / getTextInfo(state, objectId)        ADDITIONS to the reference's surface: the string of a Text object read on
+//                                                                  the device from the edit records (am355_object_text), no patch built
 //   getChanges / getChangeByHash / getMissingDeps / getChangesAdded and the sync helpers over them: index lists from the engine's
 //                                                                  hash-graph queries (am355_changes_since, am355_find_changes,
 //                                                                  am355_missing_deps, am355_changes_added; new.js:1921-2028)
@@ -61,7 +63,7 @@ function ref() {
   return refBackend
 }
 
-const AM355_E_INVALID = -3, AM355_E_UNSUPPORTED = -4
+const AM355_E_ARG = -2, AM355_E_INVALID = -3, AM355_E_UNSUPPORTED = -4
 
 // A state built on the GPU. `changes` are retained (by reference, like BackendDoc.changes new.js:1847) so that a
 // JS BackendDoc can be hydrated later; `patch` is the whole-document patch computed by the engine.
@@ -133,7 +135,7 @@ function contextOf(gen) {
   if (e) { e.used = ++tick; ctx = e.ctx }
   return e || null
 }
-const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, gpuChangesAdded: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0 }   // (diagnostics: which path served the calls)
+const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, gpuChangesAdded: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0, gpuText: 0, textFallbacks: 0 }   // (diagnostics: which path served the calls)
 
 function isFrozenCheck(backend) {
   // reference util.js:1-10
@@ -919,12 +921,62 @@ function getChangesAdded(b1, b2) {
   return ref().getChangesAdded(hydrate(b1), hydrate(b2))
 }
 
+// ---- the string of a Text object: getText / getTextInfo (additions; nothing of backend/index.js:1-8 changes) ----
+// What the reference's frontend shows as doc.<path>.toString() / .length after applyPatch(getPatch(state)), without the patch: the
+// engine gathers the string from its edit records (am355_object_text) while the state's context is live, the state's queue is not held
+// back and the state is the engine's. Otherwise, and for an engine error other than AM355_E_ARG, the JS path: the whole-document patch
+// folded by the rule of updateTextObject + toString (frontend/apply_patch.js:231-255, frontend/text.js:64-67; csrc/am355_text.hip):
+// one element per index, the last `update` of an index wins, only strings are concatenated, a `remove` splices.
+const OBJECT_ID = /^(\d{1,10})@((?:[0-9a-f]{2})+)$/
+let textOnEngine = true   // _setTextOnEngine(false): every read takes the JS path (tests, A/B)
+function textFromPatch(patch, objectId) {
+  let found = null
+  const walk = diff => {
+    if (found) return
+    if (diff.objectId === objectId) { found = diff; return }
+    if (diff.props) for (const key of Object.keys(diff.props)) for (const id of Object.keys(diff.props[key])) if (diff.props[key][id].objectId) walk(diff.props[key][id])
+    if (diff.edits) for (const e of diff.edits) if (e.value && e.value.objectId) walk(e.value)
+  }
+  walk(patch.diffs)
+  if (!found) throw new RangeError(`no such object: ${objectId}`)
+  if (found.type !== 'text') throw new RangeError('not a Text object')
+  const elems = [], str = v => (v.objectId === undefined && v.datatype === undefined && typeof v.value === 'string' ? v.value : null)
+  for (const e of found.edits) {
+    if (e.action === 'insert') elems.splice(e.index, 0, str(e.value))
+    else if (e.action === 'multi-insert') for (let k = 0; k < e.values.length; k += 4096) elems.splice(e.index + k, 0, ...e.values.slice(k, k + 4096).map(v => (e.datatype === undefined && typeof v === 'string' ? v : null)))
+    else if (e.action === 'update') elems[Math.min(e.index, elems.length)] = str(e.value)
+    else if (e.action === 'remove') elems.splice(e.index, e.count)
+  }
+  const strings = elems.filter(v => v !== null)
+  return { text: strings.join(''), length: elems.length, strings: strings.length }
+}
+function getTextInfo(backend, objectId) {
+  isFrozenCheck(backend)
+  const g = backend.state
+  const m = typeof objectId === 'string' ? OBJECT_ID.exec(objectId) : null
+  if (!JS_ONLY && textOnEngine && m && Number(m[1]) <= 0xffffffff && g instanceof GpuState && !heldBack(g) && contextOf(g.generation)) {
+    try {
+      const r = addon.objectText(ctx, Number(m[1]), new Uint8Array(Buffer.from(m[2], 'hex')))
+      counters.gpuText++
+      return r
+    } catch (e) {
+      if (e.am355Code === AM355_E_ARG) throw new RangeError(e.message)
+      if (e.am355Code === undefined) throw e
+    }
+  }
+  counters.textFallbacks++
+  return textFromPatch(getPatch(backend), objectId)
+}
+const getText = (backend, objectId) => getTextInfo(backend, objectId).text
+
 module.exports = {
   init, load, loadChanges, getPatch, getHeads, free, save, getAllChanges, getChanges, getChangeByHash, getMissingDeps,
   clone: backend => { noteGraphQuery(backend); return ref().clone(hydrate(backend)) },
   applyChanges,
   applyLocalChange,
   getChangesAdded,
+  // additions: the string of a Text object / {text, length, strings}, read on the device (see above)
+  getText, getTextInfo,
   // sync protocol: the reference's own backend/sync.js bound to this module (boundSync above)
   generateSyncMessage: (...a) => syncModule().generateSyncMessage(...a),
   receiveSyncMessage: (...a) => syncModule().receiveSyncMessage(...a),
@@ -948,6 +1000,8 @@ module.exports = {
   // between the two (am355_set_graph_probe_min) for every context there is
   _graphQueryCalls: () => contexts.reduce((s, e) => { const w = addon.graphQueryCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),
   _setGraphProbeMin: n => { graphProbeMin = n; for (const e of contexts) addon.setGraphProbeMin(e.ctx, n) },
+  _setTextOnEngine: on => { textOnEngine = !!on },
+  _textFromPatch: textFromPatch,   // (bench_text.js: the JS path's fold by itself)
   _applyProfile: profile,
   _hydrate: hydrate   // (tests: the reference handle of an engine state, made the way the state came to be)
 }

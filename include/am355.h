@@ -564,6 +564,48 @@ int am355_missing_deps(am355_ctx *ctx, const uint8_t *heads, uint32_t n_heads, c
 int am355_set_graph_probe_min(am355_ctx *ctx, uint32_t n);
 int am355_graph_query_calls(const am355_ctx *ctx, uint64_t out[2]);
 
+/*
+ * The string of a Text object, read on the device from the whole-document edit records (csrc/am355_text.hip): *utf8 / *len are the
+ * bytes of exactly the string the reference's frontend shows for that object -- Text.toString() after applyPatch(getPatch(state)) --
+ * without the patch being fetched, rendered or applied. The buffer is pinned memory owned by the context, grown on demand and valid
+ * until the next call on ctx. The object is named as in the patch: obj_ctr @ the actor's raw bytes.
+ * The rule (frontend/apply_patch.js:231-255 updateTextObject, frontend/text.js:64-67 toString):
+ *   1. one element per list index;
+ *   2. where an element shows several values (its insert plus updates, or updates only behind a row without a value), the last
+ *      `update` of that index wins (apply_patch.js:247-250);
+ *   3. only values of type UTF8 (val_tl & 15 == 6, columnar.js:47-48) are concatenated (text.js:64-67);
+ *   4. numbers, booleans, null, bytes, child objects (AM355_EDIT_CHILD), counter totals (AM355_EDIT_COUNTER) and `remove` records
+ *      (AM355_EDIT_REMOVE) contribute nothing;
+ *   5. every such element except a `remove` record still counts in the length.
+ * A value whose bytes begin EF BB BF contributes without those three bytes: the reference decodes every value by itself with
+ * TextDecoder('utf-8'), which drops a leading U+FEFF (encoding.js:9-17). All other bytes are copied as stored: invalid UTF-8 inside a
+ * hand-made change is the caller's to decode.
+ * info (may be NULL): n_elements = the object's list length (the frontend's text.length), n_strings = the elements whose value is a
+ * string, bytes = *len.
+ * Served: a state made by am355_replay, a state after am355_apply_changes / am355_apply_local_change (edit tables that in-place
+ * merges left stale are rebuilt once, as am355_save does), a document context (am355_backend_load, am355_load_document +
+ * am355_replay). The read changes neither the state nor what the next am355_apply_changes is served by, and it leaves the host
+ * copies of the tables as they were.
+ * AM355_E_STATE: no replayed state. AM355_E_UNSUPPORTED: a sharded context; a typed run of more than 4096 values with values that
+ * begin with U+FEFF inside it (read it through the patch). AM355_E_ARG: the id names no object ("no such object: <ctr>@<hex>") or
+ * an object that is no Text ("not a Text object"; _root is obj_ctr 0 with actor_len 0). A state whose whole-document patch the engine
+ * refuses returns that refusal. AM355_E_DEVICE: a record names values outside the tables (nothing is read or written out of range).
+ * am355_object_text_calls: out[0] = calls served, out[1] = kernel launches they made (the library scan counts as one; an empty
+ * Text launches nothing beyond the object lookup, which the host's copy of the object table serves when it is current).
+ * am355_set_text_pinned_max: strings of up to `bytes` bytes are gathered straight into the pinned buffer instead of into device
+ * memory and copied (0 = never). The default is 1 MiB: the direct write was 3-7 us ahead at every size measured, 64 B to 1 MiB
+ * (profiles/text_read_timings.txt); longer strings, which were not measured, take the copy.
+ * am355_text_limits: the sizes at which the kernels take another path (tests): out[0] = output bytes one workgroup of the gather
+ * owns, out[1] = records one workgroup of the size pass takes, out[2] = values of a record its own thread looks at for U+FEFF (more:
+ * the workgroup does), out[3] = values of a run with U+FEFF values inside that the gather walks (more: AM355_E_UNSUPPORTED).
+ */
+typedef struct { uint32_t n_elements, n_strings; uint64_t bytes; } am355_text_info;
+int am355_object_text(am355_ctx *ctx, uint64_t obj_ctr, const uint8_t *obj_actor, size_t actor_len,
+                      const uint8_t **utf8, size_t *len, am355_text_info *info /* may be NULL */);
+int am355_object_text_calls(const am355_ctx *ctx, uint64_t out[2]);   /* served | device launches made */
+int am355_set_text_pinned_max(am355_ctx *ctx, uint64_t bytes);
+int am355_text_limits(uint32_t out[4]);
+
 /* ---- diagnostics: device primitives exposed for kernel-level tests ---- */
 /* The device hash table of the queries above, driven by itself: a table over table_hashes (n_table x 32 bytes) is built and
  * queries (n_queries x 32 bytes) are probed, both on the device; out_idx[q] = index of the table hash equal to query q (the smallest,
