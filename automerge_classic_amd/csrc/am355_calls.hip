@@ -993,3 +993,8 @@ int sync_bloom_impl(am355_ctx* c, const uint32_t* idx, uint32_t n, uint32_t num_
 // the string of a Text object gathered from the edit records (am355_object_text): likewise a file of its own in this translation unit
 // ---------------------------------------------------------------------------------------------------------
 #include "am355_text.hip"
+
+// ---------------------------------------------------------------------------------------------------------
+// positions of a Text resolved to ids, and the edit by position built from them (am355_text_locate, am355_text_splice): likewise
+// ---------------------------------------------------------------------------------------------------------
+#include "am355_locate.hip"

@@ -1,0 +1,427 @@
+// Positions of a Text resolved to ids on the device (include/am355.h: am355_text_locate), and the positional edit built from them
+// (am355_text_splice): what the reference's frontend does in context.splice (frontend/context.js:441-502) for text.deleteAt /
+// text.insertAt, without a frontend document. A caller that keeps a Text on the engine names what it edits by position; a change
+// request names list elements by elemId and, for a deletion, by the op id of the value that goes (`pred`). Both are read here from the
+// whole-document edit records in HBM, compressed into the runs context.splice would merge into `multiOp` deletions, and only the runs
+// cross the link: a 100,000-character deletion inside pasted text is one run of 24 bytes.
+//
+// THE RULE (frontend/context.js:452-496 splice, :576-586 getPred, frontend/apply_patch.js:231-255 updateTextObject):
+//   1. An element of a Text has an elemId and exactly one pred: an `insert` edit gives pred = [edit.opId], a `multi-insert` edit gives
+//      element i elemId = edit.elemId + i and pred = [that elemId], an `update` edit REPLACES the element with pred = [edit.opId] and the
+//      elemId kept (apply_patch.js:232-250). So the pred is the op id of the last edit of the element's index.
+//   2. A deletion joins the one before it as multiOp iff the elemId actors are equal and the elemId counters consecutive, and the pred
+//      actors are equal and the pred counters consecutive (context.js:483-486; "both have exactly one pred" always holds by 1).
+//   3. An element that is a Counter cannot be deleted (context.js:455-471).
+//
+// ON THE RECORD TABLE (am355_ir_edit, the object's records [edit_begin, edit_end), no AM355_EDIT_REMOVE record among them). Record k
+// holds the elements index_k .. index_k + count_k - 1; record k + 1 either opens index_k + count_k or carries AM355_EDIT_UPDATE with
+// index == index_k + count_k - 1 and replaces that one value (am355_text.hip proves this: (a) - (e) of its header). For element j let
+// hi be the LAST record with hi.index <= j. Then
+//     elemId = (hi.elem_ctr + (j - hi.index), hi.elem_actor)        pred = (hi.id_ctr + (j - hi.index), hi.id_actor)
+// Why one search is enough (am355_merge.hip list_edits_of, k_edit_runs, k_edit_pack):
+//   (f) k_edit_pack fills EVERY record, update records too, from the head edit e of the record: id_ctr / id_actor = the op id of the row
+//       e_row[e] that carries the value, elem_ctr / elem_actor = the op id of e_elem[e], the element's insert row -- its elemId. An
+//       update record therefore carries the element's elemId itself; the issue's second search (the last record WITHOUT the update bit,
+//       for the elemId) is not needed, and would be wrong for an element whose edits all carry the update bit (removed_first in
+//       list_edits_of: no record without the bit has its index).
+//   (g) A record of several values holds `simple` edits only (k_edit_runs): row == element for each, consecutive op ids of one actor,
+//       consecutive indexes. So value i of the record has elemId == opId == (id_ctr + i, id_actor) and elem_ctr == id_ctr: both formulas
+//       above count up together, which is apply_patch.js's multi-insert rule. A record whose head edit is not simple (an update, a child,
+//       an insert whose own value is gone and whose first listed value is another row: e_row != e_elem) holds ONE value, j - hi.index is 0
+//       and the record's two ids are the element's: the `insert` edit with opId != elemId, or the `update` edit that replaced it.
+//   (h) hi is the last edit of j's index: records are in document order, the edits of one element stand side by side, and only the last
+//       value of a record shares its index with the record behind ((c) of am355_text.hip) -- for an inner value of a record hi is the
+//       record itself, for its last value the last update record behind it, if there is one.
+//   (i) AM355_EDIT_CONT records are records like any other: their index and ids are those of their first value (k_edit_pack).
+// The element is a counter iff hi carries AM355_EDIT_COUNTER (a counter completed by increments, listed under its last increment) or
+// hi is a plain value record whose type is COUNTER (val_tl & 15 == 8, columnar.js:47-48: a counter nobody has incremented yet is an
+// ordinary `set` row to the engine, and `new Counter` to the frontend).
+// kl_check verifies the premises per record before anything is searched: indexes that start at 0 and continue as stated, `first` words
+// in order and inside the table, no `remove` record. Its last thread leaves the object's length.
+//
+// Included at the end of am355_calls.hip (behind am355_text.hip, whose object lookup it shares), not compiled by itself.
+#include "am355_ctx.h"
+
+namespace am355 {
+
+constexpr uint32_t LOCATE_PINNED_RUNS = 4096;   // runs the compaction writes straight into pinned host memory (96 KiB); the ones behind go to HBM and down in one copy
+// device words of a call (d_loc)
+enum LocWord { LW_FLAGS = 0, LW_LENGTH = 1, LW_RUNS = 2, LW_COUNTERS = 3, LW_WORDS = 4 };
+enum LocFlag : uint32_t { LF_TABLE = 1,     // the records do not continue each other as the rule needs, or name values outside the table
+                          LF_REMOVE = 2,    // a `remove` record: an element that shows rows but no value
+                          LF_RANGE = 4 };   // the queried range reaches past the object's length
+
+// Check pass, one thread per record of the object: the premises of the searches. The last record's thread leaves the length.
+__global__ __launch_bounds__(BLOCK) void kl_check(const am355_ir_edit* __restrict__ edit, uint32_t begin, uint32_t R, uint32_t n_values, uint32_t* __restrict__ words) {
+  const uint32_t k = gtid();
+  if (k >= R) return;
+  const am355_ir_edit& rec = edit[begin + k];
+  const am355_ir_edit& nxt = edit[begin + k + 1];   // (the table ends with a sentinel record: k + 1 <= n_erecs)
+  uint32_t err = 0, count = 0;
+  if (rec.flags & AM355_EDIT_REMOVE) err |= LF_REMOVE;
+  if (nxt.first <= rec.first || nxt.first > n_values) err |= LF_TABLE;
+  else count = nxt.first - rec.first;
+  if (k == 0 && rec.index != 0) err |= LF_TABLE;
+  if ((rec.flags & AM355_EDIT_UPDATE) && count > 1) err |= LF_TABLE;   // (an update record holds one value)
+  if (count && (uint64_t)rec.index + count > 0xffffffffull) err |= LF_TABLE;
+  if (!err) {
+    if (k + 1 < R) {
+      const bool opens = nxt.index == rec.index + count;
+      const bool replaces = (nxt.flags & AM355_EDIT_UPDATE) && nxt.index == rec.index + count - 1;
+      if (!opens && !replaces) err |= LF_TABLE;
+    } else {
+      words[LW_LENGTH] = rec.index + count;
+    }
+  }
+  if (err) atomicOr(&words[LW_FLAGS], err);
+}
+
+// ids of element j: the last record with index <= j (indexes are non-decreasing: kl_check). Reads only records of [begin, begin + R).
+__device__ __forceinline__ uint4 locate_ids(const am355_ir_edit* __restrict__ edit, uint32_t begin, uint32_t R, uint32_t j, uint32_t& counter) {
+  uint32_t lo = 0, hi = R;   // edit[begin + lo].index <= j < edit[begin + hi].index (record 0 has index 0; hi == R: the end)
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (edit[begin + mid].index <= j) lo = mid; else hi = mid;
+  }
+  const am355_ir_edit& rec = edit[begin + lo];
+  const uint32_t d = j - rec.index;
+  counter = ((rec.flags & AM355_EDIT_COUNTER) || (!(rec.flags & AM355_EDIT_CHILD) && (rec.val_tl & 15u) == 8u)) ? 1u : 0u;
+  return uint4{rec.elem_ctr + d, rec.elem_actor, rec.id_ctr + d, rec.id_actor};
+}
+
+// Locate, one thread per queried element first + i: ids[i], counter[i] and head[i] = 1 iff the element does not continue the one before
+// it by the multiOp rule. Element 0 is a head, and so is element `lead` (1: the range begins one element early -- the reference element
+// of an insertion, which is no deletion and must not merge with the first one; 0: no such element). The neighbour's ids come from LDS;
+// the first thread of a workgroup searches for them again.
+__global__ __launch_bounds__(BLOCK) void kl_locate(const am355_ir_edit* __restrict__ edit, uint32_t begin, uint32_t R, uint32_t first, uint32_t n, uint32_t lead,
+                                                   uint32_t* __restrict__ words, uint4* __restrict__ ids, uint32_t* __restrict__ head, uint32_t* __restrict__ counter) {
+  __shared__ uint4 s_ids[BLOCK];
+  const uint32_t i = gtid();
+  const uint32_t length = words[LW_LENGTH];   // (kl_check, the launch before; 0 when it found the table broken)
+  const bool live = i < n && (uint64_t)first + i < length;
+  uint4 me = uint4{0, 0, 0, 0};
+  uint32_t cnt = 0;
+  if (live) me = locate_ids(edit, begin, R, first + i, cnt);
+  s_ids[threadIdx.x] = me;
+  __syncthreads();
+  if (i >= n) return;
+  if (!live) {
+    atomicOr(&words[LW_FLAGS], (uint32_t)LF_RANGE);
+    ids[i] = me; head[i] = 0; counter[i] = 0;
+    return;
+  }
+  uint32_t h = 1;
+  if (i != 0 && i != lead) {
+    uint32_t pc;
+    const uint4 p = threadIdx.x ? s_ids[threadIdx.x - 1] : locate_ids(edit, begin, R, first + i - 1, pc);
+    if (p.y == me.y && p.x + 1 == me.x && p.w == me.w && p.z + 1 == me.z) h = 0;
+  }
+  ids[i] = me; head[i] = h; counter[i] = cnt;
+  if (cnt) atomicAdd(&words[LW_COUNTERS], 1u);   // (counters inside a Text are rare: no contention to speak of)
+}
+
+// Compaction, one thread per queried element: a head writes its run -- ids, the distance to the next head (found by binary search over
+// the scanned head bits: pos[x] = heads in front of x, non-decreasing), whether a counter is among its elements (only when the range
+// holds a counter at all does the head walk its run's counter bits). Run r goes to pinned[r] for r < LOCATE_PINNED_RUNS, else to
+// spill[r - LOCATE_PINNED_RUNS].
+__global__ __launch_bounds__(BLOCK) void kl_runs(const uint4* __restrict__ ids, const uint32_t* __restrict__ head, const uint32_t* __restrict__ pos,
+                                                 const uint32_t* __restrict__ counter, uint32_t n, const uint32_t* __restrict__ words, am355_text_run* __restrict__ pinned,
+                                                 am355_text_run* __restrict__ spill) {
+  const uint32_t i = gtid();
+  if (i >= n || !head[i]) return;
+  const uint32_t r = pos[i];
+  uint32_t lo = i, hi = n;   // pos[lo] <= r + 1 < pos[hi]: everything up to and including the next head has at most r + 1 heads in front
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (pos[mid] <= r + 1) lo = mid; else hi = mid;
+  }
+  const uint32_t end = (lo > i && head[lo]) ? lo : lo + 1;   // the next head, or n
+  uint32_t counters = 0;
+  if (words[LW_COUNTERS])
+    for (uint32_t x = i; x < end; x++) counters |= counter[x];
+  const uint4 me = ids[i];
+  am355_text_run* out = r < LOCATE_PINNED_RUNS ? pinned + r : spill + (r - LOCATE_PINNED_RUNS);
+  out->elem_ctr = me.x; out->elem_actor = me.y; out->pred_ctr = me.z; out->pred_actor = me.w;
+  out->count = end - i;
+  out->flags = counters ? AM355_RUN_COUNTER : 0u;
+}
+
+}  // namespace am355
+
+namespace {
+
+// What both calls share: the runs of [first, first + n) of the object, *length, and *past = 1 when the range reaches past it (no runs
+// then). lead: see kl_locate. The caller has checked the state.
+int locate_core(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint64_t first, uint64_t n, uint32_t lead, const am355_text_run** runs,
+                uint32_t* n_runs, uint64_t* length, bool* past) {
+  (void)hipSetDevice(c->device);
+  { int frc = ensure_ir_fresh(c); if (frc) return frc; }   // (in-place list merges leave the edit tables stale: rebuilt once)
+  hipStream_t st = c->stream;
+  const uint32_t NV = c->counts.n_edits;
+  uint32_t oi = NONE32, eb = 0, ee = 0;
+  { int lrc = text_lookup(c, obj_ctr, obj_actor, actor_len, oi, eb, ee, &c->n_locate_launches); if (lrc) return lrc; }
+  const uint32_t R = ee - eb;
+  *runs = nullptr; *n_runs = 0; *length = 0; *past = false;
+  if (!c->h_loc_runs.ensure(sizeof(am355_text_run))) return fail(c, AM355_E_NOMEM, "host allocation failed (locate)");
+  *runs = c->h_loc_runs.as<am355_text_run>();
+  if (R == 0) {   // an empty Text: nothing to launch
+    *past = first + n > 0 || first + n < first;
+    return AM355_OK;
+  }
+  // (a range the 32-bit positions cannot hold lies past every Text; the length is still wanted)
+  const bool fits = first <= 0xffffffffull && n <= 0xffffffffull && first + n <= 0xffffffffull;
+  const uint32_t N = fits ? (uint32_t)n : 0u, F = fits ? (uint32_t)first : 0u;
+  const size_t b_words = carve_size(LW_WORDS, 4), b_ids = carve_size(N, 16), b_arr = carve_size(N, 4), b_ws = carve_round(scan_workspace_bytes(N ? N : 1));   // ids | head, counter, pos | scan workspace
+  const uint32_t spill_max = N > LOCATE_PINNED_RUNS ? N - LOCATE_PINNED_RUNS : 0u;
+  if (!c->d_loc.ensure(b_words + b_ids + 3 * b_arr + b_ws) || !c->h_loc_sig.ensure((LW_WORDS + 1) * 4) || (spill_max && !c->d_loc_runs.ensure((size_t)spill_max * sizeof(am355_text_run))) ||
+      !c->h_loc_runs.ensure((size_t)(N ? N : 1) * sizeof(am355_text_run)))
+    return fail(c, AM355_E_NOMEM, "allocation failed (locate)");
+  *runs = c->h_loc_runs.as<am355_text_run>();
+  uint8_t* dp = c->d_loc.as<uint8_t>();
+  uint32_t* dw = (uint32_t*)dp;
+  uint4* d_ids = (uint4*)(dp + b_words);
+  uint32_t* d_head = (uint32_t*)(dp + b_words + b_ids);
+  uint32_t* d_cnt = d_head + b_arr / 4;
+  uint32_t* d_pos = d_cnt + b_arr / 4;
+  void* d_ws = dp + b_words + b_ids + 3 * b_arr;
+  uint32_t* hw = c->h_loc_sig.as<uint32_t>();
+  volatile uint32_t* hseq = (volatile uint32_t*)(hw + LW_WORDS);
+  if (c->loc_seq == 0) *hseq = 0;
+  HIPCHK(c, hipMemsetAsync(dw, 0, LW_WORDS * 4, st));
+  AM355_LAUNCH_INDEPENDENT(kl_check, dim3((R + BLOCK - 1) / BLOCK), dim3(BLOCK), st, (const am355_ir_edit*)c->ir.edit, eb, R, NV, dw);
+  c->n_locate_launches++;
+  if (N) {
+    const dim3 grid((N + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(kl_locate, grid, dim3(BLOCK), 0, st, (const am355_ir_edit*)c->ir.edit, eb, R, F, N, lead, dw, d_ids, d_head, d_cnt);
+    exclusive_scan_u32(d_head, d_pos, N, dw + LW_RUNS, d_ws, st);
+    AM355_LAUNCH_INDEPENDENT(kl_runs, grid, dim3(BLOCK), st, (const uint4*)d_ids, (const uint32_t*)d_head, (const uint32_t*)d_pos, (const uint32_t*)d_cnt, N, (const uint32_t*)dw,
+                             c->h_loc_runs.as<am355_text_run>(), c->d_loc_runs.as<am355_text_run>());
+    c->n_locate_launches += 3;
+  }
+  launch_signal_words(dw, LW_WORDS, nullptr, 0, hw, hseq, ++c->loc_seq, st);
+  c->n_locate_launches++;
+  // the one wait of the call: flag word, length, number of runs
+  if (!wait_host_signal(hseq, c->loc_seq, st)) HIPCHK(c, hipMemcpy(hw, dw, LW_WORDS * 4, hipMemcpyDeviceToHost));
+  const uint32_t lf = hw[LW_FLAGS];
+  if (lf & LF_TABLE) return fail(c, AM355_E_DEVICE, "internal: the edit records of object %u do not continue each other", oi);
+  if (lf & LF_REMOVE) return fail(c, AM355_E_UNSUPPORTED, "a Text element that shows rows but no value (a `remove` record): positions through the patch");
+  *length = hw[LW_LENGTH];
+  if (!fits || first + n > *length) { *past = true; return AM355_OK; }
+  if (lf & LF_RANGE) return fail(c, AM355_E_DEVICE, "internal: the locate pass and the host disagree about the length of object %u", oi);
+  const uint32_t nr = N ? hw[LW_RUNS] : 0u;
+  if (nr > N || (N && !nr)) return fail(c, AM355_E_DEVICE, "internal: %u runs over %u elements", nr, N);
+  if (nr > LOCATE_PINNED_RUNS) {
+    HIPCHK(c, hipMemcpyAsync(c->h_loc_runs.as<am355_text_run>() + LOCATE_PINNED_RUNS, c->d_loc_runs.p, (size_t)(nr - LOCATE_PINNED_RUNS) * sizeof(am355_text_run),
+                             hipMemcpyDeviceToHost, st));
+    int prc = text_poll(c);
+    if (prc) return prc;
+  }
+  *n_runs = nr;
+  return AM355_OK;
+}
+
+int locate_state_check(am355_ctx* c, const char* who) {
+  if (!c->replayed) return fail(c, AM355_E_STATE, "%s: a replayed state is needed", who);
+  if (c->shard_world > 1) return fail(c, AM355_E_UNSUPPORTED, "%s on a sharded context", who);
+  return AM355_OK;
+}
+
+int text_locate_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint64_t first, uint64_t n, const am355_text_run** runs, uint32_t* n_runs,
+                     uint64_t* length) {
+  if (!c) return AM355_E_ARG;
+  if (!runs || !n_runs || !length || (!obj_actor && actor_len)) return fail(c, AM355_E_ARG, "am355_text_locate: null argument");
+  int rc = locate_state_check(c, "am355_text_locate");
+  if (rc) return rc;
+  bool past = false;
+  rc = locate_core(c, obj_ctr, obj_actor, actor_len, first, n, 0, runs, n_runs, length, &past);
+  if (rc) return rc;
+  if (past)
+    return fail(c, AM355_E_ARG, "elements [%llu, %llu + %llu) are out of bounds for a Text of length %llu", (unsigned long long)first, (unsigned long long)first,
+                (unsigned long long)n, (unsigned long long)*length);
+  return AM355_OK;
+}
+
+// actors of a request: raw ids, each once, the author first and the others in byte order (columnar.js:154-157)
+struct SpliceActors {
+  std::vector<std::string> table;
+  uint32_t local(const std::string& a) const {
+    for (uint32_t k = 0; k < table.size(); k++)
+      if (table[k] == a) return k;
+    return NONE32;
+  }
+};
+
+int text_splice_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint64_t start, uint64_t deletions, const uint8_t* utf8,
+                     const uint32_t* value_off, uint32_t n_values, const uint8_t* author, size_t author_len, int64_t time, const uint8_t* message, uint32_t message_len,
+                     const uint8_t** change, size_t* len) {
+  if (!c) return AM355_E_ARG;
+  auto refused = [&](int code) { c->n_splice_refused++; return code; };
+  if (!change || !len || (!obj_actor && actor_len) || !author || !author_len || (n_values && (!value_off || (!utf8 && value_off[n_values]))) || (!message && message_len))
+    return refused(fail(c, AM355_E_ARG, "am355_text_splice: null argument"));
+  for (uint32_t k = 0; k < n_values; k++)
+    if (value_off[k + 1] < value_off[k]) return refused(fail(c, AM355_E_ARG, "am355_text_splice: value offsets out of order"));
+  const bool trace = getenv("AM355_TRACE") != nullptr;
+  const auto t_begin = std::chrono::steady_clock::now();
+  auto lap = [&](const char* what) {
+    if (trace) fprintf(stderr, "text_splice: %-26s +%8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+  };
+  *change = nullptr; *len = 0;
+  int rc = locate_state_check(c, "am355_text_splice");
+  if (rc) return refused(rc);
+  (void)hipSetDevice(c->device);
+  if (c->staged && c->is_document) {   // (as am355_apply_local_change: the document becomes the state of its rebuilt changes, whose clock, heads and max_op the request needs)
+    rc = document_to_change_state(c, [](const char*) {});
+    if (rc) return refused(rc);
+    if (!c->replayed) return refused(fail(c, AM355_E_STATE, "am355_text_splice: a replayed state is needed"));
+  }
+  if (!c->pending_change.empty() || c->n_pending) return refused(fail(c, AM355_E_UNSUPPORTED, "local change onto a state with queued changes: JS path"));
+
+  // ---- locate [start - 1, start + deletions): the insertion's reference element, then the deleted ones ----
+  const uint32_t lead = start ? 1u : 0u;
+  const am355_text_run* runs = nullptr;
+  uint32_t n_runs = 0;
+  uint64_t length = 0;
+  bool past = false;
+  const uint64_t q_first = start - lead, q_n = deletions + lead;
+  const bool wraps = q_n < deletions || q_first + q_n < q_first;
+  rc = locate_core(c, obj_ctr, obj_actor, actor_len, wraps ? 0 : q_first, wraps ? 0 : q_n, lead, &runs, &n_runs, &length, &past);
+  if (rc) return refused(rc);
+  lap("located");
+  if (wraps || past)   // context.js:444-446
+    return refused(fail(c, AM355_E_ARG, "%llu deletions starting at index %llu are out of bounds for list of length %llu", (unsigned long long)deletions,
+                        (unsigned long long)start, (unsigned long long)length));
+  if (deletions == 0 && n_values == 0) { c->n_splice_served++; return AM355_OK; }   // context.js:447
+  for (uint32_t r = lead; r < n_runs; r++)
+    if (runs[r].flags & AM355_RUN_COUNTER) return refused(fail(c, AM355_E_INVALID, "Unsupported operation: deleting a counter from a list"));   // context.js:471
+  if (lead && (!n_runs || runs[0].count != 1)) return refused(fail(c, AM355_E_DEVICE, "internal: the reference element of the insertion is not a run of its own"));
+
+  // ---- the request (context.js:452-496 the deletions, :370-405 insertListItems) ----
+  const uint32_t NA = (uint32_t)c->actors.size();
+  for (uint32_t r = 0; r < n_runs; r++)
+    if (runs[r].elem_actor >= NA || runs[r].pred_actor >= NA) return refused(fail(c, AM355_E_DEVICE, "internal: run %u names an actor outside the table", r));
+  const std::string me((const char*)author, author_len), obj_a((const char*)obj_actor, actor_len);
+  SpliceActors act;
+  {
+    std::vector<std::string> others{obj_a};
+    for (uint32_t r = 0; r < n_runs; r++) {
+      if (r >= lead || n_values) others.push_back(c->actors[runs[r].elem_actor]);
+      if (r >= lead) others.push_back(c->actors[runs[r].pred_actor]);
+    }
+    std::sort(others.begin(), others.end());
+    others.erase(std::unique(others.begin(), others.end()), others.end());
+    act.table.push_back(me);
+    for (const std::string& a : others)
+      if (a != me) act.table.push_back(a);
+  }
+  const uint32_t n_act = (uint32_t)act.table.size();
+  std::vector<uint32_t> actor_off(n_act + 1, 0), actor_rank(n_act, 0);
+  std::vector<uint8_t> actor_bytes;
+  for (uint32_t k = 0; k < n_act; k++) {
+    actor_bytes.insert(actor_bytes.end(), act.table[k].begin(), act.table[k].end());
+    actor_off[k + 1] = (uint32_t)actor_bytes.size();
+    // (entries 1 .. are in byte order already: the author's rank is the number of them in front of it)
+    actor_rank[k] = k == 0 ? (uint32_t)(std::lower_bound(act.table.begin() + 1, act.table.end(), me) - (act.table.begin() + 1))
+                           : (k - 1) + (act.table[k] > me ? 1u : 0u);
+  }
+  std::vector<am355_local_op> ops;
+  std::vector<am355_local_pred> preds;
+  std::vector<am355_local_value> values;
+  const uint32_t obj_local = act.local(obj_a);
+  for (uint32_t r = lead; r < n_runs; r++) {
+    am355_local_op op{};
+    op.action = 3;   // del
+    op.obj_actor = obj_local; op.obj_ctr = (uint32_t)obj_ctr;
+    op.key_kind = AM355_LK_ELEM;
+    op.elem_actor = act.local(c->actors[runs[r].elem_actor]); op.elem_ctr = runs[r].elem_ctr;
+    op.multi = runs[r].count;
+    op.pred_first = (uint32_t)preds.size(); op.pred_num = 1;
+    preds.push_back(am355_local_pred{act.local(c->actors[runs[r].pred_actor]), runs[r].pred_ctr});
+    ops.push_back(op);
+  }
+  if (n_values) {
+    am355_local_op op{};
+    op.action = 1;   // set
+    op.obj_actor = obj_local; op.obj_ctr = (uint32_t)obj_ctr;
+    if (lead) { op.key_kind = AM355_LK_ELEM; op.elem_actor = act.local(c->actors[runs[0].elem_actor]); op.elem_ctr = runs[0].elem_ctr; }
+    else op.key_kind = AM355_LK_HEAD;
+    op.flags = AM355_LOP_INSERT | (n_values > 1 ? AM355_LOP_VALUES : 0u);
+    op.multi = n_values;
+    op.pred_first = (uint32_t)preds.size();
+    for (uint32_t k = 0; k < n_values; k++) values.push_back(am355_local_value{AM355_LV_UTF8, value_off[k], value_off[k + 1] - value_off[k], 0, 0});
+    ops.push_back(op);
+  }
+  am355_local_change lc{};
+  lc.seq = 1;
+  {
+    auto it = std::lower_bound(c->actors.begin(), c->actors.end(), me);
+    if (it != c->actors.end() && *it == me) {
+      const uint32_t rank = (uint32_t)(it - c->actors.begin());
+      for (size_t k = 0; k < c->clock_actor.size(); k++)
+        if (c->clock_actor[k] == rank) lc.seq = c->clock_seq[k] + 1;
+    }
+  }
+  lc.start_op = c->max_op + 1;
+  lc.time = time;
+  lc.message = message; lc.message_len = message_len;
+  // deps: the heads without the author's last change, which am355_apply_local_change adds itself (backend.js:73-81, 88-89)
+  std::vector<uint8_t> deps(c->heads);
+  if (lc.seq > 1 && c->h_hashes.p)
+    for (uint32_t ci = c->n_changes; ci-- > 0;) {
+      const uint8_t* a = nullptr;
+      size_t al = 0;
+      uint64_t s = 0;
+      if (!staged_author_seq(c, ci, a, al, s)) return refused(fail(c, AM355_E_DEVICE, "internal: staged change %u does not parse", ci));
+      if (s == lc.seq - 1 && al == author_len && memcmp(a, author, al) == 0) {
+        const uint8_t* h = c->h_hashes.as<uint8_t>() + 32 * (size_t)ci;
+        for (size_t k = 0; k + 32 <= deps.size(); k += 32)
+          if (memcmp(&deps[k], h, 32) == 0) { deps.erase(deps.begin() + k, deps.begin() + k + 32); break; }
+        break;
+      }
+    }
+  lc.deps = deps.data(); lc.n_deps = (uint32_t)(deps.size() / 32);
+  lc.n_actors = n_act; lc.actor_off = actor_off.data(); lc.actor_bytes = actor_bytes.data(); lc.actor_rank = actor_rank.data();
+  lc.strings = utf8; lc.strings_len = n_values ? value_off[n_values] : 0u;
+  lc.ops = ops.data(); lc.n_ops = (uint32_t)ops.size();
+  lc.values = values.data(); lc.n_values = (uint32_t)values.size();
+  lc.preds = preds.data(); lc.n_preds = (uint32_t)preds.size();
+  lap("request built");
+  rc = apply_local_change_impl(c, &lc, change, len);
+  lap("applied");
+  if (rc) return refused(rc);
+  c->n_splice_served++;
+  return AM355_OK;
+}
+
+}  // namespace
+
+extern "C" int am355_text_locate(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint64_t first, uint64_t n, const am355_text_run** runs,
+                                 uint32_t* n_runs, uint64_t* length) {
+  return guarded(c, [&]() { return text_locate_impl(c, obj_ctr, obj_actor, actor_len, first, n, runs, n_runs, length); });
+}
+extern "C" int am355_text_splice(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint64_t start, uint64_t deletions, const uint8_t* utf8,
+                                 const uint32_t* value_off, uint32_t n_values, const uint8_t* author, size_t author_len, int64_t time, const uint8_t* message,
+                                 uint32_t message_len, const uint8_t** change, size_t* len) {
+  return guarded(c, [&]() {
+    return text_splice_impl(c, obj_ctr, obj_actor, actor_len, start, deletions, utf8, value_off, n_values, author, author_len, time, message, message_len, change, len);
+  });
+}
+extern "C" int am355_text_splice_calls(const am355_ctx* c, uint64_t out[3]) {
+  if (!c || !out) return AM355_E_ARG;
+  out[0] = c->n_splice_served;
+  out[1] = c->n_splice_refused;
+  out[2] = c->n_locate_launches;
+  return AM355_OK;
+}
+extern "C" int am355_actor_of_rank(const am355_ctx* c, uint32_t rank, const uint8_t** bytes, size_t* len) {
+  if (!c || !bytes || !len) return AM355_E_ARG;
+  if (!c->replayed) return AM355_E_STATE;
+  if (rank >= c->actors.size()) return AM355_E_ARG;
+  *bytes = (const uint8_t*)c->actors[rank].data();
+  *len = c->actors[rank].size();
+  return AM355_OK;
+}
+extern "C" int am355_text_locate_limits(uint32_t out[3]) {
+  if (!out) return AM355_E_ARG;
+  out[0] = BLOCK; out[1] = scan_single_limit(); out[2] = LOCATE_PINNED_RUNS;
+  return AM355_OK;
+}

@@ -65,6 +65,7 @@ void launch_remap_ranks(const RemapRanges& r, const uint32_t* d_table, uint32_t 
 void launch_signal_words(const uint32_t* src_a, uint32_t n_a, const uint32_t* src_b, uint32_t n_b, uint32_t* host_words, volatile uint32_t* host_seq, uint32_t seq,
                          hipStream_t st);
 size_t scan_workspace_bytes(uint32_t n);
+uint32_t scan_single_limit();   // arrays of up to this many elements are scanned by one workgroup in one launch
 // out[i] = sum(in[0..i)); in == out allowed. *d_total (device, optional) receives the grand total.
 void exclusive_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* d_total, void* ws, hipStream_t st);
 // out[i] = number of bytes in [0, i) with bit 7 clear (LEB128 terminators), i = 0 .. L: the scan of a flag array that is never stored

@@ -394,6 +394,7 @@ void exclusive_scan_terminators(const uint8_t* bytes, uint32_t L, uint32_t* out,
   hipLaunchKernelGGL(k_scan_term_apply, dim3(n_tiles), dim3(BLOCK), 0, st, bytes, L, out, (const uint32_t*)sums);
 }
 
+uint32_t scan_single_limit() { return SCAN_SINGLE; }
 size_t scan_workspace_bytes(uint32_t n) { return 2 * sizeof(uint32_t) * ((size_t)(n + SCAN_TILE - 1) / SCAN_TILE + 2); }  // (room for a dual scan)
 
 void exclusive_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* d_total, void* ws, hipStream_t st) {

@@ -244,15 +244,12 @@ int text_poll(am355_ctx* c) {   // (short copies and kernels: polled, not slept 
   return AM355_OK;
 }
 
-int object_text_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, const uint8_t** utf8, size_t* len, am355_text_info* info) {
-  if (!c) return AM355_E_ARG;
-  if (!utf8 || !len || (!obj_actor && actor_len)) return fail(c, AM355_E_ARG, "am355_object_text: null argument");
-  if (!c->replayed) return fail(c, AM355_E_STATE, "am355_object_text: a replayed state is needed");
-  if (c->shard_world > 1) return fail(c, AM355_E_UNSUPPORTED, "am355_object_text on a sharded context");
-  (void)hipSetDevice(c->device);
-  { int frc = ensure_ir_fresh(c); if (frc) return frc; }   // (in-place list merges leave the edit tables stale: rebuilt once)
+// The object a call names, for am355_object_text and the calls of am355_locate.hip: its index and its edit records [eb, ee). From the host's
+// copy of the object table when it is the device's, else one launch over ir.obj (+ the launch that signals the four words; counted in
+// *launches). The caller has checked the state and run ensure_ir_fresh.
+int text_lookup(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint32_t& oi, uint32_t& eb, uint32_t& ee, uint64_t* launches) {
   hipStream_t st = c->stream;
-  const uint32_t NO = c->counts.n_objects, NR = c->counts.n_erecs, NV = c->counts.n_edits;
+  const uint32_t NO = c->counts.n_objects, NR = c->counts.n_erecs;
   const std::string id = text_id(obj_ctr, obj_actor, actor_len);
   if (obj_ctr == 0 && actor_len == 0) return fail(c, AM355_E_ARG, "not a Text object");   // (_root: a map)
   uint32_t rank = 0;
@@ -263,7 +260,8 @@ int object_text_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, s
   uint32_t* hw = c->h_text_sig.as<uint32_t>();
   volatile uint32_t* hseq = (volatile uint32_t*)(hw + TW_WORDS);
   if (c->text_seq == 0) *hseq = 0;
-  uint32_t oi = NONE32, type = 0, eb = 0, ee = 0;
+  uint32_t type = 0;
+  oi = NONE32; eb = ee = 0;
   if (c->h_tables_current && c->hir.objects && c->hir.n_objects == NO) {
     for (uint32_t i = 1; i < NO; i++)
       if (c->hir.objects[i].id_ctr == (uint32_t)obj_ctr && c->hir.objects[i].id_actor == rank) {
@@ -275,13 +273,29 @@ int object_text_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, s
     HIPCHK(c, hipMemsetAsync(dw, 0xff, 4 * 4, st));
     AM355_LAUNCH_INDEPENDENT(kt_find, dim3((NO + BLOCK - 1) / BLOCK), dim3(BLOCK), st, (const am355_ir_object*)c->ir.obj, NO, (uint32_t)obj_ctr, rank, dw);
     launch_signal_words(dw, 4, nullptr, 0, hw, hseq, ++c->text_seq, st);
-    c->n_text_launches += 2;
+    *launches += 2;
     if (!wait_host_signal(hseq, c->text_seq, st)) HIPCHK(c, hipMemcpy(hw, dw, 4 * 4, hipMemcpyDeviceToHost));
     oi = hw[TW_INDEX]; type = hw[TW_TYPE]; eb = hw[TW_BEGIN]; ee = hw[TW_END];
   }
   if (oi == NONE32) return fail(c, AM355_E_ARG, "no such object: %s", id.c_str());
   if (type != 4) return fail(c, AM355_E_ARG, "not a Text object");
   if (eb > ee || ee > NR) return fail(c, AM355_E_DEVICE, "internal: edit range [%u, %u) of object %u outside the %u records", eb, ee, oi, NR);
+  return AM355_OK;
+}
+
+int object_text_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, const uint8_t** utf8, size_t* len, am355_text_info* info) {
+  if (!c) return AM355_E_ARG;
+  if (!utf8 || !len || (!obj_actor && actor_len)) return fail(c, AM355_E_ARG, "am355_object_text: null argument");
+  if (!c->replayed) return fail(c, AM355_E_STATE, "am355_object_text: a replayed state is needed");
+  if (c->shard_world > 1) return fail(c, AM355_E_UNSUPPORTED, "am355_object_text on a sharded context");
+  (void)hipSetDevice(c->device);
+  { int frc = ensure_ir_fresh(c); if (frc) return frc; }   // (in-place list merges leave the edit tables stale: rebuilt once)
+  hipStream_t st = c->stream;
+  const uint32_t NV = c->counts.n_edits;
+  uint32_t oi = NONE32, eb = 0, ee = 0;
+  { int lrc = text_lookup(c, obj_ctr, obj_actor, actor_len, oi, eb, ee, &c->n_text_launches); if (lrc) return lrc; }
+  uint32_t* hw = c->h_text_sig.as<uint32_t>();
+  volatile uint32_t* hseq = (volatile uint32_t*)(hw + TW_WORDS);
   const uint32_t R = ee - eb;
   am355_text_info ti{0, 0, 0};
   size_t total = 0;

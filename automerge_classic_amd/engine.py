@@ -43,6 +43,11 @@ class TextInfo(ctypes.Structure):
     _fields_ = [("n_elements", ctypes.c_uint32), ("n_strings", ctypes.c_uint32), ("bytes", ctypes.c_uint64)]
 
 
+# am355_text_run: a run of consecutive (elemId, pred) pairs of a Text (actors: ranks of the engine's actor table)
+TEXT_RUN_DTYPE = np.dtype([("elem_ctr", "<u4"), ("elem_actor", "<u4"), ("pred_ctr", "<u4"), ("pred_actor", "<u4"), ("count", "<u4"), ("flags", "<u4")])
+RUN_COUNTER = 1
+
+
 class EngineError(RuntimeError):
     def __init__(self, code, message, flags=0):
         names = [n for b, n in FLAG_NAMES.items() if flags & b]
@@ -369,6 +374,15 @@ def _bind(path):
         L.am355_text_limits.argtypes = [vp]
         for f in ("am355_object_text", "am355_object_text_calls", "am355_set_text_pinned_max", "am355_text_limits"):
             getattr(L, f).restype = ctypes.c_int
+    if hasattr(L, "am355_text_splice"):   # (libraries of earlier commits, loaded for an A/B run, end before these)
+        L.am355_text_locate.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32),
+                                        ctypes.POINTER(ctypes.c_uint64)]
+        L.am355_text_splice.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, vp, vp, u32, vp, ctypes.c_size_t, ctypes.c_int64, vp, u32,
+                                        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+        L.am355_text_splice_calls.argtypes = [vp, vp]
+        L.am355_text_locate_limits.argtypes = [vp]
+        for f in ("am355_text_locate", "am355_text_splice", "am355_text_splice_calls", "am355_text_locate_limits"):
+            getattr(L, f).restype = ctypes.c_int
     L.am355_get_raw.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32)]
     L.am355_doc_changes.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_void_p)]
     L.am355_apply_changes.argtypes = [vp, vp, u64p, u32]
@@ -604,9 +618,9 @@ class Engine:
         self._check(self._L.am355_graph_query_calls(self._h, out))
         return int(out[0]), int(out[1])
 
-    def object_text(self, object_id):
-        """The string of a Text object read on the device (am355_object_text): (utf-8 bytes, TextInfo). object_id: "ctr@actorhex" as in the
-        patch. EngineError with code AM355_E_ARG: no such object / not a Text object."""
+    @staticmethod
+    def _object_id(object_id):
+        """"ctr@actorhex" (or "_root") as (counter, actor bytes, a ctypes buffer of them)."""
         if object_id == "_root":
             ctr, actor = 0, b""
         else:
@@ -614,7 +628,12 @@ class Engine:
             if not c.isdigit() or not a or len(a) % 2:
                 raise ValueError(f"not an object id: {object_id!r}")
             ctr, actor = int(c), bytes.fromhex(a)
-        buf = (ctypes.c_uint8 * max(len(actor), 1)).from_buffer_copy(actor or b"\0")
+        return ctr, actor, (ctypes.c_uint8 * max(len(actor), 1)).from_buffer_copy(actor or b"\0")
+
+    def object_text(self, object_id):
+        """The string of a Text object read on the device (am355_object_text): (utf-8 bytes, TextInfo). object_id: "ctr@actorhex" as in the
+        patch. EngineError with code AM355_E_ARG: no such object / not a Text object."""
+        ctr, actor, buf = self._object_id(object_id)
         p, n, info = ctypes.c_void_p(), ctypes.c_size_t(), TextInfo()
         self._check(self._L.am355_object_text(self._h, ctr, ctypes.cast(buf, ctypes.c_void_p), len(actor), ctypes.byref(p), ctypes.byref(n), ctypes.byref(info)))
         return (ctypes.string_at(p, n.value) if n.value else b""), info
@@ -629,6 +648,52 @@ class Engine:
         """(output bytes one gather workgroup owns, records per workgroup of the size pass, U+FEFF values looked at inline, walked at most)."""
         out = (ctypes.c_uint32 * 4)()
         self._check(self._L.am355_text_limits(out))
+        return tuple(int(x) for x in out)
+
+    def text_locate(self, object_id, first, n):
+        """Elements [first, first + n) of a Text resolved to ids on the device (am355_text_locate): (runs, length). runs: a structured
+        array (TEXT_RUN_DTYPE) of runs of consecutive (elemId, pred) pairs, actors as ranks; length: the Text's length. EngineError with
+        code AM355_E_ARG: no such object / not a Text object / the range reaches past the length."""
+        ctr, actor, buf = self._object_id(object_id)
+        p, nr, length = ctypes.c_void_p(), ctypes.c_uint32(), ctypes.c_uint64()
+        self._check(self._L.am355_text_locate(self._h, ctr, ctypes.cast(buf, ctypes.c_void_p), len(actor), int(first), int(n), ctypes.byref(p), ctypes.byref(nr),
+                                              ctypes.byref(length)))
+        runs = np.zeros(nr.value, dtype=TEXT_RUN_DTYPE)
+        if nr.value:
+            ctypes.memmove(runs.ctypes.data, p, nr.value * TEXT_RUN_DTYPE.itemsize)
+        return runs, int(length.value)
+
+    def text_splice(self, object_id, start, deletions, values, actor, time=0, message=""):
+        """One context.splice of the reference's frontend on a Text the engine holds (am355_text_splice): delete `deletions` elements from
+        position `start` on, then insert the strings `values` there, one element each; `actor`: the author's id in hex. Returns the
+        binary change (b"" when there was nothing to do); apply_patch_json() then gives the patch. EngineError with code AM355_E_ARG
+        and the reference's RangeError text when the range is out of bounds, InvalidChanges with its TypeError text for a counter among
+        the deleted elements. The caller owns the author and the order of its calls."""
+        ctr, obj_actor, buf = self._object_id(object_id)
+        parts = [v.encode("utf-8") for v in values]
+        offs = np.zeros(len(parts) + 1, dtype=np.uint32)
+        np.cumsum([len(b) for b in parts], out=offs[1:])
+        blob = np.frombuffer(b"".join(parts) or b"\0", dtype=np.uint8)
+        author = np.frombuffer(bytes.fromhex(actor), dtype=np.uint8)
+        msg = np.frombuffer(message.encode("utf-8") or b"\0", dtype=np.uint8)
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._L.am355_text_splice(self._h, ctr, ctypes.cast(buf, ctypes.c_void_p), len(obj_actor), int(start), int(deletions), blob.ctypes.data,
+                                              offs.ctypes.data, len(parts), author.ctypes.data if author.size else None, author.size, int(time), msg.ctypes.data,
+                                              len(message.encode("utf-8")), ctypes.byref(p), ctypes.byref(n)))
+        if n.value:
+            self._n_changes = int(self.stats().n_changes)
+        return ctypes.string_at(p, n.value) if n.value else b""
+
+    def text_splice_calls(self):
+        """(splices served, splices refused, kernel launches of the locate half of text_locate and text_splice)."""
+        out = (ctypes.c_uint64 * 3)()
+        self._check(self._L.am355_text_splice_calls(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def text_locate_limits(self):
+        """(elements per workgroup of the locate kernel, elements the head scan takes in one workgroup, runs written straight to pinned memory)."""
+        out = (ctypes.c_uint32 * 3)()
+        self._check(self._L.am355_text_locate_limits(out))
         return tuple(int(x) for x in out)
 
     def set_text_pinned_max(self, n_bytes):

@@ -1103,6 +1103,99 @@ static napi_value js_local_small_calls(napi_env env, napi_callback_info info) {
   return arr;
 }
 
+/* a Uint8Array argument: its bytes */
+static bool get_u8_array(napi_env env, napi_value v, const uint8_t **p, size_t *n) {
+  bool is_ta = false;
+  napi_typedarray_type t;
+  void *data = NULL;
+  if (napi_is_typedarray(env, v, &is_ta) != napi_ok || !is_ta) return false;
+  if (napi_get_typedarray_info(env, v, &t, n, &data, NULL, NULL) != napi_ok || t != napi_uint8_array) return false;
+  *p = (const uint8_t *)data;
+  return true;
+}
+/* "<ctr>@<actor in hex>" of an id whose actor is a rank of the engine's table (am355_actor_of_rank) */
+static bool id_string(napi_env env, am355_ctx *ctx, uint32_t ctr, uint32_t rank, napi_value *out) {
+  const uint8_t *a = NULL;
+  size_t n = 0;
+  char buf[16 + 2 * 256];
+  if (am355_actor_of_rank(ctx, rank, &a, &n) != AM355_OK || n > 256) return false;
+  int at = snprintf(buf, sizeof buf, "%u@", ctr);
+  for (size_t k = 0; k < n; k++) at += snprintf(buf + at, 3, "%02x", a[k]);
+  return napi_create_string_utf8(env, buf, (size_t)at, out) == napi_ok;
+}
+/* textLocate(ctx, ctr, Uint8Array actor, first, n) -> { length, runs: [{ elemId, pred, count, counter }] } = am355_text_locate: the
+ * elements [first, first + n) of a Text as runs of consecutive (elemId, pred) pairs, ids as strings */
+static napi_value js_text_locate(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5], out, runs_js, v;
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  double ctr = -1, first = -1, n = -1;
+  const uint8_t *actor = NULL;
+  size_t actor_len = 0;
+  if (argc < 5 || napi_get_value_double(env, argv[1], &ctr) != napi_ok || !get_u8_array(env, argv[2], &actor, &actor_len) ||
+      napi_get_value_double(env, argv[3], &first) != napi_ok || napi_get_value_double(env, argv[4], &n) != napi_ok || ctr < 0 || ctr > 4294967295.0 || first < 0 ||
+      n < 0 || first > 9007199254740991.0 || n > 9007199254740991.0) {
+    napi_throw_type_error(env, NULL, "textLocate takes a counter, the actor's bytes, a first position and a count");
+    return NULL;
+  }
+  const am355_text_run *runs = NULL;
+  uint32_t n_runs = 0;
+  uint64_t length = 0;
+  int rc = am355_text_locate(ctx, (uint64_t)ctr, actor, actor_len, (uint64_t)first, (uint64_t)n, &runs, &n_runs, &length);
+  if (rc) return throw_engine(env, ctx, rc);
+  NAPI_CALL(env, napi_create_object(env, &out));
+  NAPI_CALL(env, napi_create_double(env, (double)length, &v));
+  NAPI_CALL(env, napi_set_named_property(env, out, "length", v));
+  NAPI_CALL(env, napi_create_array_with_length(env, n_runs, &runs_js));
+  for (uint32_t r = 0; r < n_runs; r++) {
+    napi_value o;
+    NAPI_CALL(env, napi_create_object(env, &o));
+    if (!id_string(env, ctx, runs[r].elem_ctr, runs[r].elem_actor, &v)) { napi_throw_error(env, NULL, "textLocate: a run names an actor outside the table"); return NULL; }
+    NAPI_CALL(env, napi_set_named_property(env, o, "elemId", v));
+    if (!id_string(env, ctx, runs[r].pred_ctr, runs[r].pred_actor, &v)) { napi_throw_error(env, NULL, "textLocate: a run names an actor outside the table"); return NULL; }
+    NAPI_CALL(env, napi_set_named_property(env, o, "pred", v));
+    NAPI_CALL(env, napi_create_uint32(env, runs[r].count, &v));
+    NAPI_CALL(env, napi_set_named_property(env, o, "count", v));
+    NAPI_CALL(env, napi_get_boolean(env, (runs[r].flags & AM355_RUN_COUNTER) != 0, &v));
+    NAPI_CALL(env, napi_set_named_property(env, o, "counter", v));
+    NAPI_CALL(env, napi_set_element(env, runs_js, r, o));
+  }
+  NAPI_CALL(env, napi_set_named_property(env, out, "runs", runs_js));
+  return out;
+}
+/* textSplice(ctx, ctr, Uint8Array actor, start, deletions, Uint8Array utf8, Uint32Array valueOff, Uint8Array author, time, Uint8Array message)
+ * -> Uint8Array (the binary change; empty: there was nothing to do) = am355_text_splice: the patch is then read with fetchApplyIR */
+static napi_value js_text_splice(napi_env env, napi_callback_info info) {
+  size_t argc = 10;
+  napi_value argv[10];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  double ctr = -1, start = -1, deletions = -1, time = 0;
+  const uint8_t *actor = NULL, *utf8 = NULL, *author = NULL, *message = NULL;
+  size_t actor_len = 0, utf8_len = 0, author_len = 0, message_len = 0, n_off = 0;
+  uint32_t *off = NULL;
+  if (argc < 10 || napi_get_value_double(env, argv[1], &ctr) != napi_ok || !get_u8_array(env, argv[2], &actor, &actor_len) ||
+      napi_get_value_double(env, argv[3], &start) != napi_ok || napi_get_value_double(env, argv[4], &deletions) != napi_ok || !get_u8_array(env, argv[5], &utf8, &utf8_len) ||
+      !get_u32_array(env, argv[6], &off, &n_off) || !get_u8_array(env, argv[7], &author, &author_len) || napi_get_value_double(env, argv[8], &time) != napi_ok ||
+      !get_u8_array(env, argv[9], &message, &message_len) || ctr < 0 || ctr > 4294967295.0 || start < 0 || deletions < 0 || start > 9007199254740991.0 ||
+      deletions > 9007199254740991.0 || n_off < 1 || off[n_off - 1] != utf8_len || message_len > 0xffffffffu || time != (double)(int64_t)time) {
+    napi_throw_type_error(env, NULL, "textSplice takes (ctx, counter, actor bytes, start, deletions, utf8, value offsets, author bytes, time, message bytes)");
+    return NULL;
+  }
+  const uint8_t *bytes = NULL;
+  size_t len = 0;
+  int rc = am355_text_splice(ctx, (uint64_t)ctr, actor, actor_len, (uint64_t)start, (uint64_t)deletions, utf8, off, (uint32_t)(n_off - 1), author, author_len, (int64_t)time,
+                             message, (uint32_t)message_len, &bytes, &len);
+  if (rc) return throw_engine(env, ctx, rc);
+  napi_value ab = copy_to_arraybuffer(env, bytes, len), change;
+  if (!ab) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &change));
+  return change;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"create", NULL, js_create, NULL, NULL, NULL, napi_enumerable, NULL},
@@ -1139,6 +1232,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"setGraphProbeMin", NULL, js_set_graph_probe_min, NULL, NULL, NULL, napi_enumerable, NULL},
       {"graphQueryCalls", NULL, js_graph_query_calls, NULL, NULL, NULL, napi_enumerable, NULL},
       {"objectText", NULL, js_object_text, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"textLocate", NULL, js_text_locate, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"textSplice", NULL, js_text_splice, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomBuild", NULL, js_bloom_build, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomProbe", NULL, js_bloom_probe, NULL, NULL, NULL, napi_enumerable, NULL},
       {"fetchApplyIR", NULL, js_fetch_apply_ir, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -11,6 +11,8 @@
 //   load / save / getAllChanges after load                         (SURVEY.md a21, 8f-1, 8f-3)
 //   applyLocalChange(state, request) -> [state', patch, change]    (backend/backend.js:54-91) for the states applyChanges is served on:
 //                                                                  the change is built on the device (local_change.js, am355_apply_local_change)
+//   spliceText(state, objectId, start, deletions, strings, {actor, time, message}) / locateText(state, objectId, first, n)   ADDITIONS: a
+//     Text edited by position, for hosts without a frontend document (am355_text_splice / am355_text_locate; see below)
 //   getText(state, objectId) / getTextInfo(state, objectId)        ADDITIONS to the reference's surface: the string of a Text object read on
 //                                                                  the device from the edit records (am355_object_text), no patch built
 //   getChanges / getChangeByHash / getMissingDeps / getChangesAdded and the sync helpers over them: index lists from the engine's
@@ -135,7 +137,7 @@ function contextOf(gen) {
   if (e) { e.used = ++tick; ctx = e.ctx }
   return e || null
 }
-const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, gpuChangesAdded: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0, gpuText: 0, textFallbacks: 0 }   // (diagnostics: which path served the calls)
+const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, gpuChangesAdded: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0, gpuText: 0, textFallbacks: 0, gpuSplice: 0, spliceFallbacks: 0 }   // (diagnostics: which path served the calls)
 
 function isFrozenCheck(backend) {
   // reference util.js:1-10
@@ -969,6 +971,147 @@ function getTextInfo(backend, objectId) {
 }
 const getText = (backend, objectId) => getTextInfo(backend, objectId).text
 
+// ---- a Text edited by position: spliceText / locateText (additions; nothing of backend/index.js:1-8 changes) ----
+// spliceText(backend, objectId, start, deletions, stringOrArrayOfStrings, {actor, time, message}) -> [backend', patch, binaryChange]: one
+// context.splice of the reference's frontend (frontend/context.js:441-502; what text.deleteAt / text.insertAt come down to) for a host
+// WITHOUT a frontend document. The engine resolves the positions to elemIds and preds on the device, builds the change request the
+// frontend would have made and applies it (am355_text_splice) -- while the state's context is live, the state's queue is not held back
+// and the state is the engine's. A JS string is split by code point ([...s]), as text.insertAt(i, ...s) does; an array is taken as it
+// is, one element per string. Nothing to delete and nothing to insert: [backend, null, null], nothing is applied.
+// THE CALLER OWNS THE ACTOR AND THE ORDER OF ITS CALLS: seq is the actor's clock entry + 1 and the deps are the state's heads, as for a
+// frontend with nothing in flight. A frontend document that sits on the same backend does not learn of the change by itself.
+// Otherwise, and for AM355_E_UNSUPPORTED, the JS path: the whole-document patch folded into (elemId, pred) per element by the rule of
+// updateTextObject (frontend/apply_patch.js:231-255: insert -> opId, multi-insert -> the elemId, update -> opId with the elemId kept),
+// the request built by context.js's rule, this module's own applyLocalChange. Out of bounds: a RangeError with the reference's text;
+// a Counter among the deleted elements: a TypeError with the text of context.js:471 (the reference's frontend itself throws it for
+// lists only: for a Text it looks the element up as object[index], finds nothing, and deletes the counter) -- on both paths.
+// locateText(backend, objectId, first, n) -> { length, runs: [{ elemId, pred, count, counter }] }: the elements [first, first + n) as the
+// runs context.splice would merge into multiOp deletions (am355_text_locate, or the same fold).
+let spliceOnEngine = true   // _setSpliceOnEngine(false): every call takes the JS path (tests, A/B)
+const COUNTER_IN_TEXT = 'Unsupported operation: deleting a counter from a list'
+function elementsFromPatch(patch, objectId) {
+  let found = null
+  const walk = diff => {
+    if (found) return
+    if (diff.objectId === objectId) { found = diff; return }
+    if (diff.props) for (const key of Object.keys(diff.props)) for (const id of Object.keys(diff.props[key])) if (diff.props[key][id].objectId) walk(diff.props[key][id])
+    if (diff.edits) for (const e of diff.edits) if (e.value && e.value.objectId) walk(e.value)
+  }
+  walk(patch.diffs)
+  if (!found) throw new RangeError(`no such object: ${objectId}`)
+  if (found.type !== 'text') throw new RangeError('not a Text object')
+  const elems = []
+  for (const e of found.edits) {
+    if (e.action === 'insert') elems.splice(e.index, 0, { elemId: e.elemId, pred: e.opId, counter: e.value.datatype === 'counter' })
+    else if (e.action === 'multi-insert') {
+      const at = e.elemId.indexOf('@'), ctr = Number(e.elemId.slice(0, at)), actor = e.elemId.slice(at)
+      const made = e.values.map((v, k) => ({ elemId: (ctr + k) + actor, pred: (ctr + k) + actor, counter: e.datatype === 'counter' }))
+      for (let k = 0; k < made.length; k += 4096) elems.splice(e.index + k, 0, ...made.slice(k, k + 4096))
+    } else if (e.action === 'update') elems[e.index] = { elemId: elems[e.index].elemId, pred: e.opId, counter: e.value.datatype === 'counter' }
+    else throw new RangeError('a Text element that shows rows but no value: positions through the patch')
+  }
+  return elems
+}
+function runsOf(elems) {
+  const runs = [], parse = id => { const at = id.indexOf('@'); return [Number(id.slice(0, at)), id.slice(at)] }
+  let lastElem = null, lastPred = null
+  for (const el of elems) {
+    const e = parse(el.elemId), p = parse(el.pred), run = runs[runs.length - 1]
+    if (run && lastElem[1] === e[1] && lastElem[0] + 1 === e[0] && lastPred[1] === p[1] && lastPred[0] + 1 === p[0]) {
+      run.count++
+      run.counter = run.counter || el.counter
+    } else runs.push({ elemId: el.elemId, pred: el.pred, count: 1, counter: el.counter })
+    lastElem = e; lastPred = p
+  }
+  return runs
+}
+const outOfBounds = (start, deletions, length) => new RangeError(`${deletions} deletions starting at index ${start} are out of bounds for list of length ${length}`)
+const splitValues = values => (typeof values === 'string' ? [...values] : Array.isArray(values) ? values : values === undefined || values === null ? [] : null)
+const engineServesText = (backend, m) => !JS_ONLY && spliceOnEngine && m && Number(m[1]) <= 0xffffffff && backend.state instanceof GpuState && !backend.state.js &&
+  !heldBack(backend.state) && contextOf(backend.state.generation)
+
+function gpuSpliceText(backend, m, start, deletions, values, actor, time, message) {
+  const at = contextForApply(backend)
+  if (!at || at.handed) return null
+  const knownBefore = at.docLineage ? !!addon.hashGraphKnown(ctx, -1) : true
+  const parts = values.map(v => Buffer.from(v, 'utf8')), off = new Uint32Array(parts.length + 1)
+  parts.forEach((b, k) => { off[k + 1] = off[k] + b.length })
+  let binaryChange
+  try {
+    binaryChange = addon.textSplice(ctx, Number(m[1]), new Uint8Array(Buffer.from(m[2], 'hex')), start, deletions, new Uint8Array(Buffer.concat(parts)), off,
+      new Uint8Array(Buffer.from(actor, 'hex')), time, new Uint8Array(Buffer.from(message, 'utf8')))
+  } catch (e) {
+    // out of bounds, no such Text, a counter: decided before the state is touched (am355.h); anything else may have dropped it
+    if (e.am355Code !== AM355_E_ARG && !(e.am355Code === AM355_E_INVALID && e.message === COUNTER_IN_TEXT)) at.entry.generation = 0
+    throw e
+  }
+  if (binaryChange.length === 0) return [backend, null, null]
+  const patch = materialize(addon.fetchApplyIR(ctx, true))
+  const graphFirst = at.docLineage && !knownBefore && !!addon.hashGraphKnown(ctx, -1)
+  const result = stateAfterApply(at, [binaryChange], patch, graphFirst)
+  const own = hexOfHash(result[0].state, result[0].state.hashes.length / 32 - 1)
+  const heads = patch.deps.concat([own]).sort()
+  result[0].state.heads = heads
+  result[0].heads = heads
+  backend.frozen = true
+  return [result[0], patch, binaryChange]
+}
+
+function spliceText(backend, objectId, start, deletions, values, options = {}) {
+  isFrozenCheck(backend)
+  const list = splitValues(values), { actor, time = 0, message = '' } = options
+  if (!list || !list.every(v => typeof v === 'string')) throw new TypeError('spliceText inserts strings: a string, or an array of strings')
+  if (typeof actor !== 'string' || !/^([0-9a-f]{2})+$/.test(actor)) throw new TypeError('spliceText needs the actor id (lowercase hex) in its options')
+  if (!Number.isSafeInteger(start) || !Number.isSafeInteger(deletions) || !Number.isSafeInteger(time)) throw new TypeError('start, deletions and time are integers')
+  const m = typeof objectId === 'string' ? OBJECT_ID.exec(objectId) : null
+  if (start >= 0 && deletions >= 0 && engineServesText(backend, m)) {
+    try {
+      const result = gpuSpliceText(backend, m, start, deletions, list, actor, time, message)
+      if (result) { counters.gpuSplice++; return result }
+    } catch (e) {
+      if (e.am355Code === AM355_E_ARG) throw new RangeError(e.message)
+      if (e.am355Code === AM355_E_INVALID && e.message === COUNTER_IN_TEXT) throw new TypeError(e.message)
+      if (e.am355Code !== AM355_E_INVALID && e.am355Code !== AM355_E_UNSUPPORTED) throw e
+    }
+  }
+  counters.spliceFallbacks++
+  const whole = getPatch(backend), elems = elementsFromPatch(whole, objectId)
+  if (start < 0 || deletions < 0 || start > elems.length - deletions) throw outOfBounds(start, deletions, elems.length)
+  if (deletions === 0 && list.length === 0) return [backend, null, null]
+  const ops = []
+  for (const run of runsOf(elems.slice(start, start + deletions))) {
+    if (run.counter) throw new TypeError(COUNTER_IN_TEXT)
+    const op = { action: 'del', obj: objectId, elemId: run.elemId, insert: false, pred: [run.pred] }
+    if (run.count > 1) op.multiOp = run.count
+    ops.push(op)
+  }
+  if (list.length > 0) {
+    const op = { action: 'set', obj: objectId, elemId: start ? elems[start - 1].elemId : '_head', insert: true }
+    if (list.length > 1) op.values = list; else op.value = list[0]
+    op.pred = []
+    ops.push(op)
+  }
+  // (the deps are the state's heads; applyLocalChange adds the actor's last hash and keeps every hash once, backend.js:73-81)
+  return applyLocalChange(backend, { actor, seq: (whole.clock[actor] || 0) + 1, startOp: whole.maxOp + 1, deps: whole.deps.slice(), time, message, ops })
+}
+
+function locateText(backend, objectId, first, n) {
+  isFrozenCheck(backend)
+  if (!Number.isSafeInteger(first) || !Number.isSafeInteger(n) || first < 0 || n < 0) throw new RangeError('first and n are non-negative integers')
+  const m = typeof objectId === 'string' ? OBJECT_ID.exec(objectId) : null
+  if (engineServesText(backend, m)) {
+    try {
+      return addon.textLocate(ctx, Number(m[1]), new Uint8Array(Buffer.from(m[2], 'hex')), first, n)
+    } catch (e) {
+      if (e.am355Code === AM355_E_ARG) throw new RangeError(e.message)
+      if (e.am355Code === undefined) throw e
+    }
+  }
+  const elems = elementsFromPatch(getPatch(backend), objectId)
+  if (first + n > elems.length) throw new RangeError(`elements [${first}, ${first} + ${n}) are out of bounds for a Text of length ${elems.length}`)
+  return { length: elems.length, runs: runsOf(elems.slice(first, first + n)) }
+}
+
 module.exports = {
   init, load, loadChanges, getPatch, getHeads, free, save, getAllChanges, getChanges, getChangeByHash, getMissingDeps,
   clone: backend => { noteGraphQuery(backend); return ref().clone(hydrate(backend)) },
@@ -977,6 +1120,8 @@ module.exports = {
   getChangesAdded,
   // additions: the string of a Text object / {text, length, strings}, read on the device (see above)
   getText, getTextInfo,
+  // additions: a Text edited by position / positions resolved to ids, on the device (see above)
+  spliceText, locateText,
   // sync protocol: the reference's own backend/sync.js bound to this module (boundSync above)
   generateSyncMessage: (...a) => syncModule().generateSyncMessage(...a),
   receiveSyncMessage: (...a) => syncModule().receiveSyncMessage(...a),
@@ -1001,6 +1146,7 @@ module.exports = {
   _graphQueryCalls: () => contexts.reduce((s, e) => { const w = addon.graphQueryCalls(e.ctx); return [s[0] + w[0], s[1] + w[1]] }, [0, 0]),
   _setGraphProbeMin: n => { graphProbeMin = n; for (const e of contexts) addon.setGraphProbeMin(e.ctx, n) },
   _setTextOnEngine: on => { textOnEngine = !!on },
+  _setSpliceOnEngine: on => { spliceOnEngine = !!on },
   _textFromPatch: textFromPatch,   // (bench_text.js: the JS path's fold by itself)
   _applyProfile: profile,
   _hydrate: hydrate   // (tests: the reference handle of an engine state, made the way the state came to be)

@@ -606,6 +606,57 @@ int am355_object_text_calls(const am355_ctx *ctx, uint64_t out[2]);   /* served 
 int am355_set_text_pinned_max(am355_ctx *ctx, uint64_t bytes);
 int am355_text_limits(uint32_t out[4]);
 
+/*
+ * A Text edited by POSITION (csrc/am355_locate.hip): the inverse of am355_object_text. A change request names list elements by elemId
+ * and a deleted value by its op id (`pred`); a host that keeps a Text on the engine and has no frontend document knows positions only.
+ * am355_text_locate resolves the elements [first, first + n) of a Text to their ids on the device, compressed into the runs the
+ * reference's frontend would merge into `multiOp` deletions (frontend/context.js:474-492): run = `count` elements whose elemIds are
+ * (elem_ctr + i, elem_actor) and whose preds are (pred_ctr + i, pred_actor), i = 0 .. count - 1. Actors are ranks, as in am355_patch_ir.
+ * The pred of a Text element is the op id of the last edit of its index (frontend/apply_patch.js:231-255: insert -> opId, multi-insert
+ * -> the elemId, update -> opId with the elemId kept). flags & AM355_RUN_COUNTER: some element of the run is a Counter. *runs is pinned
+ * memory owned by the context, valid until the next call on ctx; *length = the Text's length (text.length). n == 0 is legal and returns
+ * the length. It reads only: the state, what serves the next am355_apply_changes and the host copies of the tables stay as they were
+ * (edit tables that in-place merges left stale are rebuilt once, as for am355_object_text). Same contexts and errors as
+ * am355_object_text (AM355_E_STATE, sharded AM355_E_UNSUPPORTED, AM355_E_ARG "no such object: ..." / "not a Text object"); first + n >
+ * length: AM355_E_ARG; a Text element that shows rows but no value (a `remove` record: an increment of a deleted counter):
+ * AM355_E_UNSUPPORTED; records that contradict each other: AM355_E_DEVICE (nothing is read or written out of range).
+ *
+ * am355_text_splice: one context.splice(path, start, deletions, insertions) of the reference's frontend (context.js:441-502; what
+ * text.deleteAt / text.insertAt come down to) on the Text the context holds: it locates [start - 1, start + deletions) in one query,
+ * builds exactly the change request the frontend would hand to Backend.applyLocalChange -- one `del` op per run of the deleted elements
+ * (multiOp = count), then the insertion behind element start - 1 (`_head` for start == 0): one `set` with `values` for several strings,
+ * a plain inserting `set` for one --, with seq = the author's clock entry + 1, startOp = maxOp + 1 and deps = the state's heads without
+ * the author's last change, and applies it through am355_apply_local_change (small path, bulk path, patch and envelope as there:
+ * am355_apply_patch_json / am355_fetch_apply_ir / am355_apply_local_envelope give the patch). Value i is the UTF-8 string
+ * utf8[value_off[i] .. value_off[i + 1]): one list element each. *change / *len: the binary change, as am355_apply_local_change returns
+ * it. The caller owns the author and the order of its calls: this path is for hosts WITHOUT a frontend document.
+ * Decided before the state is touched (a document context is at most turned into the state of its rebuilt changes): start > length -
+ * deletions: AM355_E_ARG with the reference's RangeError text ("<deletions> deletions starting at index <start> are out of bounds for
+ * list of length <length>"); a Counter among the deleted elements: AM355_E_INVALID with its TypeError text ("Unsupported operation:
+ * deleting a counter from a list"); deletions == 0 && n_values == 0: AM355_OK, *len = 0, nothing applied; the errors of
+ * am355_text_locate; queued changes in the state: AM355_E_UNSUPPORTED. What am355_apply_local_change refuses stays refused with its code.
+ * am355_text_splice_calls: out[0] splices served, out[1] refused (whatever the code), out[2] kernel launches of the locate half of both
+ * calls (the library scan counts as one). am355_text_locate_limits: the sizes at which the kernels take another path (tests): out[0] =
+ * elements one workgroup of the locate kernel takes, out[1] = elements up to which the scan of the head bits is one workgroup, out[2] =
+ * runs written straight into pinned memory (the ones behind go to device memory and down in one copy).
+ * A COUNTER INSIDE A TEXT: context.js:455-471 throws for a counter in a list; for a Text the reference's frontend looks the element up
+ * as object[index], which a Text does not have, does not throw and deletes the counter. am355_text_splice refuses as stated above.
+ */
+enum { AM355_RUN_COUNTER = 1u };                                           /* am355_text_run.flags */
+typedef struct { uint32_t elem_ctr, elem_actor, pred_ctr, pred_actor, count, flags; } am355_text_run;   /* actors: ranks, as in am355_patch_ir */
+int am355_text_locate(am355_ctx *ctx, uint64_t obj_ctr, const uint8_t *obj_actor, size_t actor_len,
+                      uint64_t first, uint64_t n, const am355_text_run **runs, uint32_t *n_runs, uint64_t *length);
+int am355_text_splice(am355_ctx *ctx, uint64_t obj_ctr, const uint8_t *obj_actor, size_t actor_len,
+                      uint64_t start, uint64_t deletions,
+                      const uint8_t *utf8, const uint32_t *value_off, uint32_t n_values,   /* value i = utf8[value_off[i] .. value_off[i+1]) */
+                      const uint8_t *author, size_t author_len, int64_t time, const uint8_t *message, uint32_t message_len,
+                      const uint8_t **change, size_t *len);
+int am355_text_splice_calls(const am355_ctx *ctx, uint64_t out[3]);   /* splices served | refused | device launches of the locate half */
+int am355_text_locate_limits(uint32_t out[3]);                        /* the sizes at which the kernels switch path, for the tests */
+/* The raw id of the actor with that rank (the ranks of am355_text_run and am355_patch_ir), without fetching the patch tables: *bytes is
+ * owned by ctx and valid until the next call that changes the state. AM355_E_STATE: no replayed state; AM355_E_ARG: no such rank. */
+int am355_actor_of_rank(const am355_ctx *ctx, uint32_t rank, const uint8_t **bytes, size_t *len);
+
 /* ---- diagnostics: device primitives exposed for kernel-level tests ---- */
 /* The device hash table of the queries above, driven by itself: a table over table_hashes (n_table x 32 bytes) is built and
  * queries (n_queries x 32 bytes) are probed, both on the device; out_idx[q] = index of the table hash equal to query q (the smallest,
