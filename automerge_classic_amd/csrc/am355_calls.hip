@@ -998,3 +998,8 @@ int sync_bloom_impl(am355_ctx* c, const uint32_t* idx, uint32_t n, uint32_t num_
 // positions of a Text resolved to ids, and the edit by position built from them (am355_text_locate, am355_text_splice): likewise
 // ---------------------------------------------------------------------------------------------------------
 #include "am355_locate.hip"
+
+// ---------------------------------------------------------------------------------------------------------
+// elemIds of a Text resolved to positions, deleted elements included (am355_text_position): likewise
+// ---------------------------------------------------------------------------------------------------------
+#include "am355_position.hip"

@@ -2,7 +2,7 @@
 // am355_ctx, error helpers, the AM355_TRACE lap type. am355_api.hip: entry points; am355_stage.hip: staging; am355_replay.hip: host
 // scheduler, plan, device buffers, and the two sequences of named phases that orchestrate the device stages -- the full replay
 // (replay_impl over a Stage1) and the resident applyChanges (replay_resident over a ResidentBatch); am355_calls.hip: patch IR,
-// applyChanges, dependency graph, Bloom filters -- and, included at its end, am355_graph.hip: the hash-graph queries, and am355_text.hip: the string of a Text object, and am355_locate.hip: positions of a Text to ids, the positional edit; am355_save.hip: save + history after load; am355_shard.hip: objectId sharding.
+// applyChanges, dependency graph, Bloom filters -- and, included at its end, am355_graph.hip: the hash-graph queries, and am355_text.hip: the string of a Text object, and am355_locate.hip: positions of a Text to ids, the positional edit, and am355_position.hip: elemIds of a Text to positions; am355_save.hip: save + history after load; am355_shard.hip: objectId sharding.
 #pragma once
 #include "../../include/am355.h"
 #include "am355_decode.h"
@@ -587,6 +587,11 @@ struct am355_ctx {
   HostBuf h_loc_runs, h_loc_sig;                   // pinned: the runs (valid until the next call) | the words the device signals + their sequence word
   uint32_t loc_seq = 0;
   uint64_t n_splice_served = 0, n_splice_refused = 0, n_locate_launches = 0;   // am355_text_splice_calls
+  // am355_text_position (am355_position.hip): elemIds of a Text resolved to positions on the device, by a search in the stored list order (d_pos)
+  DevBuf d_posq;                                   // result words | rec_pos | the queries and the results behind LOCATE_PINNED_RUNS
+  HostBuf h_pos_out, h_pos_ids, h_pos_sig;         // pinned: the results (valid until the next call) | the queries | the words the device signals + their sequence word
+  uint32_t pos_seq = 0;
+  uint64_t n_position_served = 0, n_position_launches = 0;   // am355_text_position_calls
   DevBuf d_map_alt, d_mapmerge;                    // the other map table | the stage's scratch
   am355_ir_map* map_alt_ptr = nullptr;             // whichever of the two map tables c->ir.map does NOT point to (null: not set up since the last carve)
   std::string resident_why;                        // why the last attempt fell back (diagnostics, AM355_TRACE)

@@ -46,6 +46,9 @@ class TextInfo(ctypes.Structure):
 # am355_text_run: a run of consecutive (elemId, pred) pairs of a Text (actors: ranks of the engine's actor table)
 TEXT_RUN_DTYPE = np.dtype([("elem_ctr", "<u4"), ("elem_actor", "<u4"), ("pred_ctr", "<u4"), ("pred_actor", "<u4"), ("count", "<u4"), ("flags", "<u4")])
 RUN_COUNTER = 1
+ELEM_ID_DTYPE = np.dtype([("ctr", "<u4"), ("actor", "<u4")])              # am355_elem_id
+ELEM_POS_DTYPE = np.dtype([("position", "<u4"), ("status", "<u4")])       # am355_elem_pos
+POS_UNKNOWN, POS_VISIBLE, POS_DELETED, POS_COUNTER = 0, 1, 2, 0x100       # AM355_POS_*
 
 
 class EngineError(RuntimeError):
@@ -383,6 +386,15 @@ def _bind(path):
         L.am355_text_locate_limits.argtypes = [vp]
         for f in ("am355_text_locate", "am355_text_splice", "am355_text_splice_calls", "am355_text_locate_limits"):
             getattr(L, f).restype = ctypes.c_int
+    if hasattr(L, "am355_text_position"):   # (libraries of earlier commits, loaded for an A/B run, end before these)
+        L.am355_text_position.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_size_t, vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
+        L.am355_rank_of_actor.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(u32)]
+        L.am355_actor_of_rank.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+        L.am355_actor_of_rank.restype = ctypes.c_int
+        L.am355_text_position_calls.argtypes = [vp, vp]
+        L.am355_text_position_limits.argtypes = [vp]
+        for f in ("am355_text_position", "am355_rank_of_actor", "am355_text_position_calls", "am355_text_position_limits"):
+            getattr(L, f).restype = ctypes.c_int
     L.am355_get_raw.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32)]
     L.am355_doc_changes.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_void_p)]
     L.am355_apply_changes.argtypes = [vp, vp, u64p, u32]
@@ -694,6 +706,61 @@ class Engine:
         """(elements per workgroup of the locate kernel, elements the head scan takes in one workgroup, runs written straight to pinned memory)."""
         out = (ctypes.c_uint32 * 3)()
         self._check(self._L.am355_text_locate_limits(out))
+        return tuple(int(x) for x in out)
+
+    def rank_of_actor(self, actor):
+        """The rank of an actor (hex id) in the state's actor table (am355_rank_of_actor), None when the state does not know the actor.
+        Ranks are renumbered when a new actor arrives: ask per call."""
+        raw = bytes.fromhex(actor)
+        buf = (ctypes.c_uint8 * max(len(raw), 1)).from_buffer_copy(raw or b"\0")
+        rank = ctypes.c_uint32()
+        rc = self._L.am355_rank_of_actor(self._h, ctypes.cast(buf, ctypes.c_void_p), len(raw), ctypes.byref(rank))
+        if rc == -2:   # AM355_E_ARG: no such actor
+            return None
+        self._check(rc)
+        return int(rank.value)
+
+    def actor_of_rank(self, rank):
+        """The id (hex) of the actor with that rank (am355_actor_of_rank): the inverse of rank_of_actor."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._L.am355_actor_of_rank(self._h, int(rank), ctypes.byref(p), ctypes.byref(n)))
+        return ctypes.string_at(p, n.value).hex()
+
+    def text_positions(self, object_id, elem_ids):
+        """ElemIds ("ctr@actorhex") of a Text resolved to positions on the device (am355_text_position): ([(status, position,
+        is_counter)], length). status: POS_VISIBLE (position = the element's index), POS_DELETED (position = the visible elements in
+        front of where it stood), POS_UNKNOWN (no applied change inserted such an element into this Text; position 0). The caret
+        directly behind a known element is position + (status == POS_VISIBLE). Actors are translated to ranks here, per call."""
+        ctr, actor, buf = self._object_id(object_id)
+        q = np.zeros(len(elem_ids), dtype=ELEM_ID_DTYPE)
+        ranks = {}
+        for k, e in enumerate(elem_ids):
+            c, _, a = str(e).partition("@")
+            if not c.isdigit() or not a or len(a) % 2:
+                raise ValueError(f"not an element id: {e!r}")
+            if a not in ranks:
+                ranks[a] = self.rank_of_actor(a)
+            # (a counter beyond 32 bits names no row: asked as an unknown actor's)
+            known = ranks[a] is not None and int(c) <= 0xFFFFFFFF
+            q[k] = (int(c) if known else 0, ranks[a] if known else 0xFFFFFFFF)
+        p, length = ctypes.c_void_p(), ctypes.c_uint64()
+        self._check(self._L.am355_text_position(self._h, ctr, ctypes.cast(buf, ctypes.c_void_p), len(actor), q.ctypes.data if len(q) else None, len(q), ctypes.byref(p),
+                                                ctypes.byref(length)))
+        out = np.zeros(len(q), dtype=ELEM_POS_DTYPE)
+        if len(q):
+            ctypes.memmove(out.ctypes.data, p, len(q) * ELEM_POS_DTYPE.itemsize)
+        return [(int(s) & 3, int(pos), bool(int(s) & POS_COUNTER)) for pos, s in zip(out["position"], out["status"])], int(length.value)
+
+    def text_position_calls(self):
+        """(text_positions calls served, kernel launches they made)."""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self._L.am355_text_position_calls(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def text_position_limits(self):
+        """(queries one workgroup of the resolve kernel takes, results written straight to pinned memory)."""
+        out = (ctypes.c_uint32 * 2)()
+        self._check(self._L.am355_text_position_limits(out))
         return tuple(int(x) for x in out)
 
     def set_text_pinned_max(self, n_bytes):

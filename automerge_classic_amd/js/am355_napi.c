@@ -1196,6 +1196,57 @@ static napi_value js_text_splice(napi_env env, napi_callback_info info) {
   return change;
 }
 
+/* rankOfActor(ctx, Uint8Array actor) -> the actor's rank in the engine's table, -1 when the state does not know the actor
+ * (am355_rank_of_actor). Ranks are renumbered when a new actor arrives: asked per call. */
+static napi_value js_rank_of_actor(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2], v;
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  const uint8_t *actor = NULL;
+  size_t actor_len = 0;
+  if (argc < 2 || !get_u8_array(env, argv[1], &actor, &actor_len)) {
+    napi_throw_type_error(env, NULL, "rankOfActor takes the actor's bytes");
+    return NULL;
+  }
+  uint32_t rank = 0;
+  int rc = am355_rank_of_actor(ctx, actor, actor_len, &rank);
+  if (rc && rc != AM355_E_ARG) return throw_engine(env, ctx, rc);
+  NAPI_CALL(env, napi_create_double(env, rc ? -1.0 : (double)rank, &v));
+  return v;
+}
+/* textPositions(ctx, ctr, Uint8Array actor, Uint32Array ids) -> { length, words: Uint32Array } = am355_text_position. ids: (counter, actor
+ * rank) pairs, rank 0xffffffff for an actor the state does not know; words: (position, status | flags) pairs, AM355_POS_* */
+static napi_value js_text_positions(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4], out, v;
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  double ctr = -1;
+  const uint8_t *actor = NULL;
+  size_t actor_len = 0, n_words = 0;
+  uint32_t *ids = NULL;
+  if (argc < 4 || napi_get_value_double(env, argv[1], &ctr) != napi_ok || !get_u8_array(env, argv[2], &actor, &actor_len) || !get_u32_array(env, argv[3], &ids, &n_words) ||
+      ctr < 0 || ctr > 4294967295.0 || (n_words & 1) || n_words / 2 > 0xffffffffu) {
+    napi_throw_type_error(env, NULL, "textPositions takes a counter, the actor's bytes and a Uint32Array of (counter, rank) pairs");
+    return NULL;
+  }
+  const am355_elem_pos *pos = NULL;
+  uint64_t length = 0;
+  int rc = am355_text_position(ctx, (uint64_t)ctr, actor, actor_len, (const am355_elem_id *)ids, (uint32_t)(n_words / 2), &pos, &length);
+  if (rc) return throw_engine(env, ctx, rc);
+  NAPI_CALL(env, napi_create_object(env, &out));
+  NAPI_CALL(env, napi_create_double(env, (double)length, &v));
+  NAPI_CALL(env, napi_set_named_property(env, out, "length", v));
+  napi_value ab = copy_to_arraybuffer(env, (const uint8_t *)pos, n_words * 4), words;
+  if (!ab) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, n_words, ab, 0, &words));
+  NAPI_CALL(env, napi_set_named_property(env, out, "words", words));
+  return out;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"create", NULL, js_create, NULL, NULL, NULL, napi_enumerable, NULL},
@@ -1234,6 +1285,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"objectText", NULL, js_object_text, NULL, NULL, NULL, napi_enumerable, NULL},
       {"textLocate", NULL, js_text_locate, NULL, NULL, NULL, napi_enumerable, NULL},
       {"textSplice", NULL, js_text_splice, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"textPositions", NULL, js_text_positions, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"rankOfActor", NULL, js_rank_of_actor, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomBuild", NULL, js_bloom_build, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomProbe", NULL, js_bloom_probe, NULL, NULL, NULL, napi_enumerable, NULL},
       {"fetchApplyIR", NULL, js_fetch_apply_ir, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -11,6 +11,7 @@
 //   load / save / getAllChanges after load                         (SURVEY.md a21, 8f-1, 8f-3)
 //   applyLocalChange(state, request) -> [state', patch, change]    (backend/backend.js:54-91) for the states applyChanges is served on:
 //                                                                  the change is built on the device (local_change.js, am355_apply_local_change)
+//   positionsOfText(state, objectId, elemIds)   ADDITION: where elements of a Text stand now, deleted ones included (am355_text_position; see below)
 //   spliceText(state, objectId, start, deletions, strings, {actor, time, message}) / locateText(state, objectId, first, n)   ADDITIONS: a
 //     Text edited by position, for hosts without a frontend document (am355_text_splice / am355_text_locate; see below)
 //   getText(state, objectId) / getTextInfo(state, objectId)        ADDITIONS to the reference's surface: the string of a Text object read on
@@ -137,7 +138,7 @@ function contextOf(gen) {
   if (e) { e.used = ++tick; ctx = e.ctx }
   return e || null
 }
-const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, gpuChangesAdded: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0, gpuText: 0, textFallbacks: 0, gpuSplice: 0, spliceFallbacks: 0 }   // (diagnostics: which path served the calls)
+const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, gpuChangesAdded: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0, gpuText: 0, textFallbacks: 0, gpuSplice: 0, spliceFallbacks: 0, gpuPosition: 0, positionFallbacks: 0 }   // (diagnostics: which path served the calls)
 
 function isFrozenCheck(backend) {
   // reference util.js:1-10
@@ -1112,6 +1113,111 @@ function locateText(backend, objectId, first, n) {
   return { length: elems.length, runs: runsOf(elems.slice(first, first + n)) }
 }
 
+// ---- elemIds of a Text resolved to positions: positionsOfText (an addition; nothing of backend/index.js:1-8 changes) ----
+// positionsOfText(backend, objectId, elemIds) -> { length, positions: [{ status: 'visible' | 'deleted' | 'unknown', position, counter }] }: where
+// the elements stand NOW -- what keeps a caret, a selection or a comment anchor alive while remote changes arrive. visible: position =
+// the element's index; deleted: the element was inserted into this Text and shows no value any more, position = the number of visible
+// elements in front of where it stood; unknown: no applied change inserted such an element into this Text (position 0). The caret
+// directly behind a known element is position + (status === 'visible').
+// Served by the engine (am355_text_position: a search in the stored list order, deleted elements included) under the conditions of
+// getText, for a state made of changes; a loaded document that has not been changed yet takes the JS path (the engine would first turn
+// its context into the state of the document's rebuilt changes, which this module's bookkeeping of loaded documents does not expect).
+// Otherwise, and on AM355_E_UNSUPPORTED, the JS path, slow by design and THE DEFINITION: per element a PROBE on the reference's backend
+// -- a change of a fresh actor with startOp = maxOp + 1, deps = heads and the one op {set, insert, elemId, pred: []}, applied to a clone
+// of the state; its op id is the greatest, so it lands directly behind the element, and the patch reports it at index = the caret
+// position behind it. A probe the reference rejects for a missing reference element gives 'unknown'. An element is visible iff the
+// whole-document patch, folded as the frontend folds it, shows it.
+let positionOnEngine = true   // _setPositionOnEngine(false): every call takes the JS path (tests, A/B)
+const ELEM_ID = /^(\d{1,16})@((?:[0-9a-f]{2})+)$/
+const POS_STATUS = ['unknown', 'visible', 'deleted']
+function shownElemIds(patch, objectId) {
+  let found = null
+  const walk = diff => {
+    if (found) return
+    if (diff.objectId === objectId) { found = diff; return }
+    if (diff.props) for (const key of Object.keys(diff.props)) for (const id of Object.keys(diff.props[key])) if (diff.props[key][id].objectId) walk(diff.props[key][id])
+    if (diff.edits) for (const e of diff.edits) if (e.value && e.value.objectId) walk(e.value)
+  }
+  walk(patch.diffs)
+  if (!found) throw new RangeError(`no such object: ${objectId}`)
+  if (found.type !== 'text') throw new RangeError('not a Text object')
+  const elems = []   // { elemId, counter } per index, as updateTextObject builds them (a `remove` splices what is there, as in textFromPatch)
+  for (const e of found.edits) {
+    if (e.action === 'insert') elems.splice(e.index, 0, { elemId: e.elemId, counter: e.value.datatype === 'counter' })
+    else if (e.action === 'multi-insert') {
+      const at = e.elemId.indexOf('@'), ctr = Number(e.elemId.slice(0, at)), actor = e.elemId.slice(at)
+      const made = e.values.map((v, k) => ({ elemId: (ctr + k) + actor, counter: e.datatype === 'counter' }))
+      for (let k = 0; k < made.length; k += 4096) elems.splice(e.index + k, 0, ...made.slice(k, k + 4096))
+    } else if (e.action === 'update') { if (elems[e.index]) elems[e.index] = { elemId: elems[e.index].elemId, counter: e.value.datatype === 'counter' } }
+    else if (e.action === 'remove') elems.splice(e.index, e.count)
+  }
+  return elems
+}
+function probeFallback(backend, objectId, elemIds) {
+  const whole = getPatch(backend), shown = new Map(shownElemIds(whole, objectId).map(el => [el.elemId, el.counter]))
+  const known = new Set(Object.keys(whole.clock))
+  let actor = 'ff'.repeat(16)
+  while (known.has(actor)) actor = (BigInt('0x' + actor) - 1n).toString(16).padStart(32, '0')
+  const js = hydrate(backend), heads = ref().getHeads(js), opId = `${whole.maxOp + 1}@${actor}`
+  const find = diff => {
+    if (diff.objectId === objectId) return diff
+    if (diff.props) for (const key of Object.keys(diff.props)) for (const id of Object.keys(diff.props[key])) { const d = diff.props[key][id].objectId && find(diff.props[key][id]); if (d) return d }
+    if (diff.edits) for (const e of diff.edits) { const d = e.value && e.value.objectId && find(e.value); if (d) return d }
+    return null
+  }
+  const ask = elemId => {
+    const probe = columnar().encodeChange({ actor, seq: 1, startOp: whole.maxOp + 1, time: 0, message: '', deps: heads,
+      ops: [{ action: 'set', obj: objectId, elemId, insert: true, value: '#', pred: [] }] })
+    try {
+      return ref().applyChanges(ref().clone(js), [probe])[1]
+    } catch (e) {
+      return null   // (no such reference element, or an actor the document has never seen)
+    }
+  }
+  // (a Text no element was ever inserted into: the reference finds no op of the object and places the probe without looking for its
+  // reference element at all -- it accepts an id nobody issued; there every element is unknown)
+  const rowless = shown.size === 0 && known.size > 0 && ask(`${whole.maxOp + 2}@${known.values().next().value}`) !== null
+  const positions = elemIds.map(elemId => {
+    if (typeof elemId !== 'string' || !ELEM_ID.test(elemId)) throw new TypeError(`not an element id: ${elemId}`)
+    const patch = rowless ? null : ask(elemId)
+    if (!patch) return { status: 'unknown', position: 0, counter: false }
+    const diff = find(patch.diffs), edit = diff && diff.edits.find(x => x.opId === opId)
+    if (!edit) throw new Error(`positionsOfText: the probe behind ${elemId} is not in the reference's patch`)
+    return shown.has(elemId) ? { status: 'visible', position: edit.index - 1, counter: shown.get(elemId) } : { status: 'deleted', position: edit.index, counter: false }
+  })
+  return { length: shown.size, positions }
+}
+function positionsOfText(backend, objectId, elemIds) {
+  isFrozenCheck(backend)
+  if (!Array.isArray(elemIds)) throw new TypeError('positionsOfText takes an array of element ids')
+  const g = backend.state
+  const m = typeof objectId === 'string' ? OBJECT_ID.exec(objectId) : null
+  if (!JS_ONLY && positionOnEngine && m && Number(m[1]) <= 0xffffffff && g instanceof GpuState && !g.doc && !heldBack(g) && contextOf(g.generation)) {
+    try {
+      const ids = new Uint32Array(2 * elemIds.length), ranks = new Map()
+      elemIds.forEach((elemId, k) => {
+        const x = typeof elemId === 'string' ? ELEM_ID.exec(elemId) : null
+        if (!x) throw new TypeError(`not an element id: ${elemId}`)
+        if (!ranks.has(x[2])) ranks.set(x[2], addon.rankOfActor(ctx, new Uint8Array(Buffer.from(x[2], 'hex'))))
+        const rank = ranks.get(x[2]), ctr = Number(x[1])
+        const asked = rank >= 0 && ctr <= 0xffffffff   // (an actor the state does not know, a counter no row can hold: unknown)
+        ids[2 * k] = asked ? ctr : 0
+        ids[2 * k + 1] = asked ? rank : 0xffffffff
+      })
+      const r = addon.textPositions(ctx, Number(m[1]), new Uint8Array(Buffer.from(m[2], 'hex')), ids)
+      counters.gpuPosition++
+      const positions = new Array(elemIds.length)
+      for (let k = 0; k < elemIds.length; k++) positions[k] = { status: POS_STATUS[r.words[2 * k + 1] & 3], position: r.words[2 * k], counter: (r.words[2 * k + 1] & 0x100) !== 0 }
+      return { length: r.length, positions }
+    } catch (e) {
+      if (e.am355Code === AM355_E_ARG) throw new RangeError(e.message)
+      if (e.am355Code !== AM355_E_UNSUPPORTED) throw e
+    }
+  }
+  counters.positionFallbacks++
+  return probeFallback(backend, objectId, elemIds)
+}
+
 module.exports = {
   init, load, loadChanges, getPatch, getHeads, free, save, getAllChanges, getChanges, getChangeByHash, getMissingDeps,
   clone: backend => { noteGraphQuery(backend); return ref().clone(hydrate(backend)) },
@@ -1122,6 +1228,8 @@ module.exports = {
   getText, getTextInfo,
   // additions: a Text edited by position / positions resolved to ids, on the device (see above)
   spliceText, locateText,
+  // addition: elemIds of a Text resolved to positions, deleted elements included, on the device (see above)
+  positionsOfText,
   // sync protocol: the reference's own backend/sync.js bound to this module (boundSync above)
   generateSyncMessage: (...a) => syncModule().generateSyncMessage(...a),
   receiveSyncMessage: (...a) => syncModule().receiveSyncMessage(...a),
@@ -1147,6 +1255,7 @@ module.exports = {
   _setGraphProbeMin: n => { graphProbeMin = n; for (const e of contexts) addon.setGraphProbeMin(e.ctx, n) },
   _setTextOnEngine: on => { textOnEngine = !!on },
   _setSpliceOnEngine: on => { spliceOnEngine = !!on },
+  _setPositionOnEngine: on => { positionOnEngine = !!on },
   _textFromPatch: textFromPatch,   // (bench_text.js: the JS path's fold by itself)
   _applyProfile: profile,
   _hydrate: hydrate   // (tests: the reference handle of an engine state, made the way the state came to be)

@@ -657,6 +657,46 @@ int am355_text_locate_limits(uint32_t out[3]);                        /* the siz
  * owned by ctx and valid until the next call that changes the state. AM355_E_STATE: no replayed state; AM355_E_ARG: no such rank. */
 int am355_actor_of_rank(const am355_ctx *ctx, uint32_t rank, const uint8_t **bytes, size_t *len);
 
+/*
+ * ElemIds of a Text resolved to POSITIONS (csrc/am355_position.hip): the inverse of am355_text_locate, and what keeps a caret, a
+ * selection or a comment anchor alive while remote changes arrive -- the only stable name for a place in an RGA text is an elemId.
+ * Query i is the element (ids[i].ctr, ids[i].actor) of the Text obj_ctr @ obj_actor; answer (*out)[i] is
+ *   AM355_POS_VISIBLE  the element is in the Text: position = its index (text.getElemId(position) === elemId in the reference's frontend);
+ *                      | AM355_POS_COUNTER when it is a Counter (the test of am355_text_locate's AM355_RUN_COUNTER);
+ *   AM355_POS_DELETED  it was inserted into this Text and shows no value any more: position = the number of visible elements in front of
+ *                      it in document order -- what the whole-document patch cannot say;
+ *   AM355_POS_UNKNOWN  no applied change inserted such an element into this object (an unknown actor, a counter no row holds, a row that
+ *                      is no insert, an element of another object): position = 0. No error: a cursor may name an element of a change
+ *                      that has not arrived yet.
+ * In both known cases the caret position directly behind the element is position + (status == AM355_POS_VISIBLE). The reference has no
+ * cursor call; the number is pinned to it by a probe: a change of a fresh actor with startOp = maxOp + 1, deps = heads and the one op
+ * {action: 'set', insert: true, elemId: X, pred: []} lands directly behind X, and the patch of Backend.applyChanges on a clone of the
+ * state reports it at index = that caret position (tools/fixtures/make_text_positions.js).
+ * Actors are RANKS, as in am355_text_run; 0xffffffff = an actor the state does not know. Ranks are renumbered when a new actor
+ * arrives: a caller keeps actor bytes and asks for ranks per call (am355_rank_of_actor, the inverse of am355_actor_of_rank; no such
+ * actor: AM355_E_ARG). *out is pinned memory owned by the context, valid until the next call on ctx; *length = the Text's length.
+ * n == 0 is legal and returns the length.
+ * Contexts and errors are those of am355_text_locate: AM355_E_STATE, AM355_E_UNSUPPORTED for a sharded context, AM355_E_ARG "no such
+ * object: ..." / "not a Text object", AM355_E_UNSUPPORTED for a Text with a `remove` record, AM355_E_DEVICE for tables that contradict
+ * each other (every row and every position is checked before it is used as an index). A DOCUMENT context is first turned into the state
+ * of its rebuilt changes, exactly as am355_text_splice does: the search runs over the op rows and the stored list order, which a loaded
+ * document does not have. Apart from that the call reads only: the state, what serves the next am355_apply_changes and the host
+ * copies of the tables stay as they were (edit tables that in-place merges left stale are rebuilt once; the row -> position table of
+ * the stored order is built when no in-place merge left it current, which is what the next in-place merge would have done itself).
+ * am355_text_position_calls: out[0] = calls served, out[1] = kernel launches they made (the object lookup included). A Text without
+ * records launches no heads pass; whether it has deleted elements only the device knows, so its queries are still resolved.
+ * am355_text_position_limits: out[0] = queries (and records) one workgroup takes, out[1] = results written straight into pinned memory
+ * (the ones behind go to device memory and down in one copy; up to that many queries are read from pinned memory too).
+ */
+enum { AM355_POS_UNKNOWN = 0u, AM355_POS_VISIBLE = 1u, AM355_POS_DELETED = 2u, AM355_POS_STATUS = 3u /* mask */, AM355_POS_COUNTER = 0x100u };
+typedef struct { uint32_t ctr, actor; } am355_elem_id;         /* actor: a rank, as in am355_text_run; 0xffffffff = unknown actor */
+typedef struct { uint32_t position, status; } am355_elem_pos;  /* status: AM355_POS_* | AM355_POS_COUNTER */
+int am355_text_position(am355_ctx *ctx, uint64_t obj_ctr, const uint8_t *obj_actor, size_t actor_len,
+                        const am355_elem_id *ids, uint32_t n, const am355_elem_pos **out, uint64_t *length);
+int am355_rank_of_actor(const am355_ctx *ctx, const uint8_t *bytes, size_t len, uint32_t *rank);   /* inverse of am355_actor_of_rank; no such actor: AM355_E_ARG */
+int am355_text_position_calls(const am355_ctx *ctx, uint64_t out[2]);   /* served | launches */
+int am355_text_position_limits(uint32_t out[2]);                        /* queries per workgroup | results written to pinned memory */
+
 /* ---- diagnostics: device primitives exposed for kernel-level tests ---- */
 /* The device hash table of the queries above, driven by itself: a table over table_hashes (n_table x 32 bytes) is built and
  * queries (n_queries x 32 bytes) are probed, both on the device; out_idx[q] = index of the table hash equal to query q (the smallest,
