@@ -9,6 +9,7 @@
 //   envelope                       backend/new.js:1870-1873, 2064-2067 (maxOp, clock, deps, pendingChanges)
 #include "am355_ctx.h"
 #include "am355_scan.h"
+#include "am355_textrec.h"
 
 // the context's host threads, streams, events and signal words; false: something could not be made (the caller deletes the context,
 // which destroys what was)
@@ -566,6 +567,28 @@ extern "C" int am355_test_carried_scan(am355_ctx* c, const uint32_t* v, uint32_t
     (void)hipMemcpyAsync(out_wg, d_wg.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st);
     (void)hipMemcpyAsync(wg_total, d_tot.p, 4 * (size_t)wgs, hipMemcpyDeviceToHost, st);
     return test_finish(c);
+  });
+}
+
+// table: n_recs edit records, the sentinel among them; the check pass of the Text calls (am355_textrec.h rec_premises) runs over the R
+// records from `begin` on. *flags: the premise bits; *length: what the word held before the call, and after it.
+extern "C" int am355_test_text_premises(am355_ctx* c, const am355_ir_edit* table, uint32_t n_recs, uint32_t begin, uint32_t R, uint32_t n_values, uint32_t* flags,
+                                        uint32_t* length) {
+  if (!c || !table || !flags || !length) return AM355_E_ARG;
+  return guarded(c, [&]() -> int {
+    if (!R || (uint64_t)begin + R + 1 > n_recs) return fail(c, AM355_E_ARG, "am355_test_text_premises: the records (and the one behind them) leave the table");
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    TestImage dt, dw;
+    uint32_t words[2] = {0u, *length};
+    if (!dt.up(table, sizeof(am355_ir_edit) * (size_t)n_recs, st) || !dw.up(words, 8, st)) return fail(c, AM355_E_NOMEM, "alloc");
+    launch_text_check(TextRecs{(const am355_ir_edit*)dt.p, begin, R, n_values}, dw.words(), st);
+    dw.down(words, st);
+    int rc = test_finish(c);
+    if (rc != AM355_OK) return rc;
+    *flags = words[0];
+    *length = words[1];
+    return AM355_OK;
   });
 }
 

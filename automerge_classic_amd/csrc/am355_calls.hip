@@ -197,7 +197,7 @@ static int run_delta_stage(am355_ctx* c, uint32_t T0, DeltaCounts* hc, bool chec
 }
 
 // Backend.applyChanges / applyLocalChange onto a loaded document: the context's state becomes the replay of the document's rebuilt changes
-static int document_to_change_state(am355_ctx* c, const std::function<void(const char*)>& lap) {
+int document_to_change_state(am355_ctx* c, const std::function<void(const char*)>& lap) {
     // Backend.applyChanges onto a loaded document. The reference rebuilds the document's changes first (computeHashGraph,
     // new.js:1887-1912, called from applyChanges :1809): the batch is scheduled against THEIR hashes. So does the engine
     // (am355_doc_changes: the device regroups rows into changes and encodes them, am355_hist.hip), then replays the rebuilt changes as
@@ -715,6 +715,18 @@ static bool staged_author_seq(const am355_ctx* c, uint32_t ci, const uint8_t*& a
   off += (size_t)v;
   return read_uleb_host(p, n, off, seq);
 }
+// *found: staged index of the author's change with that seq, the newest first (hashByActor, backend.js:73-81); NONE32: there is none
+static int staged_change_of(am355_ctx* c, const uint8_t* author, size_t author_len, uint64_t seq, uint32_t* found) {
+  *found = NONE32;
+  for (uint32_t ci = c->n_changes; ci-- > 0;) {
+    const uint8_t* a = nullptr;
+    size_t al = 0;
+    uint64_t s = 0;
+    if (!staged_author_seq(c, ci, a, al, s)) return fail(c, AM355_E_DEVICE, "internal: staged change %u does not parse", ci);
+    if (s == seq && al == author_len && memcmp(a, author, al) == 0) { *found = ci; break; }
+  }
+  return AM355_OK;
+}
 
 int apply_local_change_impl(am355_ctx* c, const am355_local_change* lc, const uint8_t** change, size_t* len) {
   if (!c) return AM355_E_ARG;
@@ -734,28 +746,16 @@ int apply_local_change_impl(am355_ctx* c, const am355_local_change* lc, const ui
   const uint8_t* author = lc->actor_bytes + lc->actor_off[0];
   const size_t author_len = lc->actor_off[1] - lc->actor_off[0];
   // backend.js:56: a seq the clock already holds
-  if (have_state) {
-    const std::string id((const char*)author, author_len);
-    auto it = std::lower_bound(c->actors.begin(), c->actors.end(), id);
-    if (it != c->actors.end() && *it == id) {
-      const uint32_t rank = (uint32_t)(it - c->actors.begin());
-      for (size_t k = 0; k < c->clock_actor.size(); k++)
-        if (c->clock_actor[k] == rank && lc->seq <= c->clock_seq[k]) return refused(fail(c, AM355_E_INVALID, "Change request has already been applied"));
-    }
-  }
+  uint32_t rank = 0;
+  if (have_state && actor_rank_of(c, author, author_len, &rank))
+    for (size_t k = 0; k < c->clock_actor.size(); k++)
+      if (c->clock_actor[k] == rank && lc->seq <= c->clock_seq[k]) return refused(fail(c, AM355_E_INVALID, "Change request has already been applied"));
   // backend.js:73-81: the author's last hash joins the deps (hashByActor: among the applied changes, the newest first)
   std::vector<uint8_t> deps(lc->deps, lc->deps + 32 * (size_t)lc->n_deps);
   bool graph_rebuilt = false;
   if (lc->seq > 1) {
     uint32_t found = NONE32;
-    if (have_state && c->h_hashes.p)
-      for (uint32_t ci = c->n_changes; ci-- > 0;) {
-        const uint8_t* a = nullptr;
-        size_t al = 0;
-        uint64_t s = 0;
-        if (!staged_author_seq(c, ci, a, al, s)) return refused(fail(c, AM355_E_DEVICE, "internal: staged change %u does not parse", ci));
-        if (s == lc->seq - 1 && al == author_len && memcmp(a, author, al) == 0) { found = ci; break; }
-      }
+    if (have_state && c->h_hashes.p && (rc = staged_change_of(c, author, author_len, lc->seq - 1, &found))) return refused(rc);
     if (found == NONE32) return refused(fail(c, AM355_E_INVALID, "Unknown change: the author's change with seq %llu is not in the state", (unsigned long long)(lc->seq - 1)));
     if (c->no_history && found < c->doc_n_changes && c->graph_mode != 0) {
       // the hash lies inside the loaded document: the reference rebuilds the document's hash graph to find it (backend.js:38-39)
@@ -790,13 +790,7 @@ int apply_local_change_impl(am355_ctx* c, const am355_local_change* lc, const ui
   am355_local_envelope& env = c->apply.local;
   env.is_local = 1;
   env.seq = lc->seq;
-  env.actor = NONE32;
-  {
-    const std::string id((const char*)author, author_len);
-    auto it = std::lower_bound(c->actors.begin(), c->actors.end(), id);
-    if (it != c->actors.end() && *it == id) env.actor = (uint32_t)(it - c->actors.begin());
-  }
-  if (env.actor == NONE32) {
+  if (!actor_rank_of(c, author, author_len, &env.actor)) {
     env = am355_local_envelope{};
     c->staged = c->replayed = c->ir_fetched = c->apply_ready = false;
     return refused(fail(c, AM355_E_DEVICE, "internal: the author of the applied change is not in the actor table"));

@@ -1,8 +1,15 @@
 // Context of the C ABI (include/am355.h) and what its translation units share: device / pinned buffers, the host thread pool, struct
-// am355_ctx, error helpers, the AM355_TRACE lap type. am355_api.hip: entry points; am355_stage.hip: staging; am355_replay.hip: host
-// scheduler, plan, device buffers, and the two sequences of named phases that orchestrate the device stages -- the full replay
-// (replay_impl over a Stage1) and the resident applyChanges (replay_resident over a ResidentBatch); am355_calls.hip: patch IR,
-// applyChanges, dependency graph, Bloom filters -- and, included at its end, am355_graph.hip: the hash-graph queries, and am355_text.hip: the string of a Text object, and am355_locate.hip: positions of a Text to ids, the positional edit, and am355_position.hip: elemIds of a Text to positions; am355_save.hip: save + history after load; am355_shard.hip: objectId sharding.
+// am355_ctx, error helpers, the AM355_TRACE lap type. The translation units:
+//   am355_api.hip     entry points, the test entries of the primitives
+//   am355_stage.hip   staging
+//   am355_replay.hip  host scheduler, plan, device buffers; the named phases of the full replay (replay_impl over a Stage1) and of the resident applyChanges (replay_resident over a ResidentBatch)
+//   am355_calls.hip   patch IR, applyChanges, local changes, dependency graph, Bloom filters; and, included at its end:
+//     am355_graph.hip     the hash-graph queries
+//     am355_text.hip      the string of a Text object
+//     am355_locate.hip    positions of a Text to ids, the edit by position
+//     am355_position.hip  elemIds of a Text to positions (the three share am355_textrec.h)
+//   am355_save.hip    save + history after load
+//   am355_shard.hip   objectId sharding
 #pragma once
 #include "../../include/am355.h"
 #include "am355_decode.h"
@@ -309,6 +316,24 @@ struct TraceLap {
   }
 };
 
+// A few result words of a call on their way to the host without a copy: a one-thread launch behind the call's kernels writes them into
+// pinned memory and the sequence word behind them (am355_prims.h launch_signal_words); the host spins on that word.
+struct SignalBlock {
+  static constexpr uint32_t WORDS = 8;
+  HostBuf h;          // the words, then their sequence word
+  uint32_t seq = 0;   // the last sequence number handed out
+  bool ready() { return h.ensure((WORDS + 1) * 4); }
+  const uint32_t* words() { return h.as<uint32_t>(); }
+  // n device words to words()[k ..], behind everything enqueued on st; returns when they are there (ready() has been true)
+  hipError_t fetch(const uint32_t* dev, uint32_t n, uint32_t k, hipStream_t st) {
+    uint32_t* hw = h.as<uint32_t>();
+    volatile uint32_t* hseq = hw + WORDS;
+    if (seq == 0) *hseq = 0;
+    launch_signal_words(dev, n, nullptr, 0, hw + k, hseq, ++seq, st);
+    return wait_host_signal(hseq, seq, st) ? hipSuccess : hipMemcpy(hw + k, dev, 4 * (size_t)n, hipMemcpyDeviceToHost);   // (no signal: the stream was drained instead)
+  }
+};
+
 struct LaneJoin {   // (whatever way its scope is left, the helper thread is not running the posted job any more)
   AsyncLane* l = nullptr;
   ~LaneJoin() { if (l) l->wait(); }
@@ -578,19 +603,17 @@ struct am355_ctx {
   uint64_t n_local_small = 0, n_local_small_bulk = 0;   // changes built by kl_small | requests that found the switch on, lay outside the limits and took the bulk path
   // am355_object_text (am355_text.hip): the string of a Text object gathered from the edit records in HBM
   DevBuf d_text, d_text_out;                       // result words | scanned offsets | elements | marks | scan workspace; the gathered bytes
-  HostBuf h_text, h_text_sig;                      // pinned: the string (valid until the next call) | the words the device signals + their sequence word
-  uint32_t text_seq = 0;
+  HostBuf h_text;                                  // pinned: the string (valid until the next call)
+  SignalBlock text_sig;                            // the result words of the object lookup and of every call on a Text (calls on a context are serial)
   size_t text_pinned_max = (size_t)1 << 20;         // am355_set_text_pinned_max: strings up to this many bytes are gathered straight into h_text, longer ones into d_text_out and copied (profiles/text_read_timings.txt: the direct write is 3-7 us ahead at every size measured, 64 B to 1 MiB)
   uint64_t n_text_served = 0, n_text_launches = 0; // am355_object_text_calls
   // am355_text_locate / am355_text_splice (am355_locate.hip): positions of a Text resolved to runs of (elemId, pred) on the device
   DevBuf d_loc, d_loc_runs;                        // result words | ids | head bits | counter bits | scanned heads | scan workspace; the runs behind LOCATE_PINNED_RUNS
-  HostBuf h_loc_runs, h_loc_sig;                   // pinned: the runs (valid until the next call) | the words the device signals + their sequence word
-  uint32_t loc_seq = 0;
+  HostBuf h_loc_runs;                              // pinned: the runs (valid until the next call)
   uint64_t n_splice_served = 0, n_splice_refused = 0, n_locate_launches = 0;   // am355_text_splice_calls
   // am355_text_position (am355_position.hip): elemIds of a Text resolved to positions on the device, by a search in the stored list order (d_pos)
   DevBuf d_posq;                                   // result words | rec_pos | the queries and the results behind LOCATE_PINNED_RUNS
-  HostBuf h_pos_out, h_pos_ids, h_pos_sig;         // pinned: the results (valid until the next call) | the queries | the words the device signals + their sequence word
-  uint32_t pos_seq = 0;
+  HostBuf h_pos_out, h_pos_ids;                    // pinned: the results (valid until the next call) | the queries
   uint64_t n_position_served = 0, n_position_launches = 0;   // am355_text_position_calls
   DevBuf d_map_alt, d_mapmerge;                    // the other map table | the stage's scratch
   am355_ir_map* map_alt_ptr = nullptr;             // whichever of the two map tables c->ir.map does NOT point to (null: not set up since the last carve)
@@ -665,6 +688,14 @@ static inline T* carve(uint8_t*& p, size_t count) {
 }
 
 static inline size_t carve_size(size_t count, size_t elem) { return carve_round(count * elem); }
+// rank of an actor id in c->actors (the actor table by rank: byte order of the raw ids, which is std::string's); false: not in it
+static inline bool actor_rank_of(const am355_ctx* c, const uint8_t* actor, size_t len, uint32_t* rank) {
+  const std::string want((const char*)actor, len);
+  auto it = std::lower_bound(c->actors.begin(), c->actors.end(), want);
+  if (it == c->actors.end() || *it != want) return false;
+  *rank = (uint32_t)(it - c->actors.begin());
+  return true;
+}
 static inline uint32_t pow2_at_least(uint64_t v) {
   uint32_t p = 64;
   while (p < v) p <<= 1;
@@ -697,6 +728,7 @@ int ensure_ir_fresh(am355_ctx* c);   // rebuilds the whole-document patch tables
 int fetch_ir_impl(am355_ctx* c, am355_patch_ir* out, bool with_edits = true);
 int patch_json_impl(am355_ctx* c, const char** json, size_t* len);
 int apply_changes_impl(am355_ctx* c, const uint8_t* arena, const uint64_t* offsets, uint32_t n);
+int document_to_change_state(am355_ctx* c, const std::function<void(const char*)>& lap);   // a document context becomes the state of its rebuilt changes
 int apply_patch_json_impl(am355_ctx* c, const char** json, size_t* len);
 int encode_change_impl(am355_ctx* c, const am355_local_change* lc, const uint8_t** bytes, size_t* len, uint8_t* hash);
 int apply_local_change_impl(am355_ctx* c, const am355_local_change* lc, const uint8_t** change, size_t* len);

@@ -13,79 +13,43 @@
 //      actors are equal and the pred counters consecutive (context.js:483-486; "both have exactly one pred" always holds by 1).
 //   3. An element that is a Counter cannot be deleted (context.js:455-471).
 //
-// ON THE RECORD TABLE (am355_ir_edit, the object's records [edit_begin, edit_end), no AM355_EDIT_REMOVE record among them). Record k
-// holds the elements index_k .. index_k + count_k - 1; record k + 1 either opens index_k + count_k or carries AM355_EDIT_UPDATE with
-// index == index_k + count_k - 1 and replaces that one value (am355_text.hip proves this: (a) - (e) of its header). For element j let
-// hi be the LAST record with hi.index <= j. Then
+// ON THE RECORD TABLE (am355_textrec.h, which proves it, (a) - (h)): for element j let hi be the LAST record with hi.index <= j. Then
 //     elemId = (hi.elem_ctr + (j - hi.index), hi.elem_actor)        pred = (hi.id_ctr + (j - hi.index), hi.id_actor)
-// Why one search is enough (am355_merge.hip list_edits_of, k_edit_runs, k_edit_pack):
-//   (f) k_edit_pack fills EVERY record, update records too, from the head edit e of the record: id_ctr / id_actor = the op id of the row
-//       e_row[e] that carries the value, elem_ctr / elem_actor = the op id of e_elem[e], the element's insert row -- its elemId. An
-//       update record therefore carries the element's elemId itself; the issue's second search (the last record WITHOUT the update bit,
-//       for the elemId) is not needed, and would be wrong for an element whose edits all carry the update bit (removed_first in
-//       list_edits_of: no record without the bit has its index).
-//   (g) A record of several values holds `simple` edits only (k_edit_runs): row == element for each, consecutive op ids of one actor,
-//       consecutive indexes. So value i of the record has elemId == opId == (id_ctr + i, id_actor) and elem_ctr == id_ctr: both formulas
-//       above count up together, which is apply_patch.js's multi-insert rule. A record whose head edit is not simple (an update, a child,
-//       an insert whose own value is gone and whose first listed value is another row: e_row != e_elem) holds ONE value, j - hi.index is 0
-//       and the record's two ids are the element's: the `insert` edit with opId != elemId, or the `update` edit that replaced it.
-//   (h) hi is the last edit of j's index: records are in document order, the edits of one element stand side by side, and only the last
-//       value of a record shares its index with the record behind ((c) of am355_text.hip) -- for an inner value of a record hi is the
-//       record itself, for its last value the last update record behind it, if there is one.
-//   (i) AM355_EDIT_CONT records are records like any other: their index and ids are those of their first value (k_edit_pack).
-// The element is a counter iff hi carries AM355_EDIT_COUNTER (a counter completed by increments, listed under its last increment) or
-// hi is a plain value record whose type is COUNTER (val_tl & 15 == 8, columnar.js:47-48: a counter nobody has incremented yet is an
-// ordinary `set` row to the engine, and `new Counter` to the frontend).
-// kl_check verifies the premises per record before anything is searched: indexes that start at 0 and continue as stated, `first` words
-// in order and inside the table, no `remove` record. Its last thread leaves the object's length.
+// and the element is a counter iff hi is one (rec_is_counter). kl_check verifies the premises per record before anything is searched
+// (rec_premises); its last thread leaves the object's length.
 //
-// Included at the end of am355_calls.hip (behind am355_text.hip, whose object lookup it shares), not compiled by itself.
-#include "am355_ctx.h"
+// Included at the end of am355_calls.hip, not compiled by itself.
+#include "am355_textrec.h"
 
 namespace am355 {
 
-constexpr uint32_t LOCATE_PINNED_RUNS = 4096;   // runs the compaction writes straight into pinned host memory (96 KiB); the ones behind go to HBM and down in one copy
 // device words of a call (d_loc)
 enum LocWord { LW_FLAGS = 0, LW_LENGTH = 1, LW_RUNS = 2, LW_COUNTERS = 3, LW_WORDS = 4 };
-enum LocFlag : uint32_t { LF_TABLE = 1,     // the records do not continue each other as the rule needs, or name values outside the table
-                          LF_REMOVE = 2,    // a `remove` record: an element that shows rows but no value
-                          LF_RANGE = 4 };   // the queried range reaches past the object's length
+constexpr uint32_t LF_RANGE = RF_CALL;   // flag bit of a call: the queried range reaches past the object's length
 
 // Check pass, one thread per record of the object: the premises of the searches. The last record's thread leaves the length.
-__global__ __launch_bounds__(BLOCK) void kl_check(const am355_ir_edit* __restrict__ edit, uint32_t begin, uint32_t R, uint32_t n_values, uint32_t* __restrict__ words) {
+__global__ __launch_bounds__(BLOCK) void kl_check(TextRecs t, uint32_t* __restrict__ words) {
   const uint32_t k = gtid();
-  if (k >= R) return;
-  const am355_ir_edit& rec = edit[begin + k];
-  const am355_ir_edit& nxt = edit[begin + k + 1];   // (the table ends with a sentinel record: k + 1 <= n_erecs)
-  uint32_t err = 0, count = 0;
-  if (rec.flags & AM355_EDIT_REMOVE) err |= LF_REMOVE;
-  if (nxt.first <= rec.first || nxt.first > n_values) err |= LF_TABLE;
-  else count = nxt.first - rec.first;
-  if (k == 0 && rec.index != 0) err |= LF_TABLE;
-  if ((rec.flags & AM355_EDIT_UPDATE) && count > 1) err |= LF_TABLE;   // (an update record holds one value)
-  if (count && (uint64_t)rec.index + count > 0xffffffffull) err |= LF_TABLE;
-  if (!err) {
-    if (k + 1 < R) {
-      const bool opens = nxt.index == rec.index + count;
-      const bool replaces = (nxt.flags & AM355_EDIT_UPDATE) && nxt.index == rec.index + count - 1;
-      if (!opens && !replaces) err |= LF_TABLE;
-    } else {
-      words[LW_LENGTH] = rec.index + count;
-    }
-  }
+  if (k >= t.R) return;
+  uint32_t count, length;
+  const uint32_t err = rec_premises(t, k, count, length);
   if (err) atomicOr(&words[LW_FLAGS], err);
+  else if (k + 1 == t.R) words[LW_LENGTH] = length;
+}
+void launch_text_check(const TextRecs& t, uint32_t* words, hipStream_t st) {
+  AM355_LAUNCH_INDEPENDENT(kl_check, dim3((t.R + BLOCK - 1) / BLOCK), dim3(BLOCK), st, t, words);
 }
 
 // ids of element j: the last record with index <= j (indexes are non-decreasing: kl_check). Reads only records of [begin, begin + R).
-__device__ __forceinline__ uint4 locate_ids(const am355_ir_edit* __restrict__ edit, uint32_t begin, uint32_t R, uint32_t j, uint32_t& counter) {
-  uint32_t lo = 0, hi = R;   // edit[begin + lo].index <= j < edit[begin + hi].index (record 0 has index 0; hi == R: the end)
+__device__ __forceinline__ uint4 locate_ids(const TextRecs& t, uint32_t j, uint32_t& counter) {
+  uint32_t lo = 0, hi = t.R;   // t[lo].index <= j < t[hi].index (record 0 has index 0; hi == R: the end)
   while (hi - lo > 1) {
     const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (edit[begin + mid].index <= j) lo = mid; else hi = mid;
+    if (t[mid].index <= j) lo = mid; else hi = mid;
   }
-  const am355_ir_edit& rec = edit[begin + lo];
+  const am355_ir_edit& rec = t[lo];
   const uint32_t d = j - rec.index;
-  counter = ((rec.flags & AM355_EDIT_COUNTER) || (!(rec.flags & AM355_EDIT_CHILD) && (rec.val_tl & 15u) == 8u)) ? 1u : 0u;
+  counter = rec_is_counter(rec) ? 1u : 0u;
   return uint4{rec.elem_ctr + d, rec.elem_actor, rec.id_ctr + d, rec.id_actor};
 }
 
@@ -93,15 +57,15 @@ __device__ __forceinline__ uint4 locate_ids(const am355_ir_edit* __restrict__ ed
 // it by the multiOp rule. Element 0 is a head, and so is element `lead` (1: the range begins one element early -- the reference element
 // of an insertion, which is no deletion and must not merge with the first one; 0: no such element). The neighbour's ids come from LDS;
 // the first thread of a workgroup searches for them again.
-__global__ __launch_bounds__(BLOCK) void kl_locate(const am355_ir_edit* __restrict__ edit, uint32_t begin, uint32_t R, uint32_t first, uint32_t n, uint32_t lead,
-                                                   uint32_t* __restrict__ words, uint4* __restrict__ ids, uint32_t* __restrict__ head, uint32_t* __restrict__ counter) {
+__global__ __launch_bounds__(BLOCK) void kl_locate(TextRecs t, uint32_t first, uint32_t n, uint32_t lead, uint32_t* __restrict__ words, uint4* __restrict__ ids,
+                                                   uint32_t* __restrict__ head, uint32_t* __restrict__ counter) {
   __shared__ uint4 s_ids[BLOCK];
   const uint32_t i = gtid();
   const uint32_t length = words[LW_LENGTH];   // (kl_check, the launch before; 0 when it found the table broken)
   const bool live = i < n && (uint64_t)first + i < length;
   uint4 me = uint4{0, 0, 0, 0};
   uint32_t cnt = 0;
-  if (live) me = locate_ids(edit, begin, R, first + i, cnt);
+  if (live) me = locate_ids(t, first + i, cnt);
   s_ids[threadIdx.x] = me;
   __syncthreads();
   if (i >= n) return;
@@ -113,7 +77,7 @@ __global__ __launch_bounds__(BLOCK) void kl_locate(const am355_ir_edit* __restri
   uint32_t h = 1;
   if (i != 0 && i != lead) {
     uint32_t pc;
-    const uint4 p = threadIdx.x ? s_ids[threadIdx.x - 1] : locate_ids(edit, begin, R, first + i - 1, pc);
+    const uint4 p = threadIdx.x ? s_ids[threadIdx.x - 1] : locate_ids(t, first + i - 1, pc);
     if (p.y == me.y && p.x + 1 == me.x && p.w == me.w && p.z + 1 == me.z) h = 0;
   }
   ids[i] = me; head[i] = h; counter[i] = cnt;
@@ -122,8 +86,7 @@ __global__ __launch_bounds__(BLOCK) void kl_locate(const am355_ir_edit* __restri
 
 // Compaction, one thread per queried element: a head writes its run -- ids, the distance to the next head (found by binary search over
 // the scanned head bits: pos[x] = heads in front of x, non-decreasing), whether a counter is among its elements (only when the range
-// holds a counter at all does the head walk its run's counter bits). Run r goes to pinned[r] for r < LOCATE_PINNED_RUNS, else to
-// spill[r - LOCATE_PINNED_RUNS].
+// holds a counter at all does the head walk its run's counter bits). Run r goes where pinned_or_spill says.
 __global__ __launch_bounds__(BLOCK) void kl_runs(const uint4* __restrict__ ids, const uint32_t* __restrict__ head, const uint32_t* __restrict__ pos,
                                                  const uint32_t* __restrict__ counter, uint32_t n, const uint32_t* __restrict__ words, am355_text_run* __restrict__ pinned,
                                                  am355_text_run* __restrict__ spill) {
@@ -140,7 +103,7 @@ __global__ __launch_bounds__(BLOCK) void kl_runs(const uint4* __restrict__ ids, 
   if (words[LW_COUNTERS])
     for (uint32_t x = i; x < end; x++) counters |= counter[x];
   const uint4 me = ids[i];
-  am355_text_run* out = r < LOCATE_PINNED_RUNS ? pinned + r : spill + (r - LOCATE_PINNED_RUNS);
+  am355_text_run* out = pinned_or_spill(pinned, spill, r);
   out->elem_ctr = me.x; out->elem_actor = me.y; out->pred_ctr = me.z; out->pred_actor = me.w;
   out->count = end - i;
   out->flags = counters ? AM355_RUN_COUNTER : 0u;
@@ -151,16 +114,13 @@ __global__ __launch_bounds__(BLOCK) void kl_runs(const uint4* __restrict__ ids, 
 namespace {
 
 // What both calls share: the runs of [first, first + n) of the object, *length, and *past = 1 when the range reaches past it (no runs
-// then). lead: see kl_locate. The caller has checked the state.
-int locate_core(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint64_t first, uint64_t n, uint32_t lead, const am355_text_run** runs,
-                uint32_t* n_runs, uint64_t* length, bool* past) {
-  (void)hipSetDevice(c->device);
-  { int frc = ensure_ir_fresh(c); if (frc) return frc; }   // (in-place list merges leave the edit tables stale: rebuilt once)
+// then). lead: see kl_locate. who, open_flags: the call and what its opening asks for (text_open).
+int locate_core(am355_ctx* c, const char* who, uint32_t open_flags, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint64_t first, uint64_t n, uint32_t lead,
+                const am355_text_run** runs, uint32_t* n_runs, uint64_t* length, bool* past) {
+  TextObject o;
+  { int orc = text_open(c, who, obj_ctr, obj_actor, actor_len, open_flags, &c->n_locate_launches, o); if (orc) return orc; }
   hipStream_t st = c->stream;
-  const uint32_t NV = c->counts.n_edits;
-  uint32_t oi = NONE32, eb = 0, ee = 0;
-  { int lrc = text_lookup(c, obj_ctr, obj_actor, actor_len, oi, eb, ee, &c->n_locate_launches); if (lrc) return lrc; }
-  const uint32_t R = ee - eb;
+  const uint32_t R = o.recs.R, oi = o.index;
   *runs = nullptr; *n_runs = 0; *length = 0; *past = false;
   if (!c->h_loc_runs.ensure(sizeof(am355_text_run))) return fail(c, AM355_E_NOMEM, "host allocation failed (locate)");
   *runs = c->h_loc_runs.as<am355_text_run>();
@@ -173,7 +133,7 @@ int locate_core(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t
   const uint32_t N = fits ? (uint32_t)n : 0u, F = fits ? (uint32_t)first : 0u;
   const size_t b_words = carve_size(LW_WORDS, 4), b_ids = carve_size(N, 16), b_arr = carve_size(N, 4), b_ws = carve_round(scan_workspace_bytes(N ? N : 1));   // ids | head, counter, pos | scan workspace
   const uint32_t spill_max = N > LOCATE_PINNED_RUNS ? N - LOCATE_PINNED_RUNS : 0u;
-  if (!c->d_loc.ensure(b_words + b_ids + 3 * b_arr + b_ws) || !c->h_loc_sig.ensure((LW_WORDS + 1) * 4) || (spill_max && !c->d_loc_runs.ensure((size_t)spill_max * sizeof(am355_text_run))) ||
+  if (!c->d_loc.ensure(b_words + b_ids + 3 * b_arr + b_ws) || (spill_max && !c->d_loc_runs.ensure((size_t)spill_max * sizeof(am355_text_run))) ||
       !c->h_loc_runs.ensure((size_t)(N ? N : 1) * sizeof(am355_text_run)))
     return fail(c, AM355_E_NOMEM, "allocation failed (locate)");
   *runs = c->h_loc_runs.as<am355_text_run>();
@@ -184,45 +144,30 @@ int locate_core(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t
   uint32_t* d_cnt = d_head + b_arr / 4;
   uint32_t* d_pos = d_cnt + b_arr / 4;
   void* d_ws = dp + b_words + b_ids + 3 * b_arr;
-  uint32_t* hw = c->h_loc_sig.as<uint32_t>();
-  volatile uint32_t* hseq = (volatile uint32_t*)(hw + LW_WORDS);
-  if (c->loc_seq == 0) *hseq = 0;
   HIPCHK(c, hipMemsetAsync(dw, 0, LW_WORDS * 4, st));
-  AM355_LAUNCH_INDEPENDENT(kl_check, dim3((R + BLOCK - 1) / BLOCK), dim3(BLOCK), st, (const am355_ir_edit*)c->ir.edit, eb, R, NV, dw);
+  launch_text_check(o.recs, dw, st);
   c->n_locate_launches++;
   if (N) {
     const dim3 grid((N + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(kl_locate, grid, dim3(BLOCK), 0, st, (const am355_ir_edit*)c->ir.edit, eb, R, F, N, lead, dw, d_ids, d_head, d_cnt);
+    hipLaunchKernelGGL(kl_locate, grid, dim3(BLOCK), 0, st, o.recs, F, N, lead, dw, d_ids, d_head, d_cnt);
     exclusive_scan_u32(d_head, d_pos, N, dw + LW_RUNS, d_ws, st);
     AM355_LAUNCH_INDEPENDENT(kl_runs, grid, dim3(BLOCK), st, (const uint4*)d_ids, (const uint32_t*)d_head, (const uint32_t*)d_pos, (const uint32_t*)d_cnt, N, (const uint32_t*)dw,
                              c->h_loc_runs.as<am355_text_run>(), c->d_loc_runs.as<am355_text_run>());
     c->n_locate_launches += 3;
   }
-  launch_signal_words(dw, LW_WORDS, nullptr, 0, hw, hseq, ++c->loc_seq, st);
   c->n_locate_launches++;
   // the one wait of the call: flag word, length, number of runs
-  if (!wait_host_signal(hseq, c->loc_seq, st)) HIPCHK(c, hipMemcpy(hw, dw, LW_WORDS * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, c->text_sig.fetch(dw, LW_WORDS, 0, st));
+  const uint32_t* hw = c->text_sig.words();
   const uint32_t lf = hw[LW_FLAGS];
-  if (lf & LF_TABLE) return fail(c, AM355_E_DEVICE, "internal: the edit records of object %u do not continue each other", oi);
-  if (lf & LF_REMOVE) return fail(c, AM355_E_UNSUPPORTED, "a Text element that shows rows but no value (a `remove` record): positions through the patch");
+  { int prc = text_premise_error(c, TC_LOCATE, lf, oi); if (prc) return prc; }
   *length = hw[LW_LENGTH];
   if (!fits || first + n > *length) { *past = true; return AM355_OK; }
   if (lf & LF_RANGE) return fail(c, AM355_E_DEVICE, "internal: the locate pass and the host disagree about the length of object %u", oi);
   const uint32_t nr = N ? hw[LW_RUNS] : 0u;
   if (nr > N || (N && !nr)) return fail(c, AM355_E_DEVICE, "internal: %u runs over %u elements", nr, N);
-  if (nr > LOCATE_PINNED_RUNS) {
-    HIPCHK(c, hipMemcpyAsync(c->h_loc_runs.as<am355_text_run>() + LOCATE_PINNED_RUNS, c->d_loc_runs.p, (size_t)(nr - LOCATE_PINNED_RUNS) * sizeof(am355_text_run),
-                             hipMemcpyDeviceToHost, st));
-    int prc = text_poll(c);
-    if (prc) return prc;
-  }
+  { int src = spill_down(c, c->h_loc_runs.as<am355_text_run>(), (const am355_text_run*)c->d_loc_runs.as<am355_text_run>(), nr); if (src) return src; }
   *n_runs = nr;
-  return AM355_OK;
-}
-
-int locate_state_check(am355_ctx* c, const char* who) {
-  if (!c->replayed) return fail(c, AM355_E_STATE, "%s: a replayed state is needed", who);
-  if (c->shard_world > 1) return fail(c, AM355_E_UNSUPPORTED, "%s on a sharded context", who);
   return AM355_OK;
 }
 
@@ -230,10 +175,8 @@ int text_locate_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, s
                      uint64_t* length) {
   if (!c) return AM355_E_ARG;
   if (!runs || !n_runs || !length || (!obj_actor && actor_len)) return fail(c, AM355_E_ARG, "am355_text_locate: null argument");
-  int rc = locate_state_check(c, "am355_text_locate");
-  if (rc) return rc;
   bool past = false;
-  rc = locate_core(c, obj_ctr, obj_actor, actor_len, first, n, 0, runs, n_runs, length, &past);
+  int rc = locate_core(c, "am355_text_locate", 0, obj_ctr, obj_actor, actor_len, first, n, 0, runs, n_runs, length, &past);
   if (rc) return rc;
   if (past)
     return fail(c, AM355_E_ARG, "elements [%llu, %llu + %llu) are out of bounds for a Text of length %llu", (unsigned long long)first, (unsigned long long)first,
@@ -260,23 +203,11 @@ int text_splice_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, s
     return refused(fail(c, AM355_E_ARG, "am355_text_splice: null argument"));
   for (uint32_t k = 0; k < n_values; k++)
     if (value_off[k + 1] < value_off[k]) return refused(fail(c, AM355_E_ARG, "am355_text_splice: value offsets out of order"));
-  const bool trace = getenv("AM355_TRACE") != nullptr;
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (trace) fprintf(stderr, "text_splice: %-26s +%8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-  };
+  const TraceLap lap("text_splice:", 26);
   *change = nullptr; *len = 0;
-  int rc = locate_state_check(c, "am355_text_splice");
-  if (rc) return refused(rc);
-  (void)hipSetDevice(c->device);
-  if (c->staged && c->is_document) {   // (as am355_apply_local_change: the document becomes the state of its rebuilt changes, whose clock, heads and max_op the request needs)
-    rc = document_to_change_state(c, [](const char*) {});
-    if (rc) return refused(rc);
-    if (!c->replayed) return refused(fail(c, AM355_E_STATE, "am355_text_splice: a replayed state is needed"));
-  }
-  if (!c->pending_change.empty() || c->n_pending) return refused(fail(c, AM355_E_UNSUPPORTED, "local change onto a state with queued changes: JS path"));
 
-  // ---- locate [start - 1, start + deletions): the insertion's reference element, then the deleted ones ----
+  // ---- locate [start - 1, start + deletions): the insertion's reference element, then the deleted ones; on the state of the document's
+  // rebuilt changes, whose clock, heads and max_op the request needs ----
   const uint32_t lead = start ? 1u : 0u;
   const am355_text_run* runs = nullptr;
   uint32_t n_runs = 0;
@@ -284,7 +215,7 @@ int text_splice_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, s
   bool past = false;
   const uint64_t q_first = start - lead, q_n = deletions + lead;
   const bool wraps = q_n < deletions || q_first + q_n < q_first;
-  rc = locate_core(c, obj_ctr, obj_actor, actor_len, wraps ? 0 : q_first, wraps ? 0 : q_n, lead, &runs, &n_runs, &length, &past);
+  int rc = locate_core(c, "am355_text_splice", TO_CHANGE_STATE | TO_NO_QUEUE, obj_ctr, obj_actor, actor_len, wraps ? 0 : q_first, wraps ? 0 : q_n, lead, &runs, &n_runs, &length, &past);
   if (rc) return refused(rc);
   lap("located");
   if (wraps || past)   // context.js:444-446
@@ -352,32 +283,22 @@ int text_splice_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, s
   }
   am355_local_change lc{};
   lc.seq = 1;
-  {
-    auto it = std::lower_bound(c->actors.begin(), c->actors.end(), me);
-    if (it != c->actors.end() && *it == me) {
-      const uint32_t rank = (uint32_t)(it - c->actors.begin());
-      for (size_t k = 0; k < c->clock_actor.size(); k++)
-        if (c->clock_actor[k] == rank) lc.seq = c->clock_seq[k] + 1;
-    }
-  }
+  uint32_t rank = 0;
+  if (actor_rank_of(c, author, author_len, &rank))
+    for (size_t k = 0; k < c->clock_actor.size(); k++)
+      if (c->clock_actor[k] == rank) lc.seq = c->clock_seq[k] + 1;
   lc.start_op = c->max_op + 1;
   lc.time = time;
   lc.message = message; lc.message_len = message_len;
   // deps: the heads without the author's last change, which am355_apply_local_change adds itself (backend.js:73-81, 88-89)
   std::vector<uint8_t> deps(c->heads);
-  if (lc.seq > 1 && c->h_hashes.p)
-    for (uint32_t ci = c->n_changes; ci-- > 0;) {
-      const uint8_t* a = nullptr;
-      size_t al = 0;
-      uint64_t s = 0;
-      if (!staged_author_seq(c, ci, a, al, s)) return refused(fail(c, AM355_E_DEVICE, "internal: staged change %u does not parse", ci));
-      if (s == lc.seq - 1 && al == author_len && memcmp(a, author, al) == 0) {
-        const uint8_t* h = c->h_hashes.as<uint8_t>() + 32 * (size_t)ci;
-        for (size_t k = 0; k + 32 <= deps.size(); k += 32)
-          if (memcmp(&deps[k], h, 32) == 0) { deps.erase(deps.begin() + k, deps.begin() + k + 32); break; }
-        break;
-      }
-    }
+  uint32_t last = NONE32;
+  if (lc.seq > 1 && c->h_hashes.p && (rc = staged_change_of(c, author, author_len, lc.seq - 1, &last))) return refused(rc);
+  if (last != NONE32) {
+    const uint8_t* h = c->h_hashes.as<uint8_t>() + 32 * (size_t)last;
+    for (size_t k = 0; k + 32 <= deps.size(); k += 32)
+      if (memcmp(&deps[k], h, 32) == 0) { deps.erase(deps.begin() + k, deps.begin() + k + 32); break; }
+  }
   lc.deps = deps.data(); lc.n_deps = (uint32_t)(deps.size() / 32);
   lc.n_actors = n_act; lc.actor_off = actor_off.data(); lc.actor_bytes = actor_bytes.data(); lc.actor_rank = actor_rank.data();
   lc.strings = utf8; lc.strings_len = n_values ? value_off[n_values] : 0u;

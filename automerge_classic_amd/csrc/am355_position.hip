@@ -12,7 +12,7 @@
 //
 // ONE MECHANISM FOR BOTH: a search by position in the stored list order. MergeBufs.order holds every insert row of every list, deleted
 // ones too, in document order; pos_of[row] (resorder_positions) is its inverse. The edit records of the object ([edit_begin, edit_end),
-// am355_locate.hip (f) - (i)) are in document order and every record carries its head element's elemId, so
+// am355_textrec.h (f) - (h)) are in document order and every record carries its head element's elemId, so
 //     rec_pos[k] = pos_of[row_of(record k's elemId)]
 // is non-decreasing (an update record repeats the position of the value it replaces). For a queried element at position p:
 //   hi = the LAST record with rec_pos[hi] <= p; none: nothing visible stands in front of it -- DELETED at 0;
@@ -21,12 +21,12 @@
 //   actor can stand between two of them. If one of them has position == p the element is VISIBLE at hi.index + d, else DELETED there.
 // Why the last such record is the right one for a visible element: it lies in some record k at offset i, so rec_pos[k] <= p; the
 // record behind has a greater position unless it is the update that replaces exactly this element, whose one value is the element.
-// kp_heads builds rec_pos in one parallel pass and makes kl_check's premise checks beside it, so a query's chain of dependent loads is
+// kp_heads builds rec_pos in one parallel pass and checks the premises of the record table (rec_premises) beside it, so a query's chain of dependent loads is
 // log2(records) + log2(count) * log2(spans) instead of log2(records) * log2(spans).
 // Every row and every position read is checked against the row count and the list length before it is used as an index.
 //
-// Included at the end of am355_calls.hip (behind am355_locate.hip, whose object lookup and state check it shares), not compiled by itself.
-#include "am355_ctx.h"
+// Included at the end of am355_calls.hip, not compiled by itself.
+#include "am355_textrec.h"
 #include "am355_rows.h"
 #include "am355_resorder.h"
 
@@ -34,14 +34,10 @@ namespace am355 {
 
 // device words of a call (d_posq)
 enum PosWord { PW_FLAGS = 0, PW_LENGTH = 1, PW_WORDS = 2 };
-enum PosFlag : uint32_t { PF_TABLE = 1,     // the records do not continue each other, name values outside the table, or their head elements are not in document order
-                          PF_REMOVE = 2,    // a `remove` record: an element that shows rows but no value
-                          PF_RANGE = 4 };   // a row or a position read for a query lies outside the tables
+constexpr uint32_t PF_RANGE = RF_CALL;   // flag bit of a call: a row or a position read for a query lies outside the tables (RF_TABLE here also: the head elements of the records are not in document order)
 
 struct PosQuery {
-  const am355_ir_edit* edit;   // the whole-document edit records
-  uint32_t begin, R;           // the object's records [begin, begin + R)
-  uint32_t n_values;           // values of the whole table (the `first` word of the sentinel record)
+  TextRecs recs;               // the object's records
   const uint32_t* pos_of;      // [rows] position in `order` of every list insert row
   uint32_t n_list;             // entries of `order`
   uint32_t obj_ctr, obj_actor; // the Text
@@ -60,40 +56,32 @@ __device__ __forceinline__ uint32_t pos_of_elem(const MergeBufs& b, const PosQue
   return p;
 }
 
-// Heads pass, one thread per record of the object: kl_check's premises (am355_locate.hip), rec_pos[k], and rec_pos[k] <= rec_pos[k + 1].
+// Heads pass, one thread per record of the object: the premises (rec_premises), rec_pos[k], and rec_pos[k] <= rec_pos[k + 1].
 // The last record's thread leaves the length.
 __global__ __launch_bounds__(BLOCK) void kp_heads(MergeBufs b, PosQuery q, uint32_t* __restrict__ rec_pos, uint32_t* __restrict__ words) {
   const uint32_t k = gtid();
-  if (k >= q.R) return;
-  const am355_ir_edit& rec = q.edit[q.begin + k];
-  const am355_ir_edit& nxt = q.edit[q.begin + k + 1];   // (the table ends with a sentinel record: k + 1 <= n_erecs)
-  uint32_t err = 0, count = 0;
-  if (rec.flags & AM355_EDIT_REMOVE) err |= PF_REMOVE;
-  if (nxt.first <= rec.first || nxt.first > q.n_values) err |= PF_TABLE;
-  else count = nxt.first - rec.first;
-  if (k == 0 && rec.index != 0) err |= PF_TABLE;
-  if ((rec.flags & AM355_EDIT_UPDATE) && count > 1) err |= PF_TABLE;   // (an update record holds one value)
-  if (count && (uint64_t)rec.index + count > 0xffffffffull) err |= PF_TABLE;
-  if (count && (uint64_t)rec.elem_ctr + count > 0xffffffffull) err |= PF_TABLE;
+  if (k >= q.recs.R) return;
+  const am355_ir_edit& rec = q.recs[k];
+  uint32_t count, length;
+  uint32_t err = rec_premises(q.recs, k, count, length);
+  if (count && (uint64_t)rec.elem_ctr + count > 0xffffffffull) err |= RF_TABLE;
   bool bad = false;
   const uint32_t p = pos_of_elem(b, q, rec.elem_actor, rec.elem_ctr, bad);
-  if (p == NONE32) err |= PF_TABLE;   // (the head element of a record is an insert row of this object)
+  if (p == NONE32) err |= RF_TABLE;   // (the head element of a record is an insert row of this object)
   rec_pos[k] = p;
   if (!err) {
-    if (k + 1 < q.R) {
-      const bool opens = nxt.index == rec.index + count;
-      const bool replaces = (nxt.flags & AM355_EDIT_UPDATE) && nxt.index == rec.index + count - 1;
-      if (!opens && !replaces) err |= PF_TABLE;
+    if (k + 1 < q.recs.R) {
+      const am355_ir_edit& nxt = q.recs[k + 1];
       const uint32_t pn = pos_of_elem(b, q, nxt.elem_actor, nxt.elem_ctr, bad);
-      if (pn == NONE32 || pn < p) err |= PF_TABLE;
+      if (pn == NONE32 || pn < p) err |= RF_TABLE;
     } else {
-      words[PW_LENGTH] = rec.index + count;
+      words[PW_LENGTH] = length;
     }
   }
   if (err) atomicOr(&words[PW_FLAGS], err);
 }
 
-// Resolve, one thread per query: see the header. Result i goes to pinned[i] for i < LOCATE_PINNED_RUNS, else to spill[i - LOCATE_PINNED_RUNS].
+// Resolve, one thread per query: see the header. Result i goes where pinned_or_spill says.
 __global__ __launch_bounds__(BLOCK) void kp_resolve(MergeBufs b, PosQuery q, const uint32_t* __restrict__ rec_pos, const am355_elem_id* __restrict__ ids, uint32_t n,
                                                     uint32_t* __restrict__ words, am355_elem_pos* __restrict__ pinned, am355_elem_pos* __restrict__ spill) {
   const uint32_t i = gtid();
@@ -104,15 +92,15 @@ __global__ __launch_bounds__(BLOCK) void kp_resolve(MergeBufs b, PosQuery q, con
   const uint32_t p = pos_of_elem(b, q, id.actor, id.ctr, bad);
   if (p != NONE32) {
     status = AM355_POS_DELETED;
-    uint32_t lo = 0, hi = q.R;   // records [0, lo) have rec_pos <= p, records [hi, R) a greater one
+    uint32_t lo = 0, hi = q.recs.R;   // records [0, lo) have rec_pos <= p, records [hi, R) a greater one
     while (lo < hi) {
       const uint32_t mid = lo + ((hi - lo) >> 1);
       if (rec_pos[mid] <= p) lo = mid + 1; else hi = mid;
     }
     if (lo) {
-      const am355_ir_edit& rec = q.edit[q.begin + lo - 1];
-      const uint32_t first = rec.first, next = q.edit[q.begin + lo].first;
-      const uint32_t count = next > first ? next - first : 0u;   // (kp_heads has checked the words; a broken table fails the call)
+      const am355_ir_edit& rec = q.recs[lo - 1];
+      uint32_t count;
+      (void)rec_count(q.recs, lo - 1, count);   // (kp_heads has checked the words; a broken table fails the call)
       uint32_t a = 0, e = count;   // elements [0, a) of the record stand in front of p, elements [e, count) at or behind it
       bool found = false;
       while (a < e && !bad) {
@@ -125,7 +113,7 @@ __global__ __launch_bounds__(BLOCK) void kp_resolve(MergeBufs b, PosQuery q, con
       position = rec.index + a;
       if (found) {
         status = AM355_POS_VISIBLE;
-        if ((rec.flags & AM355_EDIT_COUNTER) || (!(rec.flags & AM355_EDIT_CHILD) && (rec.val_tl & 15u) == 8u)) status |= AM355_POS_COUNTER;
+        if (rec_is_counter(rec)) status |= AM355_POS_COUNTER;
       }
     }
   }
@@ -133,7 +121,7 @@ __global__ __launch_bounds__(BLOCK) void kp_resolve(MergeBufs b, PosQuery q, con
     atomicOr(&words[PW_FLAGS], (uint32_t)PF_RANGE);
     status = AM355_POS_UNKNOWN; position = 0;
   }
-  am355_elem_pos* out = i < LOCATE_PINNED_RUNS ? pinned + i : spill + (i - LOCATE_PINNED_RUNS);
+  am355_elem_pos* out = pinned_or_spill(pinned, spill, i);
   out->position = position;
   out->status = status;
 }
@@ -147,21 +135,10 @@ int text_position_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor,
   if (!c) return AM355_E_ARG;
   if (!out || !length || (!obj_actor && actor_len) || (n && !ids)) return fail(c, AM355_E_ARG, "am355_text_position: null argument");
   *out = nullptr; *length = 0;
-  int rc = locate_state_check(c, "am355_text_position");
-  if (rc) return rc;
-  (void)hipSetDevice(c->device);
-  if (c->staged && c->is_document) {   // (as am355_text_splice: the document becomes the state of its rebuilt changes, whose rows and list order are searched)
-    rc = document_to_change_state(c, [](const char*) {});
-    if (rc) return rc;
-    if (!c->replayed) return fail(c, AM355_E_STATE, "am355_text_position: a replayed state is needed");
-  }
-  { int frc = ensure_ir_fresh(c); if (frc) return frc; }   // (in-place list merges leave the edit tables stale: rebuilt once)
+  TextObject o;   // (on the state of a document's rebuilt changes, whose rows and list order are searched)
+  { int orc = text_open(c, "am355_text_position", obj_ctr, obj_actor, actor_len, TO_CHANGE_STATE, &c->n_position_launches, o); if (orc) return orc; }
   hipStream_t st = c->stream;
-  uint32_t oi = NONE32, eb = 0, ee = 0;
-  { int lrc = text_lookup(c, obj_ctr, obj_actor, actor_len, oi, eb, ee, &c->n_position_launches); if (lrc) return lrc; }
-  uint32_t obj_rank = 0;
-  if (!text_rank_of(c, obj_actor, actor_len, &obj_rank)) return fail(c, AM355_E_DEVICE, "internal: the actor of object %u has no rank", oi);
-  const uint32_t R = ee - eb, NL = c->counts.n_list_ins;
+  const uint32_t R = o.recs.R, oi = o.index, NL = c->counts.n_list_ins;
   MergeBufs& b = c->mb;
   if (b.n_ops != c->n_ops || !b.order || !b.kind || !b.spans) return fail(c, AM355_E_DEVICE, "internal: the op rows of the state are not on the device");
   if (!c->h_pos_out.ensure(((size_t)(n ? n : 1)) * sizeof(am355_elem_pos))) return fail(c, AM355_E_NOMEM, "host allocation failed (position)");
@@ -181,21 +158,14 @@ int text_position_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor,
   const uint32_t spill_max = n > LOCATE_PINNED_RUNS ? n - LOCATE_PINNED_RUNS : 0u;
   const size_t b_words = carve_size(PW_WORDS, 4), b_rec = carve_size(R, 4), b_ids = carve_size(spill_max ? n : 0, sizeof(am355_elem_id)),
                b_spill = carve_size(spill_max, sizeof(am355_elem_pos));
-  if (!c->d_posq.ensure(b_words + b_rec + b_ids + b_spill + 256) || !c->h_pos_sig.ensure((PW_WORDS + 1) * 4) ||
-      !c->h_pos_ids.ensure(((size_t)(n ? n : 1)) * sizeof(am355_elem_id)))
+  if (!c->d_posq.ensure(b_words + b_rec + b_ids + b_spill + 256) || !c->h_pos_ids.ensure(((size_t)(n ? n : 1)) * sizeof(am355_elem_id)))
     return fail(c, AM355_E_NOMEM, "allocation failed (position)");
   uint8_t* dp = c->d_posq.as<uint8_t>();
   uint32_t* dw = (uint32_t*)dp;
   uint32_t* d_rec = (uint32_t*)(dp + b_words);
   am355_elem_id* d_ids = (am355_elem_id*)(dp + b_words + b_rec);
   am355_elem_pos* d_spill = (am355_elem_pos*)(dp + b_words + b_rec + b_ids);
-  uint32_t* hw = c->h_pos_sig.as<uint32_t>();
-  volatile uint32_t* hseq = (volatile uint32_t*)(hw + PW_WORDS);
-  if (c->pos_seq == 0) *hseq = 0;
-  PosQuery q;
-  q.edit = (const am355_ir_edit*)c->ir.edit; q.begin = eb; q.R = R; q.n_values = c->counts.n_edits;
-  q.pos_of = c->d_pos.as<uint32_t>(); q.n_list = NL;
-  q.obj_ctr = (uint32_t)obj_ctr; q.obj_actor = obj_rank;
+  const PosQuery q{o.recs, c->d_pos.as<uint32_t>(), NL, (uint32_t)obj_ctr, o.actor_rank};
   HIPCHK(c, hipMemsetAsync(dw, 0, PW_WORDS * 4, st));
   if (R) {
     AM355_LAUNCH_INDEPENDENT(kp_heads, dim3((R + BLOCK - 1) / BLOCK), dim3(BLOCK), st, b, q, d_rec, dw);
@@ -211,17 +181,15 @@ int text_position_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor,
     }
     AM355_LAUNCH_INDEPENDENT(kp_resolve, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), st, b, q, (const uint32_t*)d_rec, src, n, dw, c->h_pos_out.as<am355_elem_pos>(), d_spill);
     c->n_position_launches++;
-    if (spill_max)
-      HIPCHK(c, hipMemcpyAsync(c->h_pos_out.as<am355_elem_pos>() + LOCATE_PINNED_RUNS, d_spill, (size_t)spill_max * sizeof(am355_elem_pos), hipMemcpyDeviceToHost, st));
   }
-  launch_signal_words(dw, PW_WORDS, nullptr, 0, hw, hseq, ++c->pos_seq, st);
   c->n_position_launches++;
-  // the one wait of the call: flag word and length, behind the copy of the results
-  if (!wait_host_signal(hseq, c->pos_seq, st)) HIPCHK(c, hipMemcpy(hw, dw, PW_WORDS * 4, hipMemcpyDeviceToHost));
+  // the one wait of the call: flag word and length; the results behind the pinned bound follow in one copy
+  HIPCHK(c, c->text_sig.fetch(dw, PW_WORDS, 0, st));
+  const uint32_t* hw = c->text_sig.words();
   const uint32_t pf = hw[PW_FLAGS];
-  if (pf & PF_REMOVE) return fail(c, AM355_E_UNSUPPORTED, "a Text element that shows rows but no value (a `remove` record): positions through the patch");
-  if (pf & PF_TABLE) return fail(c, AM355_E_DEVICE, "internal: the edit records of object %u do not continue each other, or their elements are not in document order", oi);
+  { int prc = text_premise_error(c, TC_POSITION, pf, oi); if (prc) return prc; }
   if (pf & PF_RANGE) return fail(c, AM355_E_DEVICE, "internal: a row or a position of object %u lies outside the tables", oi);
+  { int src = spill_down(c, c->h_pos_out.as<am355_elem_pos>(), (const am355_elem_pos*)d_spill, n); if (src) return src; }
   *length = R ? hw[PW_LENGTH] : 0u;
   c->n_position_served++;
   return AM355_OK;
@@ -237,7 +205,7 @@ extern "C" int am355_rank_of_actor(const am355_ctx* c, const uint8_t* bytes, siz
   if (!c || !rank || !bytes) return AM355_E_ARG;
   if (!c->replayed) return AM355_E_STATE;
   if (!len) return AM355_E_ARG;   // (no actor has an empty id)
-  return text_rank_of(const_cast<am355_ctx*>(c), bytes, len, rank) ? AM355_OK : AM355_E_ARG;
+  return actor_rank_of(c, bytes, len, rank) ? AM355_OK : AM355_E_ARG;
 }
 extern "C" int am355_text_position_calls(const am355_ctx* c, uint64_t out[2]) {
   if (!c || !out) return AM355_E_ARG;

@@ -49,6 +49,8 @@ RUN_COUNTER = 1
 ELEM_ID_DTYPE = np.dtype([("ctr", "<u4"), ("actor", "<u4")])              # am355_elem_id
 ELEM_POS_DTYPE = np.dtype([("position", "<u4"), ("status", "<u4")])       # am355_elem_pos
 POS_UNKNOWN, POS_VISIBLE, POS_DELETED, POS_COUNTER = 0, 1, 2, 0x100       # AM355_POS_*
+IR_EDIT_DTYPE = np.dtype([(n, "<u4") for n in ("flags", "index", "id_ctr", "id_actor", "elem_ctr", "elem_actor", "first", "val_tl", "val_off", "pad")])   # am355_ir_edit
+EDIT_UPDATE, EDIT_REMOVE = 1, 8                                           # AM355_EDIT_*
 
 
 class EngineError(RuntimeError):
@@ -303,7 +305,7 @@ def _bind(path):
                     ("am355_test_sort_bits", [vp, vp, vp, u32, ci, ci, vp, ctypes.POINTER(ci)]), ("am355_test_chain_mark", [vp, vp, vp, u32, u32]),
                     ("am355_test_remap", [vp, vp, u32, u32, vp, u32, vp, u32, ctypes.POINTER(u32)]), ("am355_test_fill", [vp, vp, u32, u32, vp, u32, ctypes.POINTER(u32)]),
                     ("am355_test_copy", [vp, vp, sz, vp, sz, ci, vp, u32, ctypes.POINTER(u32)]), ("am355_test_signal_words", [vp, vp, u32, vp, u32, u32, vp, u32, vp]),
-                    ("am355_test_carried_scan", [vp, vp, u32, vp, vp, vp])):
+                    ("am355_test_carried_scan", [vp, vp, u32, vp, vp, vp]), ("am355_test_text_premises", [vp, vp, u32, u32, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)])):
         if not hasattr(L, f):   # (a library of an earlier commit, loaded for an A/B run)
             continue
         getattr(L, f).argtypes = args
@@ -1044,6 +1046,14 @@ class Engine:
         out, out_wg, tot = np.empty_like(v), np.empty_like(v), np.empty((v.size + 255) // 256, dtype=np.uint32)
         self._check(self._L.am355_test_carried_scan(self._h, v.ctypes.data, v.size, out.ctypes.data, out_wg.ctypes.data, tot.ctypes.data))
         return out, out_wg, tot
+
+    def prim_text_premises(self, table, begin, n_recs, n_values, length_before=0xdeadbeef):
+        """am355_test_text_premises: the check pass of the Text calls over records [begin, begin + n_recs) of `table` (IR_EDIT_DTYPE, the
+        sentinel among its records). Returns (flag word, length word behind the pass)."""
+        t = np.ascontiguousarray(table, dtype=IR_EDIT_DTYPE)
+        flags, length = ctypes.c_uint32(0), ctypes.c_uint32(length_before)
+        self._check(self._L.am355_test_text_premises(self._h, t.ctypes.data, t.size, begin, n_recs, n_values, ctypes.byref(flags), ctypes.byref(length)))
+        return flags.value, length.value
 
     def rows(self):
         n = int(self.stats().n_ops)

@@ -738,6 +738,12 @@ int am355_test_copy(am355_ctx *ctx, uint8_t *dst, size_t dst_bytes, const uint8_
 int am355_test_signal_words(am355_ctx *ctx, const uint32_t *a, uint32_t n_a, const uint32_t *b, uint32_t n_b, uint32_t seq, uint32_t *host_words, uint32_t host_words_n,
                             uint32_t *seq_word);
 int am355_test_carried_scan(am355_ctx *ctx, const uint32_t *v, uint32_t n, uint32_t *out, uint32_t *out_wg, uint32_t *wg_total);
+/* The check pass of the calls on a Text (am355_text_locate, am355_text_splice, am355_text_position) over a hand-made record table:
+ * `table` holds n_recs records, the sentinel among them, and the R >= 1 records from `begin` on are checked as those of one object
+ * (begin + R + 1 <= n_recs: every record read lies in the table); n_values: values of the whole table. *flags: 1 = the records do not
+ * continue each other or name values outside the table, 2 = a `remove` record. *length: in, what the length word holds before the
+ * pass; out, what it holds behind it -- the object's length when flags == 0, else as it was. */
+int am355_test_text_premises(am355_ctx *ctx, const am355_ir_edit *table, uint32_t n_recs, uint32_t begin, uint32_t R, uint32_t n_values, uint32_t *flags, uint32_t *length);
 /* decoded op rows of the last replay, copied to caller arrays of length n_ops (any pointer may be NULL) */
 int am355_get_rows(am355_ctx *ctx, uint32_t *obj_actor, uint32_t *obj_ctr, uint32_t *key_actor, uint32_t *key_ctr, uint32_t *key_off,
                    uint32_t *key_len, uint32_t *action, uint32_t *val_tl, uint32_t *val_off, uint32_t *pred_num, uint32_t *id_ctr,

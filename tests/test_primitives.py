@@ -1,7 +1,8 @@
 """The device primitives of csrc/am355_prims.hip and the workgroup / carried scans of csrc/am355_scan.h, each driven by itself through the
 am355_test_* hooks (am355_api.hip) at the sizes, alignments and values where its kernels change path: the launch counts of the scans,
 their 16-byte and narrow loads, sums that wrap at 2^32, the fused / unfused radix sort and its buffer parity, the doubling rounds of
-chain_mark inside a tile, the head / body / tail words of the range kernels.
+chain_mark inside a tile, the head / body / tail words of the range kernels. Last, the check pass of the calls on a Text
+(csrc/am355_textrec.h rec_premises) on hand-made record tables, which the engine itself never builds broken.
 
 Everything is integer work, so every comparison is exact, against NumPy or a plain Python loop over the same input -- never against a
 second call of the engine. Buffers go to the device whole and come back whole with 0xA5A5A5A5 (or live values, where a stray write
@@ -863,3 +864,164 @@ def test_carried_scan_groups_emulated(emu_lib, n):
 @pytest.mark.gpu
 def test_carried_scan_gpu():
     carried_cases(_gpu, CARRIED_SIZES)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# am355_textrec.h rec_premises: the check pass of the calls on a Text (am355_locate.hip kl_check), on hand-made record tables
+# ---------------------------------------------------------------------------------------------------------------------------
+RF_TABLE, RF_REMOVE = 1, 2
+LENGTH_BEFORE = 0xDEADBEEF   # what the length word holds before the pass: a pass that leaves no length leaves this
+
+
+def _premises_ref(t, begin, R, n_values):
+    """The rule, restated: (flag word, length word) for the records [begin, begin + R) of table t."""
+    flags, length = 0, LENGTH_BEFORE
+    for k in range(R):
+        rec, nxt = t[begin + k], t[begin + k + 1]
+        index, first, nfirst = int(rec["index"]), int(rec["first"]), int(nxt["first"])
+        err, count = 0, 0
+        if rec["flags"] & engine.EDIT_REMOVE:
+            err |= RF_REMOVE
+        if nfirst <= first or nfirst > n_values:          # `first` words in order and inside the table
+            err |= RF_TABLE
+        else:
+            count = nfirst - first
+        if k == 0 and index != 0:                         # record 0 has index 0
+            err |= RF_TABLE
+        if rec["flags"] & engine.EDIT_UPDATE and count > 1:   # an update record holds one value
+            err |= RF_TABLE
+        if count and index + count > 0xFFFFFFFF:
+            err |= RF_TABLE
+        if not err:
+            if k + 1 < R:
+                opens = int(nxt["index"]) == index + count
+                replaces = bool(nxt["flags"] & engine.EDIT_UPDATE) and int(nxt["index"]) == index + count - 1
+                if not opens and not replaces:
+                    err |= RF_TABLE
+            else:
+                length = index + count                    # the last record leaves the length
+        flags |= err
+    return flags, length
+
+
+def _premises_table(R, begin, behind):
+    """A well-formed object of R records at `begin`: an insert record of 3 values, the update that replaces its last value, a record that
+    opens the next index, and so on; `begin` foreign records in front and `behind` foreign records plus the sentinel at the end. The foreign
+    records would each break the rule if the pass took them for the object's (a `remove` bit, an index out of line)."""
+    t = np.zeros(begin + R + behind + 1, dtype=engine.IR_EDIT_DTYPE)
+    for name in ("id_ctr", "id_actor", "elem_ctr", "elem_actor", "val_tl", "val_off", "pad"):
+        t[name] = SENT
+    first = 0
+    for k in range(begin):
+        t[k]["flags"], t[k]["index"], t[k]["first"] = engine.EDIT_REMOVE, 77, first
+        first += 2
+    index = 0
+    for k in range(R):
+        rec = t[begin + k]
+        if k % 3 == 0:
+            rec["flags"], rec["index"], count = 0, index, 3
+            index += 3
+        elif k % 3 == 1:
+            rec["flags"], rec["index"], count = engine.EDIT_UPDATE, index - 1, 1
+        else:
+            rec["flags"], rec["index"], count = 0, index, 1 + k % 2
+            index += count
+        rec["first"] = first
+        first += count
+    for k in range(begin + R, len(t)):
+        # (the record directly behind the object would pass for the update of its last value)
+        t[k]["flags"], t[k]["index"], t[k]["first"] = engine.EDIT_UPDATE | engine.EDIT_REMOVE, index - 1, first
+        first += 1 if k + 1 < len(t) else 0
+    return t, first, index   # the table, n_values, the object's length
+
+
+def _shift_index(t, begin, R, p, delta):
+    for k in range(p, R):
+        t[begin + k]["index"] = (int(t[begin + k]["index"]) + delta) & 0xFFFFFFFF
+
+
+def _premises_defects():
+    """name -> (flag word it must give, fn(t, begin, R, p, n_values) -> n_values or None where the defect has no place at record p)"""
+    def index0(t, begin, R, p, nv):
+        if p != 0:
+            return None   # (only record 0 has a fixed index; at any other record this is the gap)
+        t[begin]["index"] = 1
+        return nv
+
+    def first_order(t, begin, R, p, nv):
+        t[begin + p + 1]["first"] = t[begin + p]["first"]
+        return nv
+
+    def first_past(t, begin, R, p, nv):
+        return int(t[begin + p + 1]["first"]) - 1
+
+    def update_two(t, begin, R, p, nv):
+        # record p grows by one value (every `first` behind it and the indexes of the object behind it move along) and carries the bit
+        t["first"][begin + p + 1:] += 1
+        _shift_index(t, begin, R, p + 1, 1)
+        t[begin + p]["flags"] |= engine.EDIT_UPDATE
+        return nv + 1
+
+    def gap(t, begin, R, p, nv):
+        if p == 0:
+            return None
+        _shift_index(t, begin, R, p, 2)   # (2: an update record moved by 1 would open the next index)
+        return nv
+
+    def replaces_without_bit(t, begin, R, p, nv):
+        if p == 0:
+            return None
+        prev = t[begin + p - 1]
+        want = int(prev["index"]) + int(t[begin + p]["first"]) - int(prev["first"]) - 1
+        _shift_index(t, begin, R, p, want - int(t[begin + p]["index"]))
+        t[begin + p]["flags"] &= ~np.uint32(engine.EDIT_UPDATE)
+        return nv
+
+    def remove(t, begin, R, p, nv):
+        t[begin + p]["flags"] |= engine.EDIT_REMOVE
+        return nv
+
+    def past_32_bits(t, begin, R, p, nv):
+        # index + count == 2^32, which wraps to the index the record behind has. (In a table that passes every other check index + count
+        # <= the values in front of the next record, so this defect never stands alone: here with index != 0 or a gap in front of it.)
+        count = int(t[begin + p + 1]["first"]) - int(t[begin + p]["first"])
+        _shift_index(t, begin, R, p, (1 << 32) - count - int(t[begin + p]["index"]))
+        return nv
+
+    return {"index0": (RF_TABLE, index0), "first_order": (RF_TABLE, first_order), "first_past": (RF_TABLE, first_past), "update_two": (RF_TABLE, update_two),
+            "gap": (RF_TABLE, gap), "replaces_without_bit": (RF_TABLE, replaces_without_bit), "remove": (RF_REMOVE, remove), "past_32_bits": (RF_TABLE, past_32_bits)}
+
+
+def premises_cases(make_engine):
+    eng = make_engine()
+    try:
+        block = eng.text_locate_limits()[0]
+        n_cases = 0
+        # R = 1: only the last-record thread runs; R = block + 1: the last record alone in the second workgroup; begin > 0: foreign records on both sides
+        for R, begin, behind in ((1, 0, 0), (2, 0, 0), (3, 0, 0), (3, 5, 4), (1, 5, 4), (block + 1, 0, 0), (block + 1, 3, 2)):
+            good, n_values, length = _premises_table(R, begin, behind)
+            what = f"R={R} begin={begin}"
+            assert _premises_ref(good, begin, R, n_values) == (0, length), what
+            assert eng.prim_text_premises(good, begin, R, n_values, LENGTH_BEFORE) == (0, length), what
+            for p in sorted({0, R - 1, min(block - 1, R - 1)}):   # record 0, the last record, the last record of the first workgroup
+                for name, (flags, put) in _premises_defects().items():
+                    t = good.copy()
+                    nv = put(t, begin, R, p, n_values)
+                    if nv is None:
+                        continue
+                    want = _premises_ref(t, begin, R, nv)
+                    assert want[0] == flags, f"{what}: {name} at record {p}: the restated rule gives flags {want[0]}"
+                    assert eng.prim_text_premises(t, begin, R, nv, LENGTH_BEFORE) == want, f"{what}: {name} at record {p}"
+                    n_cases += 1
+        assert n_cases >= 7 * 8   # (every defect was placed)
+    finally:
+        eng.close()
+
+
+def test_text_premises_emulated(emu_lib):
+    premises_cases(_emulated(emu_lib))
+
+
+@pytest.mark.gpu
+def test_text_premises_gpu():
+    premises_cases(_gpu)
