@@ -572,17 +572,17 @@ extern "C" int am355_test_carried_scan(am355_ctx* c, const uint32_t* v, uint32_t
 
 // table: n_recs edit records, the sentinel among them; the check pass of the Text calls (am355_textrec.h rec_premises) runs over the R
 // records from `begin` on. *flags: the premise bits; *length: what the word held before the call, and after it.
-extern "C" int am355_test_text_premises(am355_ctx* c, const am355_ir_edit* table, uint32_t n_recs, uint32_t begin, uint32_t R, uint32_t n_values, uint32_t* flags,
-                                        uint32_t* length) {
+static int test_premises(am355_ctx* c, const char* who, void (*launch)(const TextRecs&, uint32_t*, hipStream_t), const am355_ir_edit* table, uint32_t n_recs, uint32_t begin,
+                         uint32_t R, uint32_t n_values, uint32_t* flags, uint32_t* length) {
   if (!c || !table || !flags || !length) return AM355_E_ARG;
   return guarded(c, [&]() -> int {
-    if (!R || (uint64_t)begin + R + 1 > n_recs) return fail(c, AM355_E_ARG, "am355_test_text_premises: the records (and the one behind them) leave the table");
+    if (!R || (uint64_t)begin + R + 1 > n_recs) return fail(c, AM355_E_ARG, "%s: the records (and the one behind them) leave the table", who);
     (void)hipSetDevice(c->device);
     hipStream_t st = c->stream;
     TestImage dt, dw;
     uint32_t words[2] = {0u, *length};
     if (!dt.up(table, sizeof(am355_ir_edit) * (size_t)n_recs, st) || !dw.up(words, 8, st)) return fail(c, AM355_E_NOMEM, "alloc");
-    launch_text_check(TextRecs{(const am355_ir_edit*)dt.p, begin, R, n_values}, dw.words(), st);
+    launch(TextRecs{(const am355_ir_edit*)dt.p, begin, R, n_values}, dw.words(), st);
     dw.down(words, st);
     int rc = test_finish(c);
     if (rc != AM355_OK) return rc;
@@ -590,6 +590,15 @@ extern "C" int am355_test_text_premises(am355_ctx* c, const am355_ir_edit* table
     *length = words[1];
     return AM355_OK;
   });
+}
+extern "C" int am355_test_text_premises(am355_ctx* c, const am355_ir_edit* table, uint32_t n_recs, uint32_t begin, uint32_t R, uint32_t n_values, uint32_t* flags,
+                                        uint32_t* length) {
+  return test_premises(c, "am355_test_text_premises", launch_text_check, table, n_recs, begin, R, n_values, flags, length);
+}
+// the same over the check pass of the calls on a plain list (am355_list_locate.hip klist_check)
+extern "C" int am355_test_list_premises(am355_ctx* c, const am355_ir_edit* table, uint32_t n_recs, uint32_t begin, uint32_t R, uint32_t n_values, uint32_t* flags,
+                                        uint32_t* length) {
+  return test_premises(c, "am355_test_list_premises", launch_list_check, table, n_recs, begin, R, n_values, flags, length);
 }
 
 extern "C" int am355_get_rows(am355_ctx* c, uint32_t* obj_actor, uint32_t* obj_ctr, uint32_t* key_actor, uint32_t* key_ctr, uint32_t* key_off,

@@ -997,3 +997,9 @@ int sync_bloom_impl(am355_ctx* c, const uint32_t* idx, uint32_t n, uint32_t num_
 // elemIds of a Text resolved to positions, deleted elements included (am355_text_position): likewise
 // ---------------------------------------------------------------------------------------------------------
 #include "am355_position.hip"
+
+// ---------------------------------------------------------------------------------------------------------
+// positions of a plain list resolved to ids and every pred, the edit and the assignment by position (am355_list_locate, am355_list_splice,
+// am355_list_set): likewise
+// ---------------------------------------------------------------------------------------------------------
+#include "am355_list_locate.hip"

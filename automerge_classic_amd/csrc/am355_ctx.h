@@ -8,6 +8,7 @@
 //     am355_text.hip      the string of a Text object
 //     am355_locate.hip    positions of a Text to ids, the edit by position
 //     am355_position.hip  elemIds of a Text to positions (the three share am355_textrec.h)
+//     am355_list_locate.hip  positions of a plain list to ids and every pred, the edit and the assignment by position (shares it too)
 //   am355_save.hip    save + history after load
 //   am355_shard.hip   objectId sharding
 #pragma once
@@ -611,6 +612,10 @@ struct am355_ctx {
   DevBuf d_loc, d_loc_runs;                        // result words | ids | head bits | counter bits | scanned heads | scan workspace; the runs behind LOCATE_PINNED_RUNS
   HostBuf h_loc_runs;                              // pinned: the runs (valid until the next call)
   uint64_t n_splice_served = 0, n_splice_refused = 0, n_locate_launches = 0;   // am355_text_splice_calls
+  // am355_list_locate / am355_list_splice / am355_list_set (am355_list_locate.hip): positions of a plain list resolved to runs of (elemId, every pred)
+  DevBuf d_lloc, d_lloc_runs, d_lloc_preds;        // result words | ids | per-element words | scans | scan workspace; the runs and the preds behind LOCATE_PINNED_RUNS
+  HostBuf h_lloc_runs, h_lloc_preds;               // pinned: the runs and their preds (valid until the next call)
+  uint64_t n_list_served = 0, n_list_refused = 0, n_list_launches = 0;   // am355_list_splice_calls
   // am355_text_position (am355_position.hip): elemIds of a Text resolved to positions on the device, by a search in the stored list order (d_pos)
   DevBuf d_posq;                                   // result words | rec_pos | the queries and the results behind LOCATE_PINNED_RUNS
   HostBuf h_pos_out, h_pos_ids;                    // pinned: the results (valid until the next call) | the queries

@@ -40,19 +40,6 @@ void launch_text_check(const TextRecs& t, uint32_t* words, hipStream_t st) {
   AM355_LAUNCH_INDEPENDENT(kl_check, dim3((t.R + BLOCK - 1) / BLOCK), dim3(BLOCK), st, t, words);
 }
 
-// ids of element j: the last record with index <= j (indexes are non-decreasing: kl_check). Reads only records of [begin, begin + R).
-__device__ __forceinline__ uint4 locate_ids(const TextRecs& t, uint32_t j, uint32_t& counter) {
-  uint32_t lo = 0, hi = t.R;   // t[lo].index <= j < t[hi].index (record 0 has index 0; hi == R: the end)
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (t[mid].index <= j) lo = mid; else hi = mid;
-  }
-  const am355_ir_edit& rec = t[lo];
-  const uint32_t d = j - rec.index;
-  counter = rec_is_counter(rec) ? 1u : 0u;
-  return uint4{rec.elem_ctr + d, rec.elem_actor, rec.id_ctr + d, rec.id_actor};
-}
-
 // Locate, one thread per queried element first + i: ids[i], counter[i] and head[i] = 1 iff the element does not continue the one before
 // it by the multiOp rule. Element 0 is a head, and so is element `lead` (1: the range begins one element early -- the reference element
 // of an insertion, which is no deletion and must not merge with the first one; 0: no such element). The neighbour's ids come from LDS;
@@ -184,15 +171,65 @@ int text_locate_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, s
   return AM355_OK;
 }
 
-// actors of a request: raw ids, each once, the author first and the others in byte order (columnar.js:154-157)
+// actors of a request: raw ids, each once, the author first and the others in byte order (columnar.js:154-157), as the tables of
+// am355_local_change
 struct SpliceActors {
   std::vector<std::string> table;
+  std::vector<uint32_t> off, rank;
+  std::vector<uint8_t> bytes;
+  SpliceActors(const std::string& me, std::vector<std::string> others) {
+    std::sort(others.begin(), others.end());
+    others.erase(std::unique(others.begin(), others.end()), others.end());
+    table.push_back(me);
+    for (const std::string& a : others)
+      if (a != me) table.push_back(a);
+    const uint32_t n = (uint32_t)table.size();
+    off.assign(n + 1, 0); rank.assign(n, 0);
+    for (uint32_t k = 0; k < n; k++) {
+      bytes.insert(bytes.end(), table[k].begin(), table[k].end());
+      off[k + 1] = (uint32_t)bytes.size();
+      // (entries 1 .. are in byte order already: the author's rank is the number of them in front of it)
+      rank[k] = k == 0 ? (uint32_t)(std::lower_bound(table.begin() + 1, table.end(), me) - (table.begin() + 1)) : (k - 1) + (table[k] > me ? 1u : 0u);
+    }
+  }
   uint32_t local(const std::string& a) const {
     for (uint32_t k = 0; k < table.size(); k++)
       if (table[k] == a) return k;
     return NONE32;
   }
 };
+
+// The request of a positional edit completed and applied: seq = the author's clock entry + 1, startOp = maxOp + 1, deps = the heads
+// without the author's last change, which am355_apply_local_change adds itself (backend.js:73-81, 88-89).
+int splice_apply(am355_ctx* c, const SpliceActors& act, const uint8_t* author, size_t author_len, int64_t time, const uint8_t* message, uint32_t message_len,
+                 const uint8_t* strings, uint32_t strings_len, const std::vector<am355_local_op>& ops, const std::vector<am355_local_value>& values,
+                 const std::vector<am355_local_pred>& preds, const uint8_t** change, size_t* len) {
+  am355_local_change lc{};
+  lc.seq = 1;
+  uint32_t rank = 0;
+  if (actor_rank_of(c, author, author_len, &rank))
+    for (size_t k = 0; k < c->clock_actor.size(); k++)
+      if (c->clock_actor[k] == rank) lc.seq = c->clock_seq[k] + 1;
+  lc.start_op = c->max_op + 1;
+  lc.time = time;
+  lc.message = message; lc.message_len = message_len;
+  std::vector<uint8_t> deps(c->heads);
+  uint32_t last = NONE32;
+  int rc;
+  if (lc.seq > 1 && c->h_hashes.p && (rc = staged_change_of(c, author, author_len, lc.seq - 1, &last))) return rc;
+  if (last != NONE32) {
+    const uint8_t* h = c->h_hashes.as<uint8_t>() + 32 * (size_t)last;
+    for (size_t k = 0; k + 32 <= deps.size(); k += 32)
+      if (memcmp(&deps[k], h, 32) == 0) { deps.erase(deps.begin() + k, deps.begin() + k + 32); break; }
+  }
+  lc.deps = deps.data(); lc.n_deps = (uint32_t)(deps.size() / 32);
+  lc.n_actors = (uint32_t)act.table.size(); lc.actor_off = act.off.data(); lc.actor_bytes = act.bytes.data(); lc.actor_rank = act.rank.data();
+  lc.strings = strings; lc.strings_len = strings_len;
+  lc.ops = ops.data(); lc.n_ops = (uint32_t)ops.size();
+  lc.values = values.data(); lc.n_values = (uint32_t)values.size();
+  lc.preds = preds.data(); lc.n_preds = (uint32_t)preds.size();
+  return apply_local_change_impl(c, &lc, change, len);
+}
 
 int text_splice_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint64_t start, uint64_t deletions, const uint8_t* utf8,
                      const uint32_t* value_off, uint32_t n_values, const uint8_t* author, size_t author_len, int64_t time, const uint8_t* message, uint32_t message_len,
@@ -231,29 +268,12 @@ int text_splice_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, s
   for (uint32_t r = 0; r < n_runs; r++)
     if (runs[r].elem_actor >= NA || runs[r].pred_actor >= NA) return refused(fail(c, AM355_E_DEVICE, "internal: run %u names an actor outside the table", r));
   const std::string me((const char*)author, author_len), obj_a((const char*)obj_actor, actor_len);
-  SpliceActors act;
-  {
-    std::vector<std::string> others{obj_a};
-    for (uint32_t r = 0; r < n_runs; r++) {
-      if (r >= lead || n_values) others.push_back(c->actors[runs[r].elem_actor]);
-      if (r >= lead) others.push_back(c->actors[runs[r].pred_actor]);
-    }
-    std::sort(others.begin(), others.end());
-    others.erase(std::unique(others.begin(), others.end()), others.end());
-    act.table.push_back(me);
-    for (const std::string& a : others)
-      if (a != me) act.table.push_back(a);
+  std::vector<std::string> others{obj_a};
+  for (uint32_t r = 0; r < n_runs; r++) {
+    if (r >= lead || n_values) others.push_back(c->actors[runs[r].elem_actor]);
+    if (r >= lead) others.push_back(c->actors[runs[r].pred_actor]);
   }
-  const uint32_t n_act = (uint32_t)act.table.size();
-  std::vector<uint32_t> actor_off(n_act + 1, 0), actor_rank(n_act, 0);
-  std::vector<uint8_t> actor_bytes;
-  for (uint32_t k = 0; k < n_act; k++) {
-    actor_bytes.insert(actor_bytes.end(), act.table[k].begin(), act.table[k].end());
-    actor_off[k + 1] = (uint32_t)actor_bytes.size();
-    // (entries 1 .. are in byte order already: the author's rank is the number of them in front of it)
-    actor_rank[k] = k == 0 ? (uint32_t)(std::lower_bound(act.table.begin() + 1, act.table.end(), me) - (act.table.begin() + 1))
-                           : (k - 1) + (act.table[k] > me ? 1u : 0u);
-  }
+  const SpliceActors act(me, others);
   std::vector<am355_local_op> ops;
   std::vector<am355_local_pred> preds;
   std::vector<am355_local_value> values;
@@ -281,32 +301,8 @@ int text_splice_impl(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, s
     for (uint32_t k = 0; k < n_values; k++) values.push_back(am355_local_value{AM355_LV_UTF8, value_off[k], value_off[k + 1] - value_off[k], 0, 0});
     ops.push_back(op);
   }
-  am355_local_change lc{};
-  lc.seq = 1;
-  uint32_t rank = 0;
-  if (actor_rank_of(c, author, author_len, &rank))
-    for (size_t k = 0; k < c->clock_actor.size(); k++)
-      if (c->clock_actor[k] == rank) lc.seq = c->clock_seq[k] + 1;
-  lc.start_op = c->max_op + 1;
-  lc.time = time;
-  lc.message = message; lc.message_len = message_len;
-  // deps: the heads without the author's last change, which am355_apply_local_change adds itself (backend.js:73-81, 88-89)
-  std::vector<uint8_t> deps(c->heads);
-  uint32_t last = NONE32;
-  if (lc.seq > 1 && c->h_hashes.p && (rc = staged_change_of(c, author, author_len, lc.seq - 1, &last))) return refused(rc);
-  if (last != NONE32) {
-    const uint8_t* h = c->h_hashes.as<uint8_t>() + 32 * (size_t)last;
-    for (size_t k = 0; k + 32 <= deps.size(); k += 32)
-      if (memcmp(&deps[k], h, 32) == 0) { deps.erase(deps.begin() + k, deps.begin() + k + 32); break; }
-  }
-  lc.deps = deps.data(); lc.n_deps = (uint32_t)(deps.size() / 32);
-  lc.n_actors = n_act; lc.actor_off = actor_off.data(); lc.actor_bytes = actor_bytes.data(); lc.actor_rank = actor_rank.data();
-  lc.strings = utf8; lc.strings_len = n_values ? value_off[n_values] : 0u;
-  lc.ops = ops.data(); lc.n_ops = (uint32_t)ops.size();
-  lc.values = values.data(); lc.n_values = (uint32_t)values.size();
-  lc.preds = preds.data(); lc.n_preds = (uint32_t)preds.size();
   lap("request built");
-  rc = apply_local_change_impl(c, &lc, change, len);
+  rc = splice_apply(c, act, author, author_len, time, message, message_len, utf8, n_values ? value_off[n_values] : 0u, ops, values, preds, change, len);
   lap("applied");
   if (rc) return refused(rc);
   c->n_splice_served++;

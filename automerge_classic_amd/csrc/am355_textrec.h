@@ -85,12 +85,30 @@ __device__ __forceinline__ uint32_t rec_premises(const TextRecs& t, uint32_t k, 
   if (k + 1 == t.R) { length = rec.index + count; return 0; }
   return t[k + 1].index == rec.index + count || rec_overwritten(t, k, count) ? 0u : (uint32_t)RF_TABLE;
 }
+// the last record with index <= j (indexes are non-decreasing: the check pass). Reads only records of [begin, begin + R), R >= 1.
+__device__ __forceinline__ uint32_t rec_last_at(const TextRecs& t, uint32_t j) {
+  uint32_t lo = 0, hi = t.R;   // t[lo].index <= j < t[hi].index (record 0 has index 0; hi == R: the end)
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (t[mid].index <= j) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+// ids of element j by THE IDS OF AN ELEMENT above: {elemId ctr, elemId actor, id ctr, id actor} of its last edit; counter = rec_is_counter of it
+__device__ __forceinline__ uint4 locate_ids(const TextRecs& t, uint32_t j, uint32_t& counter) {
+  const am355_ir_edit& rec = t[rec_last_at(t, j)];
+  const uint32_t d = j - rec.index;
+  counter = rec_is_counter(rec) ? 1u : 0u;
+  return uint4{rec.elem_ctr + d, rec.elem_actor, rec.id_ctr + d, rec.id_actor};
+}
 // where item i of a result goes: pinned[i] for i < LOCATE_PINNED_RUNS, else spill[i - LOCATE_PINNED_RUNS]
 template <class T>
 __device__ __forceinline__ T* pinned_or_spill(T* pinned, T* spill, uint32_t i) { return i < LOCATE_PINNED_RUNS ? pinned + i : spill + (i - LOCATE_PINNED_RUNS); }
 
 // the check pass (am355_locate.hip kl_check) over t: words[0] |= the premise bits, words[1] = the length when there are none
 void launch_text_check(const TextRecs& t, uint32_t* words, hipStream_t st);
+// the check pass of the calls on a plain list (am355_list_locate.hip klist_check): the same words, and its own bit for an element without an insert
+void launch_list_check(const TextRecs& t, uint32_t* words, hipStream_t st);
 
 // device words of the lookup and of a read (d_text): what kt_find found, then the totals and the flag word of kt_sizes
 enum TextWord { TW_INDEX = 0, TW_TYPE = 1, TW_BEGIN = 2, TW_END = 3, TW_BYTES = 4, TW_ELEMS = 5, TW_NONSTR = 6, TW_FLAGS = 7, TW_WORDS = 8 };
@@ -138,9 +156,10 @@ static inline int text_premise_error(am355_ctx* c, TextCall call, uint32_t flags
 enum TextOpenFlag : uint32_t { TO_CHANGE_STATE = 1,   // a document context becomes the state of its rebuilt changes first (as am355_apply_local_change)
                                TO_NO_QUEUE = 2 };     // refused on a state with queued changes
 struct TextObject { uint32_t index, actor_rank; TextRecs recs; };   // index in the object table | rank of the id's actor | its records
-// The opening of a call `who` on the Text (obj_ctr, obj_actor): the state it needs, the edit tables fresh, the object found -- from the host's copy
+// The opening of a call `who` on the Text (or, want_type 2, the plain list) (obj_ctr, obj_actor): the state it needs, the edit tables fresh, the object found -- from the host's copy
 // of the object table when it is the device's, else one launch over ir.obj (+ the launch that signals the four words; counted in *launches).
-static inline int text_open(am355_ctx* c, const char* who, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint32_t flags, uint64_t* launches, TextObject& o) {
+static inline int text_open(am355_ctx* c, const char* who, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint32_t flags, uint64_t* launches, TextObject& o,
+                            uint32_t want_type = 4) {   // (4: a Text; 2: a plain list)
   if (!c->replayed) return fail(c, AM355_E_STATE, "%s: a replayed state is needed", who);
   if (c->shard_world > 1) return fail(c, AM355_E_UNSUPPORTED, "%s on a sharded context", who);
   (void)hipSetDevice(c->device);
@@ -158,7 +177,8 @@ static inline int text_open(am355_ctx* c, const char* who, uint64_t obj_ctr, con
     for (size_t k = 0; k < actor_len; k++) { id.push_back("0123456789abcdef"[obj_actor[k] >> 4]); id.push_back("0123456789abcdef"[obj_actor[k] & 15]); }
     return fail(c, AM355_E_ARG, "no such object: %s", id.c_str());
   };
-  if (obj_ctr == 0 && actor_len == 0) return fail(c, AM355_E_ARG, "not a Text object");   // (_root: a map)
+  const char* not_wanted = want_type == 4 ? "not a Text object" : "not a list object";
+  if (obj_ctr == 0 && actor_len == 0) return fail(c, AM355_E_ARG, "%s", not_wanted);   // (_root: a map)
   uint32_t rank = 0;
   if (obj_ctr > 0xffffffffull || !actor_rank_of(c, obj_actor, actor_len, &rank)) return no_such();
   if (!c->d_text.ensure(TW_WORDS * 4) || !c->text_sig.ready()) return fail(c, AM355_E_NOMEM, "allocation failed (text)");
@@ -179,7 +199,7 @@ static inline int text_open(am355_ctx* c, const char* who, uint64_t obj_ctr, con
     oi = hw[TW_INDEX]; type = hw[TW_TYPE]; eb = hw[TW_BEGIN]; ee = hw[TW_END];
   }
   if (oi == NONE32) return no_such();
-  if (type != 4) return fail(c, AM355_E_ARG, "not a Text object");
+  if (type != want_type) return fail(c, AM355_E_ARG, "%s", not_wanted);
   if (eb > ee || ee > NR) return fail(c, AM355_E_DEVICE, "internal: edit range [%u, %u) of object %u outside the %u records", eb, ee, oi, NR);
   o.index = oi; o.actor_rank = rank;
   o.recs = TextRecs{(const am355_ir_edit*)c->ir.edit, eb, ee - eb, c->counts.n_edits};

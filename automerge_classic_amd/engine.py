@@ -45,6 +45,9 @@ class TextInfo(ctypes.Structure):
 
 # am355_text_run: a run of consecutive (elemId, pred) pairs of a Text (actors: ranks of the engine's actor table)
 TEXT_RUN_DTYPE = np.dtype([("elem_ctr", "<u4"), ("elem_actor", "<u4"), ("pred_ctr", "<u4"), ("pred_actor", "<u4"), ("count", "<u4"), ("flags", "<u4")])
+# am355_list_run / am355_list_pred: a run of consecutive elements of a plain list and the preds of its elements
+LIST_RUN_DTYPE = np.dtype([("elem_ctr", "<u4"), ("elem_actor", "<u4"), ("count", "<u4"), ("flags", "<u4"), ("pred_first", "<u4"), ("pred_num", "<u4")])
+LIST_PRED_DTYPE = np.dtype([("actor", "<u4"), ("ctr", "<u4")])
 RUN_COUNTER = 1
 ELEM_ID_DTYPE = np.dtype([("ctr", "<u4"), ("actor", "<u4")])              # am355_elem_id
 ELEM_POS_DTYPE = np.dtype([("position", "<u4"), ("status", "<u4")])       # am355_elem_pos
@@ -388,6 +391,18 @@ def _bind(path):
         L.am355_text_locate_limits.argtypes = [vp]
         for f in ("am355_text_locate", "am355_text_splice", "am355_text_splice_calls", "am355_text_locate_limits"):
             getattr(L, f).restype = ctypes.c_int
+    if hasattr(L, "am355_list_splice"):   # (libraries of earlier commits, loaded for an A/B run, end before these)
+        pvp, psz = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)
+        L.am355_list_locate.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, pvp, ctypes.POINTER(u32), pvp, ctypes.POINTER(u32),
+                                        ctypes.POINTER(ctypes.c_uint64)]
+        L.am355_list_splice.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, vp, u32, vp, u32, vp, ctypes.c_size_t, ctypes.c_int64, vp, u32,
+                                        pvp, psz]
+        L.am355_list_set.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_size_t, ctypes.c_uint64, vp, vp, u32, vp, ctypes.c_size_t, ctypes.c_int64, vp, u32, pvp, psz]
+        L.am355_list_splice_calls.argtypes = [vp, vp]
+        L.am355_list_locate_limits.argtypes = [vp]
+        L.am355_test_list_premises.argtypes = [vp, vp, u32, u32, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+        for f in ("am355_list_locate", "am355_list_splice", "am355_list_set", "am355_list_splice_calls", "am355_list_locate_limits", "am355_test_list_premises"):
+            getattr(L, f).restype = ctypes.c_int
     if hasattr(L, "am355_text_position"):   # (libraries of earlier commits, loaded for an A/B run, end before these)
         L.am355_text_position.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_size_t, vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
         L.am355_rank_of_actor.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(u32)]
@@ -708,6 +723,97 @@ class Engine:
         """(elements per workgroup of the locate kernel, elements the head scan takes in one workgroup, runs written straight to pinned memory)."""
         out = (ctypes.c_uint32 * 3)()
         self._check(self._L.am355_text_locate_limits(out))
+        return tuple(int(x) for x in out)
+
+    def list_locate(self, object_id, first, n):
+        """Elements [first, first + n) of a plain list resolved to ids on the device (am355_list_locate): (runs, preds, length). runs: a
+        structured array (LIST_RUN_DTYPE) of runs of consecutive elemIds, each with the range [pred_first, pred_first + pred_num) of
+        preds (LIST_PRED_DTYPE; a run of several elements has one pred, which counts up with the elemId); actors as ranks. EngineError
+        with code AM355_E_ARG: no such object / not a list object / the range reaches past the length."""
+        ctr, actor, buf = self._object_id(object_id)
+        p, q, nr, nq, length = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
+        self._check(self._L.am355_list_locate(self._h, ctr, ctypes.cast(buf, ctypes.c_void_p), len(actor), int(first), int(n), ctypes.byref(p), ctypes.byref(nr),
+                                              ctypes.byref(q), ctypes.byref(nq), ctypes.byref(length)))
+        runs, preds = np.zeros(nr.value, dtype=LIST_RUN_DTYPE), np.zeros(nq.value, dtype=LIST_PRED_DTYPE)
+        if nr.value:
+            ctypes.memmove(runs.ctypes.data, p, nr.value * LIST_RUN_DTYPE.itemsize)
+        if nq.value:
+            ctypes.memmove(preds.ctypes.data, q, nq.value * LIST_PRED_DTYPE.itemsize)
+        return runs, preds, int(length.value)
+
+    @staticmethod
+    def _list_values(values):
+        """values of list_splice / list_set as am355_local_value: a plain str / bool / None / int (-> int) / float (-> float64), or a
+        pair (datatype, number) with datatype 'int', 'uint', 'float64', 'counter' or 'timestamp'."""
+        out = np.zeros(len(values), dtype=_VALUE_DTYPE)
+        strings = bytearray()
+        for k, v in enumerate(values):
+            datatype = None
+            if isinstance(v, tuple):
+                datatype, v = v
+            if v is None and datatype is None:
+                out[k]["tag"] = LV_NULL
+            elif isinstance(v, bool) and datatype is None:
+                out[k]["tag"] = LV_TRUE if v else LV_FALSE
+            elif isinstance(v, str) and datatype is None:
+                b = v.encode("utf-8")
+                out[k] = (LV_UTF8, len(strings), len(b), 0, 0)
+                strings.extend(b)
+            elif isinstance(v, (bytes, bytearray)) and datatype is None:
+                out[k]["tag"] = LV_BYTES
+            elif isinstance(v, (int, float)) and not isinstance(v, bool):
+                if datatype is None:
+                    datatype = "int" if isinstance(v, int) else "float64"
+                if datatype == "float64":
+                    out[k] = (LV_FLOAT64, 0, 0, 0, int(np.array([float(v)], dtype="<f8").view("<u8")[0]))
+                elif datatype in ("int", "uint", "counter", "timestamp") and isinstance(v, int) and abs(v) <= _MAX_SAFE and (datatype != "uint" or v >= 0):
+                    out[k] = ({"counter": LV_COUNTER, "timestamp": LV_TIMESTAMP, "int": LV_INT, "uint": LV_UINT}[datatype], 0, 0, 0, v & 0xFFFFFFFFFFFFFFFF)
+                else:
+                    out[k]["tag"] = LV_BAD
+            else:
+                out[k]["tag"] = LV_BAD
+        return out, np.frombuffer(bytes(strings) or b"\0", dtype=np.uint8), len(strings)
+
+    def _list_call(self, call, object_id, where, values, actor, time, message):
+        ctr, obj_actor, buf = self._object_id(object_id)
+        vals, blob, blob_len = self._list_values(values)
+        author = np.frombuffer(bytes.fromhex(actor), dtype=np.uint8)
+        raw = message.encode("utf-8")
+        msg = np.frombuffer(raw or b"\0", dtype=np.uint8)
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        head = (self._h, ctr, ctypes.cast(buf, ctypes.c_void_p), len(obj_actor)) + where
+        vargs = (vals.ctypes.data if vals.size else None, len(values)) if call == "splice" else (vals.ctypes.data,)
+        fn = self._L.am355_list_splice if call == "splice" else self._L.am355_list_set
+        self._check(fn(*head, *vargs, blob.ctypes.data, blob_len, author.ctypes.data if author.size else None, author.size, int(time), msg.ctypes.data, len(raw),
+                       ctypes.byref(p), ctypes.byref(n)))
+        if n.value:
+            self._n_changes = int(self.stats().n_changes)
+        return ctypes.string_at(p, n.value) if n.value else b""
+
+    def list_splice(self, object_id, start, deletions, values, actor, time=0, message=""):
+        """One context.splice of the reference's frontend on a plain list the engine holds (am355_list_splice): delete `deletions` elements
+        from position `start` on, then insert `values` there (see _list_values for their form); `actor`: the author's id in hex. Returns
+        the binary change (b"" when there was nothing to do); apply_patch_json() then gives the patch. EngineError with code AM355_E_ARG
+        and the reference's RangeError text when the range is out of bounds, InvalidChanges with its TypeError text for a deleted element
+        that shows a counter. The caller owns the author and the order of its calls."""
+        return self._list_call("splice", object_id, (int(start), int(deletions)), list(values), actor, time, message)
+
+    def list_set(self, object_id, index, value, actor, time=0, message=""):
+        """list[index] = value (am355_list_set, context.js setListIndex): an index at or past the length inserts nulls up to it and the
+        value; InvalidChanges with the reference's RangeError text onto an element that shows a counter. The op is always emitted: the
+        reference skips an assignment of the value the element already shows, the engine holds no JS values to compare."""
+        return self._list_call("set", object_id, (int(index),), [value], actor, time, message)
+
+    def list_splice_calls(self):
+        """(list_splice / list_set calls served, refused, kernel launches of the locate half of the three list calls)."""
+        out = (ctypes.c_uint64 * 3)()
+        self._check(self._L.am355_list_splice_calls(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def list_locate_limits(self):
+        """(elements per workgroup of the locate kernel, elements the scan takes in one workgroup, runs / preds written straight to pinned memory)."""
+        out = (ctypes.c_uint32 * 3)()
+        self._check(self._L.am355_list_locate_limits(out))
         return tuple(int(x) for x in out)
 
     def rank_of_actor(self, actor):
@@ -1053,6 +1159,13 @@ class Engine:
         t = np.ascontiguousarray(table, dtype=IR_EDIT_DTYPE)
         flags, length = ctypes.c_uint32(0), ctypes.c_uint32(length_before)
         self._check(self._L.am355_test_text_premises(self._h, t.ctypes.data, t.size, begin, n_recs, n_values, ctypes.byref(flags), ctypes.byref(length)))
+        return flags.value, length.value
+
+    def prim_list_premises(self, table, begin, n_recs, n_values, length_before=0xdeadbeef):
+        """am355_test_list_premises: the same over the check pass of the calls on a plain list (bit 8: an element without an insert)."""
+        t = np.ascontiguousarray(table, dtype=IR_EDIT_DTYPE)
+        flags, length = ctypes.c_uint32(0), ctypes.c_uint32(length_before)
+        self._check(self._L.am355_test_list_premises(self._h, t.ctypes.data, t.size, begin, n_recs, n_values, ctypes.byref(flags), ctypes.byref(length)))
         return flags.value, length.value
 
     def rows(self):

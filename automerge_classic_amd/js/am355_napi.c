@@ -1196,6 +1196,99 @@ static napi_value js_text_splice(napi_env env, napi_callback_info info) {
   return change;
 }
 
+/* listLocate(ctx, ctr, Uint8Array actor, first, n) -> { length, runs: [{ elemId, preds: [opId, ...], count, counter }] } = am355_list_locate:
+ * the elements [first, first + n) of a plain list as runs of consecutive elemIds; a run of several elements has one pred, which counts up
+ * with the elemId; ids as strings */
+static napi_value js_list_locate(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5], out, runs_js, v;
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  double ctr = -1, first = -1, n = -1;
+  const uint8_t *actor = NULL;
+  size_t actor_len = 0;
+  if (argc < 5 || napi_get_value_double(env, argv[1], &ctr) != napi_ok || !get_u8_array(env, argv[2], &actor, &actor_len) ||
+      napi_get_value_double(env, argv[3], &first) != napi_ok || napi_get_value_double(env, argv[4], &n) != napi_ok || ctr < 0 || ctr > 4294967295.0 || first < 0 ||
+      n < 0 || first > 9007199254740991.0 || n > 9007199254740991.0) {
+    napi_throw_type_error(env, NULL, "listLocate takes a counter, the actor's bytes, a first position and a count");
+    return NULL;
+  }
+  const am355_list_run *runs = NULL;
+  const am355_list_pred *preds = NULL;
+  uint32_t n_runs = 0, n_preds = 0;
+  uint64_t length = 0;
+  int rc = am355_list_locate(ctx, (uint64_t)ctr, actor, actor_len, (uint64_t)first, (uint64_t)n, &runs, &n_runs, &preds, &n_preds, &length);
+  if (rc) return throw_engine(env, ctx, rc);
+  NAPI_CALL(env, napi_create_object(env, &out));
+  NAPI_CALL(env, napi_create_double(env, (double)length, &v));
+  NAPI_CALL(env, napi_set_named_property(env, out, "length", v));
+  NAPI_CALL(env, napi_create_array_with_length(env, n_runs, &runs_js));
+  for (uint32_t r = 0; r < n_runs; r++) {
+    napi_value o, preds_js;
+    NAPI_CALL(env, napi_create_object(env, &o));
+    if (!id_string(env, ctx, runs[r].elem_ctr, runs[r].elem_actor, &v)) { napi_throw_error(env, NULL, "listLocate: a run names an actor outside the table"); return NULL; }
+    NAPI_CALL(env, napi_set_named_property(env, o, "elemId", v));
+    NAPI_CALL(env, napi_create_array_with_length(env, runs[r].pred_num, &preds_js));
+    for (uint32_t q = 0; q < runs[r].pred_num; q++) {
+      const am355_list_pred *p = &preds[runs[r].pred_first + q];   /* (inside the array: am355_list_locate checks every run) */
+      if (!id_string(env, ctx, p->ctr, p->actor, &v)) { napi_throw_error(env, NULL, "listLocate: a pred names an actor outside the table"); return NULL; }
+      NAPI_CALL(env, napi_set_element(env, preds_js, q, v));
+    }
+    NAPI_CALL(env, napi_set_named_property(env, o, "preds", preds_js));
+    NAPI_CALL(env, napi_create_uint32(env, runs[r].count, &v));
+    NAPI_CALL(env, napi_set_named_property(env, o, "count", v));
+    NAPI_CALL(env, napi_get_boolean(env, (runs[r].flags & AM355_RUN_COUNTER) != 0, &v));
+    NAPI_CALL(env, napi_set_named_property(env, o, "counter", v));
+    NAPI_CALL(env, napi_set_element(env, runs_js, r, o));
+  }
+  NAPI_CALL(env, napi_set_named_property(env, out, "runs", runs_js));
+  return out;
+}
+/* listSplice(ctx, ctr, Uint8Array actor, start, deletions, Uint32Array values, Uint8Array strings, Uint8Array author, time, Uint8Array message)
+ * listSet(ctx, ctr, Uint8Array actor, index, Uint32Array value, Uint8Array strings, Uint8Array author, time, Uint8Array message)
+ * -> Uint8Array (the binary change; empty: there was nothing to do) = am355_list_splice / am355_list_set. values: six words per value, the
+ * layout of am355_local_value (js/local_change.js flattenValues); the patch is then read with fetchApplyIR */
+static napi_value list_edit(napi_env env, napi_callback_info info, bool is_set) {
+  size_t argc = 10, want = is_set ? 9 : 10, a = is_set ? 4 : 5;
+  napi_value argv[10];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  double ctr = -1, start = -1, deletions = 0, time = 0;
+  const uint8_t *actor = NULL, *strings = NULL, *author = NULL, *message = NULL;
+  size_t actor_len = 0, strings_len = 0, author_len = 0, message_len = 0, n_words = 0;
+  uint32_t *words = NULL;
+  const size_t vw = sizeof(am355_local_value) / 4;
+  if (argc < want || napi_get_value_double(env, argv[1], &ctr) != napi_ok || !get_u8_array(env, argv[2], &actor, &actor_len) ||
+      napi_get_value_double(env, argv[3], &start) != napi_ok || (!is_set && napi_get_value_double(env, argv[4], &deletions) != napi_ok) ||
+      !get_u32_array(env, argv[a], &words, &n_words) || !get_u8_array(env, argv[a + 1], &strings, &strings_len) || !get_u8_array(env, argv[a + 2], &author, &author_len) ||
+      napi_get_value_double(env, argv[a + 3], &time) != napi_ok || !get_u8_array(env, argv[a + 4], &message, &message_len) || ctr < 0 || ctr > 4294967295.0 || start < 0 ||
+      deletions < 0 || start > 9007199254740991.0 || deletions > 9007199254740991.0 || n_words % vw || n_words / vw > 0xffffffffu || (is_set && n_words != vw) ||
+      strings_len > 0xffffffffu || message_len > 0xffffffffu || time != (double)(int64_t)time) {
+    napi_throw_type_error(env, NULL, is_set ? "listSet takes (ctx, counter, actor bytes, index, one value, strings, author bytes, time, message bytes)"
+                                            : "listSplice takes (ctx, counter, actor bytes, start, deletions, values, strings, author bytes, time, message bytes)");
+    return NULL;
+  }
+  am355_local_value *values = (am355_local_value *)malloc(n_words ? n_words * 4 : 1);   /* (a copy: the struct holds a 64-bit word) */
+  if (!values) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  if (n_words) memcpy(values, words, n_words * 4);
+  const uint8_t *bytes = NULL;
+  size_t len = 0;
+  int rc = is_set ? am355_list_set(ctx, (uint64_t)ctr, actor, actor_len, (uint64_t)start, values, strings, (uint32_t)strings_len, author, author_len, (int64_t)time, message,
+                                   (uint32_t)message_len, &bytes, &len)
+                  : am355_list_splice(ctx, (uint64_t)ctr, actor, actor_len, (uint64_t)start, (uint64_t)deletions, values, (uint32_t)(n_words / vw), strings,
+                                      (uint32_t)strings_len, author, author_len, (int64_t)time, message, (uint32_t)message_len, &bytes, &len);
+  free(values);
+  if (rc) return throw_engine(env, ctx, rc);
+  napi_value ab = copy_to_arraybuffer(env, bytes, len), change;
+  if (!ab) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &change));
+  return change;
+}
+static napi_value js_list_splice(napi_env env, napi_callback_info info) { return list_edit(env, info, false); }
+static napi_value js_list_set(napi_env env, napi_callback_info info) { return list_edit(env, info, true); }
+
 /* rankOfActor(ctx, Uint8Array actor) -> the actor's rank in the engine's table, -1 when the state does not know the actor
  * (am355_rank_of_actor). Ranks are renumbered when a new actor arrives: asked per call. */
 static napi_value js_rank_of_actor(napi_env env, napi_callback_info info) {
@@ -1285,6 +1378,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"objectText", NULL, js_object_text, NULL, NULL, NULL, napi_enumerable, NULL},
       {"textLocate", NULL, js_text_locate, NULL, NULL, NULL, napi_enumerable, NULL},
       {"textSplice", NULL, js_text_splice, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"listLocate", NULL, js_list_locate, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"listSplice", NULL, js_list_splice, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"listSet", NULL, js_list_set, NULL, NULL, NULL, napi_enumerable, NULL},
       {"textPositions", NULL, js_text_positions, NULL, NULL, NULL, napi_enumerable, NULL},
       {"rankOfActor", NULL, js_rank_of_actor, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomBuild", NULL, js_bloom_build, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -12,6 +12,8 @@
 //   applyLocalChange(state, request) -> [state', patch, change]    (backend/backend.js:54-91) for the states applyChanges is served on:
 //                                                                  the change is built on the device (local_change.js, am355_apply_local_change)
 //   positionsOfText(state, objectId, elemIds)   ADDITION: where elements of a Text stand now, deleted ones included (am355_text_position; see below)
+//   spliceList(state, objectId, start, deletions, values, {actor, time, message}) / setListItem(state, objectId, index, value, options) /
+//   locateList(state, objectId, first, n)   ADDITIONS: a plain list edited by position (am355_list_splice / _set / _locate; see below)
 //   spliceText(state, objectId, start, deletions, strings, {actor, time, message}) / locateText(state, objectId, first, n)   ADDITIONS: a
 //     Text edited by position, for hosts without a frontend document (am355_text_splice / am355_text_locate; see below)
 //   getText(state, objectId) / getTextInfo(state, objectId)        ADDITIONS to the reference's surface: the string of a Text object read on
@@ -37,7 +39,7 @@ const LOCAL_SMALL = process.env.MI355X_LOCAL_SMALL !== '0'   // am355_set_local_
 const PATCH_VIA_JSON = process.env.MI355X_PATCH_VIA_JSON === '1'   // A/B: JSON text rendered by the engine + JSON.parse
 const LOCAL_CHANGE = process.env.MI355X_LOCAL_CHANGE !== '0'   // applyLocalChange on the engine (MI355X_LOCAL_CHANGE=0: the reference path, for A/B)
 const { materialize } = require('./materialize.js')
-const { flatten } = require('./local_change.js')
+const { flatten, flattenValues } = require('./local_change.js')
 let addon = null, ctx = null
 // A few engine contexts, used least-recently-used first: a GPU-built state remembers which replay (generation) made it, and as
 // long as that replay still sits in one of the contexts, Backend.save of the state is served from it instead of replaying the
@@ -138,7 +140,7 @@ function contextOf(gen) {
   if (e) { e.used = ++tick; ctx = e.ctx }
   return e || null
 }
-const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, gpuChangesAdded: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0, gpuText: 0, textFallbacks: 0, gpuSplice: 0, spliceFallbacks: 0, gpuPosition: 0, positionFallbacks: 0 }   // (diagnostics: which path served the calls)
+const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, gpuChangesAdded: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0, gpuText: 0, textFallbacks: 0, gpuSplice: 0, spliceFallbacks: 0, gpuListSplice: 0, listSpliceFallbacks: 0, gpuPosition: 0, positionFallbacks: 0 }   // (diagnostics: which path served the calls)
 
 function isFrozenCheck(backend) {
   // reference util.js:1-10
@@ -1031,6 +1033,20 @@ const splitValues = values => (typeof values === 'string' ? [...values] : Array.
 const engineServesText = (backend, m) => !JS_ONLY && spliceOnEngine && m && Number(m[1]) <= 0xffffffff && backend.state instanceof GpuState && !backend.state.js &&
   !heldBack(backend.state) && contextOf(backend.state.generation)
 
+// [backend', patch, binaryChange] of a positional edit the engine has applied to the context `at` (empty change: nothing was to do)
+function positionalResult(backend, at, knownBefore, binaryChange) {
+  if (binaryChange.length === 0) return [backend, null, null]
+  const patch = materialize(addon.fetchApplyIR(ctx, true))
+  const graphFirst = at.docLineage && !knownBefore && !!addon.hashGraphKnown(ctx, -1)
+  const result = stateAfterApply(at, [binaryChange], patch, graphFirst)
+  const own = hexOfHash(result[0].state, result[0].state.hashes.length / 32 - 1)
+  const heads = patch.deps.concat([own]).sort()
+  result[0].state.heads = heads
+  result[0].heads = heads
+  backend.frozen = true
+  return [result[0], patch, binaryChange]
+}
+
 function gpuSpliceText(backend, m, start, deletions, values, actor, time, message) {
   const at = contextForApply(backend)
   if (!at || at.handed) return null
@@ -1046,16 +1062,7 @@ function gpuSpliceText(backend, m, start, deletions, values, actor, time, messag
     if (e.am355Code !== AM355_E_ARG && !(e.am355Code === AM355_E_INVALID && e.message === COUNTER_IN_TEXT)) at.entry.generation = 0
     throw e
   }
-  if (binaryChange.length === 0) return [backend, null, null]
-  const patch = materialize(addon.fetchApplyIR(ctx, true))
-  const graphFirst = at.docLineage && !knownBefore && !!addon.hashGraphKnown(ctx, -1)
-  const result = stateAfterApply(at, [binaryChange], patch, graphFirst)
-  const own = hexOfHash(result[0].state, result[0].state.hashes.length / 32 - 1)
-  const heads = patch.deps.concat([own]).sort()
-  result[0].state.heads = heads
-  result[0].heads = heads
-  backend.frozen = true
-  return [result[0], patch, binaryChange]
+  return positionalResult(backend, at, knownBefore, binaryChange)
 }
 
 function spliceText(backend, objectId, start, deletions, values, options = {}) {
@@ -1111,6 +1118,195 @@ function locateText(backend, objectId, first, n) {
   const elems = elementsFromPatch(getPatch(backend), objectId)
   if (first + n > elems.length) throw new RangeError(`elements [${first}, ${first} + ${n}) are out of bounds for a Text of length ${elems.length}`)
   return { length: elems.length, runs: runsOf(elems.slice(first, first + n)) }
+}
+
+// ---- a plain list edited by position: spliceList / setListItem / locateList (additions; nothing of backend/index.js:1-8 changes) ----
+// spliceList(backend, objectId, start, deletions, values, {actor, time, message}) -> [backend', patch, binaryChange]: one context.splice of
+// the reference's frontend on a list made by makeList (list.deleteAt / list.insertAt), setListItem(backend, objectId, index, value,
+// options): list[index] = value (context.js:411-435; an index at or past the length inserts nulls up to it) -- for a host WITHOUT a
+// frontend document, under the conditions of spliceText and with its ownership of actor and order. An element of a list keeps every
+// conflicting value: a deletion or an assignment names the op ids of all of them as pred (apply_patch.js:156-213, context.js:576-586).
+// A value is a string, a boolean, null, a number (a safe integer is an int, any other a float64, context.js:83-88), a Date (timestamp)
+// or { value, datatype } with datatype 'int', 'uint', 'float64', 'counter' or 'timestamp'. Objects cannot be inserted (TypeError).
+// Several inserted values that all carry the same datatype are one `set` with `values`, else one inserting `set` per value.
+// setListItem ALWAYS makes the op: the reference's frontend skips an assignment of the value the element already shows when there is no
+// conflict; this module holds no frontend values to compare -- on both paths.
+// Served by the engine (am355_list_splice / am355_list_set / am355_list_locate); otherwise, and on AM355_E_UNSUPPORTED, the JS path: the
+// whole-document patch folded into (elemId, preds) per element by the rule of updateListObject, the request built by context.js's rules,
+// this module's own applyLocalChange. Out of bounds: a RangeError with the reference's text; a deleted element that shows a Counter: the
+// TypeError of context.js:471; an assignment onto one: the RangeError of context.js:422 -- on both paths. A list with an element whose
+// first edit is an `update` (the reference's frontend has no elemId for it) is a RangeError on the JS path.
+// locateList(backend, objectId, first, n) -> { length, runs: [{ elemId, preds, count, counter }] }.
+const COUNTER_ASSIGN = 'Cannot overwrite a Counter object; use .increment() or .decrement() to change its value.'
+const LIST_DATATYPES = new Set(['int', 'uint', 'float64', 'counter', 'timestamp'])
+function listValue(v) {   // -> { value, datatype } as an op of the reference's frontend carries them
+  if (v === null || typeof v === 'string' || typeof v === 'boolean') return { value: v, datatype: undefined }
+  if (typeof v === 'number') return { value: v, datatype: Number.isSafeInteger(v) ? 'int' : 'float64' }
+  if (v instanceof Date) return { value: v.getTime(), datatype: 'timestamp' }
+  if (typeof v === 'object' && !Array.isArray(v) && typeof v.value === 'number' && LIST_DATATYPES.has(v.datatype) && Object.keys(v).length === 2) return { value: v.value, datatype: v.datatype }
+  throw new TypeError('a list value is a string, a boolean, null, a number, a Date or { value, datatype }: objects are not inserted by position')
+}
+function listElementsFromPatch(patch, objectId) {
+  let found = null
+  const walk = diff => {
+    if (found) return
+    if (diff.objectId === objectId) { found = diff; return }
+    if (diff.props) for (const key of Object.keys(diff.props)) for (const id of Object.keys(diff.props[key])) if (diff.props[key][id].objectId) walk(diff.props[key][id])
+    if (diff.edits) for (const e of diff.edits) if (e.value && e.value.objectId) walk(e.value)
+  }
+  walk(patch.diffs)
+  if (!found) throw new RangeError(`no such object: ${objectId}`)
+  if (found.type !== 'list') throw new RangeError('not a list object')
+  const elems = [], edits = found.edits
+  for (let i = 0; i < edits.length; i++) {
+    const e = edits[i]
+    if (e.action === 'insert' || e.action === 'update') {
+      const preds = [e.opId]
+      let shown = e.value
+      while (i + 1 < edits.length && edits[i + 1].index === e.index && edits[i + 1].action === 'update') { i++; preds.push(edits[i].opId); shown = edits[i].value }
+      const counter = shown.datatype === 'counter'
+      if (e.action === 'insert') elems.splice(e.index, 0, { elemId: e.elemId, preds, counter })
+      else if (e.index < elems.length) elems[e.index] = { elemId: elems[e.index].elemId, preds, counter }   // (behind a multi-insert: the updates replace the conflicts)
+      else throw new RangeError('a list element whose first edit is an `update`: the frontend has no elemId for it')
+    } else if (e.action === 'multi-insert') {
+      const at = e.elemId.indexOf('@'), ctr = Number(e.elemId.slice(0, at)), actor = e.elemId.slice(at)
+      const made = e.values.map((v, k) => ({ elemId: (ctr + k) + actor, preds: [(ctr + k) + actor], counter: e.datatype === 'counter' }))
+      for (let k = 0; k < made.length; k += 4096) elems.splice(e.index + k, 0, ...made.slice(k, k + 4096))
+    } else throw new RangeError('a list element that shows rows but no value: positions through the patch')
+  }
+  return elems
+}
+function listRunsOf(elems) {
+  const runs = [], parse = id => { const at = id.indexOf('@'); return [Number(id.slice(0, at)), id.slice(at)] }
+  let lastElem = null, lastPred = null
+  for (const el of elems) {
+    const e = parse(el.elemId), p = el.preds.length === 1 ? parse(el.preds[0]) : null, run = runs[runs.length - 1]
+    if (run && lastPred && p && lastElem[1] === e[1] && lastElem[0] + 1 === e[0] && lastPred[1] === p[1] && lastPred[0] + 1 === p[0]) {
+      run.count++
+      run.counter = run.counter || el.counter
+    } else runs.push({ elemId: el.elemId, preds: el.preds.slice(), count: 1, counter: el.counter })
+    lastElem = e; lastPred = p
+  }
+  return runs
+}
+// the ops of context.splice over the folded elements; nextOp: the op number of the first one
+function listSpliceOps(elems, objectId, start, deletions, values, actor, nextOp) {
+  if (start < 0 || deletions < 0 || start > elems.length - deletions) throw outOfBounds(start, deletions, elems.length)
+  const ops = []
+  for (const run of listRunsOf(elems.slice(start, start + deletions))) {
+    if (run.counter) throw new TypeError(COUNTER_IN_TEXT)
+    const op = { action: 'del', obj: objectId, elemId: run.elemId, insert: false, pred: run.preds }
+    if (run.count > 1) op.multiOp = run.count
+    ops.push(op)
+    nextOp += run.count
+  }
+  let elemId = start ? elems[start - 1].elemId : '_head'
+  if (values.length > 1 && values.every(v => v.datatype === values[0].datatype)) {
+    const op = { action: 'set', obj: objectId, elemId, insert: true, values: values.map(v => v.value), pred: [] }
+    if (values[0].datatype) op.datatype = values[0].datatype
+    ops.push(op)
+  } else {
+    for (const v of values) {
+      const op = { action: 'set', obj: objectId, elemId, insert: true, value: v.value, pred: [] }
+      if (v.datatype) op.datatype = v.datatype
+      ops.push(op)
+      elemId = `${nextOp++}@${actor}`
+    }
+  }
+  return ops
+}
+function listCallArgs(name, objectId, options, numbers) {
+  const { actor, time = 0, message = '' } = options
+  if (typeof actor !== 'string' || !/^([0-9a-f]{2})+$/.test(actor)) throw new TypeError(`${name} needs the actor id (lowercase hex) in its options`)
+  if (!numbers.every(Number.isSafeInteger) || !Number.isSafeInteger(time)) throw new TypeError('positions, counts and time are integers')
+  return { actor, time, message, m: typeof objectId === 'string' ? OBJECT_ID.exec(objectId) : null }
+}
+// one list call on the engine: call(at, idBytes...) -> the binary change; null when the engine does not serve the state
+function gpuListEdit(backend, flat, call) {
+  const at = contextForApply(backend)
+  if (!at || at.handed || !flat) return null
+  const knownBefore = at.docLineage ? !!addon.hashGraphKnown(ctx, -1) : true
+  let binaryChange
+  try {
+    binaryChange = call(flat)
+  } catch (e) {
+    // out of bounds, no such list, a counter: decided before the state is touched (am355.h); anything else may have dropped it
+    if (e.am355Code !== AM355_E_ARG && !(e.am355Code === AM355_E_INVALID && (e.message === COUNTER_IN_TEXT || e.message === COUNTER_ASSIGN))) at.entry.generation = 0
+    throw e
+  }
+  return positionalResult(backend, at, knownBefore, binaryChange)
+}
+function listOnEngine(backend, m, flat, call) {
+  if (!engineServesText(backend, m)) return null
+  try {
+    const result = gpuListEdit(backend, flat, call)
+    if (result) counters.gpuListSplice++
+    return result
+  } catch (e) {
+    if (e.am355Code === AM355_E_ARG) throw new RangeError(e.message)
+    if (e.am355Code === AM355_E_INVALID && e.message === COUNTER_IN_TEXT) throw new TypeError(e.message)
+    if (e.am355Code === AM355_E_INVALID && e.message === COUNTER_ASSIGN) throw new RangeError(e.message)
+    if (e.am355Code !== AM355_E_INVALID && e.am355Code !== AM355_E_UNSUPPORTED) throw e
+    return null
+  }
+}
+const hexBytes = hex => new Uint8Array(Buffer.from(hex, 'hex'))
+
+function spliceList(backend, objectId, start, deletions, values, options = {}) {
+  isFrozenCheck(backend)
+  if (!Array.isArray(values) && values !== undefined && values !== null) throw new TypeError('spliceList inserts an array of values')
+  const list = (values || []).map(listValue)
+  const { actor, time, message, m } = listCallArgs('spliceList', objectId, options, [start, deletions])
+  if (start >= 0 && deletions >= 0) {
+    const served = listOnEngine(backend, m, flattenValues(list), flat => addon.listSplice(ctx, Number(m[1]), hexBytes(m[2]), start, deletions, flat.values, flat.strings,
+      hexBytes(actor), time, new Uint8Array(Buffer.from(message, 'utf8'))))
+    if (served) return served
+  }
+  counters.listSpliceFallbacks++
+  const whole = getPatch(backend), elems = listElementsFromPatch(whole, objectId)
+  const ops = listSpliceOps(elems, objectId, start, deletions, list, actor, whole.maxOp + 1)
+  if (ops.length === 0) return [backend, null, null]
+  // (the deps are the state's heads; applyLocalChange adds the actor's last hash and keeps every hash once, backend.js:73-81)
+  return applyLocalChange(backend, { actor, seq: (whole.clock[actor] || 0) + 1, startOp: whole.maxOp + 1, deps: whole.deps.slice(), time, message, ops })
+}
+
+function setListItem(backend, objectId, index, value, options = {}) {
+  isFrozenCheck(backend)
+  const v = listValue(value)
+  const { actor, time, message, m } = listCallArgs('setListItem', objectId, options, [index])
+  if (index < 0) throw new RangeError(`A list index must be positive, but you passed ${index}`)
+  const served = listOnEngine(backend, m, flattenValues([v]), flat => addon.listSet(ctx, Number(m[1]), hexBytes(m[2]), index, flat.values, flat.strings, hexBytes(actor), time,
+    new Uint8Array(Buffer.from(message, 'utf8'))))
+  if (served) return served
+  counters.listSpliceFallbacks++
+  const whole = getPatch(backend), elems = listElementsFromPatch(whole, objectId)
+  let ops
+  if (index >= elems.length) {   // context.js:416-420
+    ops = listSpliceOps(elems, objectId, elems.length, 0, Array(index - elems.length).fill({ value: null, datatype: undefined }).concat([v]), actor, whole.maxOp + 1)
+  } else {
+    if (elems[index].counter) throw new RangeError(COUNTER_ASSIGN)
+    const op = { action: 'set', obj: objectId, elemId: elems[index].elemId, insert: false, value: v.value, pred: elems[index].preds }
+    if (v.datatype) op.datatype = v.datatype
+    ops = [op]
+  }
+  return applyLocalChange(backend, { actor, seq: (whole.clock[actor] || 0) + 1, startOp: whole.maxOp + 1, deps: whole.deps.slice(), time, message, ops })
+}
+
+function locateList(backend, objectId, first, n) {
+  isFrozenCheck(backend)
+  if (!Number.isSafeInteger(first) || !Number.isSafeInteger(n) || first < 0 || n < 0) throw new RangeError('first and n are non-negative integers')
+  const m = typeof objectId === 'string' ? OBJECT_ID.exec(objectId) : null
+  if (engineServesText(backend, m)) {
+    try {
+      return addon.listLocate(ctx, Number(m[1]), hexBytes(m[2]), first, n)
+    } catch (e) {
+      if (e.am355Code === AM355_E_ARG) throw new RangeError(e.message)
+      if (e.am355Code === undefined) throw e
+    }
+  }
+  const elems = listElementsFromPatch(getPatch(backend), objectId)
+  if (first + n > elems.length) throw new RangeError(`elements [${first}, ${first} + ${n}) are out of bounds for a list of length ${elems.length}`)
+  return { length: elems.length, runs: listRunsOf(elems.slice(first, first + n)) }
 }
 
 // ---- elemIds of a Text resolved to positions: positionsOfText (an addition; nothing of backend/index.js:1-8 changes) ----
@@ -1228,6 +1424,8 @@ module.exports = {
   getText, getTextInfo,
   // additions: a Text edited by position / positions resolved to ids, on the device (see above)
   spliceText, locateText,
+  // additions: a plain list edited by position / positions resolved to ids and every pred, on the device (see above)
+  spliceList, setListItem, locateList,
   // addition: elemIds of a Text resolved to positions, deleted elements included, on the device (see above)
   positionsOfText,
   // sync protocol: the reference's own backend/sync.js bound to this module (boundSync above)

@@ -30,6 +30,50 @@ function opId(s) {
 
 const f64 = new Float64Array(1), f64words = new Uint32Array(f64.buffer)
 
+// one value as the six words of am355_local_value (tag, off, len, pad, payload low, payload high); putString(s) -> [off, len] of the arena
+function valueWords(v, datatype, multi, putString) {
+  let tag = LV.BAD, off = 0, len = 0, lo = 0, hi = 0
+  const isNum = typeof v === 'number'
+  if (typeof datatype === 'number') throw new NotFlat('numeric datatype')
+  const integer = x => { const big = BigInt.asUintN(64, BigInt(x)); lo = Number(big & 0xffffffffn); hi = Number(big >> 32n) }
+  if (multi && (datatype === undefined) === isNum) {
+    // (validDatatype, columnar.js:438-444: the reference throws)
+  } else if (v === null) tag = LV.NULL
+  else if (v === false || v === true) tag = v ? LV.TRUE : LV.FALSE
+  else if (typeof v === 'string') { tag = LV.UTF8; [off, len] = putString(v) }
+  else if (ArrayBuffer.isView(v)) tag = LV.BYTES
+  else if (isNum) {
+    const named = NAMED.get(datatype)
+    if (named !== undefined) {
+      if (Number.isSafeInteger(v) && (datatype !== 'uint' || v >= 0)) { tag = named; integer(v) }
+    } else if (datatype !== 'float64' && Number.isSafeInteger(v)) { tag = LV.INT; integer(v) }
+    else { tag = LV.FLOAT64; f64[0] = v; lo = f64words[0]; hi = f64words[1] }
+  } else throw new NotFlat('value that is no primitive')
+  return [tag, off, len, 0, lo, hi]
+}
+
+// [{ value, datatype }] as the values and the string arena of am355_list_splice / am355_list_set; null: a value the flat form cannot express
+function flattenValues(list) {
+  const chunks = [], words = []
+  let stringsLen = 0
+  const putString = s => {
+    const b = Buffer.from(s, 'utf8')
+    if (b.toString('utf8') !== s) throw new NotFlat('lone surrogate')
+    const off = stringsLen
+    chunks.push(b)
+    stringsLen += b.length
+    return [off, b.length]
+  }
+  try {
+    for (const { value, datatype } of list) words.push(...valueWords(value, datatype, false, putString))
+  } catch (e) {
+    if (!(e instanceof NotFlat)) throw e
+    return null
+  }
+  const strings = Buffer.concat(chunks, stringsLen)
+  return { values: Uint32Array.from(words), strings: new Uint8Array(strings.buffer, strings.byteOffset, strings.length) }
+}
+
 function flatten(request) {
   try {
     if (request === null || typeof request !== 'object' || !Array.isArray(request.ops) || !Array.isArray(request.deps)) throw new NotFlat('request')
@@ -50,26 +94,7 @@ function flatten(request) {
     }
     const ops = new Uint32Array(OP_WORDS * request.ops.length)
     const values = [], preds = [], parsed = []
-    const putValue = (v, datatype, multi) => {
-      let tag = LV.BAD, off = 0, len = 0, lo = 0, hi = 0
-      const isNum = typeof v === 'number'
-      if (typeof datatype === 'number') throw new NotFlat('numeric datatype')
-      const integer = x => { const big = BigInt.asUintN(64, BigInt(x)); lo = Number(big & 0xffffffffn); hi = Number(big >> 32n) }
-      if (multi && (datatype === undefined) === isNum) {
-        // (validDatatype, columnar.js:438-444: the reference throws)
-      } else if (v === null) tag = LV.NULL
-      else if (v === false || v === true) tag = v ? LV.TRUE : LV.FALSE
-      else if (typeof v === 'string') { tag = LV.UTF8; [off, len] = putString(v) }
-      else if (ArrayBuffer.isView(v)) tag = LV.BYTES
-      else if (isNum) {
-        const named = NAMED.get(datatype)
-        if (named !== undefined) {
-          if (Number.isSafeInteger(v) && (datatype !== 'uint' || v >= 0)) { tag = named; integer(v) }
-        } else if (datatype !== 'float64' && Number.isSafeInteger(v)) { tag = LV.INT; integer(v) }
-        else { tag = LV.FLOAT64; f64[0] = v; lo = f64words[0]; hi = f64words[1] }
-      } else throw new NotFlat('value that is no primitive')
-      values.push(tag, off, len, 0, lo, hi)
-    }
+    const putValue = (v, datatype, multi) => { values.push(...valueWords(v, datatype, multi, putString)) }
     request.ops.forEach((op, i) => {
       if (op === null || typeof op !== 'object') throw new NotFlat('op')
       const action = ACTIONS.indexOf(op.action)
@@ -136,4 +161,4 @@ function flatten(request) {
   }
 }
 
-module.exports = { flatten }
+module.exports = { flatten, flattenValues }

@@ -658,6 +658,66 @@ int am355_text_locate_limits(uint32_t out[3]);                        /* the siz
 int am355_actor_of_rank(const am355_ctx *ctx, uint32_t rank, const uint8_t **bytes, size_t *len);
 
 /*
+ * A plain LIST edited by POSITION (csrc/am355_list_locate.hip): what am355_text_locate / am355_text_splice are for a Text, for an object
+ * made by makeList (type 2) -- doc.cards.deleteAt(3), doc.cards.insertAt(0, 7, 8, 9), doc.cards[2] = 'x' for a host without a frontend
+ * document. The difference to a Text: an element of a list keeps EVERY conflicting value (frontend/apply_patch.js:156-213
+ * updateListObject), and the pred of a deletion or an assignment names the op ids of all of them (context.js:576-586 getPred).
+ * am355_list_locate resolves the elements [first, first + n) to runs: run = `count` elements whose elemIds are (elem_ctr + i, elem_actor).
+ * A run of count > 1 has pred_num == 1 and element i's pred is ((*preds)[pred_first].ctr + i, .actor); a run of count == 1 has the
+ * pred_num >= 1 preds (*preds)[pred_first .. pred_first + pred_num), in ascending op id (counter, then actor bytes) -- the order
+ * am355_local_op wants. Runs are the deletions context.splice merges into `multiOp` (context.js:479-486: both elements have exactly one
+ * pred, elemIds and preds of equal actors and consecutive counters); an element of several values is always a run of its own. Actors are
+ * ranks, as in am355_patch_ir. (The reference's own exception is reproduced: `update` edits behind a `multi-insert` edit replace the
+ * element's conflicts in its frontend, apply_patch.js:187-190, so the inserted value's id is not among the preds then; only a hand-made
+ * `set` without pred onto an existing element makes such a history.) flags & AM355_RUN_COUNTER: the value the list SHOWS for some element of the run (the last one) is a Counter.
+ * *runs / *preds are pinned memory owned by the context, valid until the next call on ctx; *length = list.length; n == 0 is legal and
+ * returns the length. It reads only, as am355_text_locate does, with its contexts and errors (AM355_E_STATE, sharded
+ * AM355_E_UNSUPPORTED, AM355_E_ARG "no such object: ..." / "not a list object" for anything but a plain list, first + n > length:
+ * AM355_E_ARG, a `remove` record: AM355_E_UNSUPPORTED, records that contradict each other: AM355_E_DEVICE), and two of its own, both
+ * AM355_E_UNSUPPORTED: an element whose first edit is an `update` (it was reported as `remove` first; the reference's frontend has no
+ * elemId for it), and an element of more than 4096 values (the bound am355_apply_local_change has for the preds of one op).
+ *
+ * am355_list_splice: one context.splice(path, start, deletions, insertions) (context.js:441-502) on the list the context holds. It locates
+ * [start - 1, start + deletions) in one query and builds the request of the frontend: one `del` per run of the deleted elements (multiOp =
+ * count, pred = all preds), then insertListItems (context.js:370-405) behind element start - 1 (`_head` for start == 0): several values
+ * that all carry the same datatype are ONE `set` with `values` (strings, booleans and null carry none and are one class; AM355_LV_INT,
+ * _UINT, _FLOAT64, _COUNTER and _TIMESTAMP are each their own), otherwise one inserting `set` per value, each naming the element the op
+ * before it made. Values are am355_local_value, as for am355_apply_local_change (AM355_LV_UTF8: a range of `strings`; AM355_LV_BYTES stays
+ * refused there). seq, startOp, deps and the application are those of am355_text_splice. Decided before the state is touched (a document
+ * context is at most turned into the state of its rebuilt changes): start > length - deletions: AM355_E_ARG with the reference's
+ * RangeError text ("<deletions> deletions starting at index <start> are out of bounds for list of length <length>"); a deleted element
+ * that shows a Counter: AM355_E_INVALID with its TypeError text ("Unsupported operation: deleting a counter from a list"; for a list the
+ * reference really throws); deletions == 0 && n_values == 0: AM355_OK, *len = 0, nothing applied; the errors of am355_list_locate; queued
+ * changes in the state: AM355_E_UNSUPPORTED. Inserting objects is not served: `child` ops are not in the flat request form.
+ *
+ * am355_list_set: list[index] = value (context.js:411-435 setListIndex). index >= length: a splice at `length` of index - length nulls
+ * followed by the value (at most 2^20 nulls; more: AM355_E_UNSUPPORTED). Otherwise one `set`, insert: false, with the element's elemId and
+ * pred = all its preds; onto an element that shows a Counter: AM355_E_INVALID with the reference's RangeError text ("Cannot overwrite a
+ * Counter object; use .increment() or .decrement() to change its value."). THE CALL ALWAYS EMITS THE OP: the reference skips it when the
+ * new value === the shown one and the element has at most one value; the engine holds no JS values, so a caller that wants that
+ * economy compares before it calls.
+ * am355_list_splice_calls: out[0] calls of am355_list_splice and am355_list_set served, out[1] refused (whatever the code), out[2] kernel
+ * launches of the locate half of the three calls. am355_list_locate_limits: out[0] = elements one workgroup of the locate kernel takes,
+ * out[1] = elements up to which the scan is one workgroup, out[2] = runs, and preds, written straight into pinned memory (the ones behind
+ * go to device memory and down in one copy each).
+ * Not built: am355_text_position for lists, increments, a locate without the rebuild of stale edit tables.
+ */
+typedef struct { uint32_t elem_ctr, elem_actor, count, flags, pred_first, pred_num; } am355_list_run;   /* flags: AM355_RUN_COUNTER; actors: ranks */
+typedef struct { uint32_t actor, ctr; } am355_list_pred;                                               /* actor: a rank */
+int am355_list_locate(am355_ctx *ctx, uint64_t obj_ctr, const uint8_t *obj_actor, size_t actor_len, uint64_t first, uint64_t n,
+                      const am355_list_run **runs, uint32_t *n_runs, const am355_list_pred **preds, uint32_t *n_preds, uint64_t *length);
+int am355_list_splice(am355_ctx *ctx, uint64_t obj_ctr, const uint8_t *obj_actor, size_t actor_len, uint64_t start, uint64_t deletions,
+                      const am355_local_value *values, uint32_t n_values, const uint8_t *strings, uint32_t strings_len,
+                      const uint8_t *author, size_t author_len, int64_t time, const uint8_t *message, uint32_t message_len,
+                      const uint8_t **change, size_t *len);
+int am355_list_set(am355_ctx *ctx, uint64_t obj_ctr, const uint8_t *obj_actor, size_t actor_len, uint64_t index,
+                   const am355_local_value *value, const uint8_t *strings, uint32_t strings_len,
+                   const uint8_t *author, size_t author_len, int64_t time, const uint8_t *message, uint32_t message_len,
+                   const uint8_t **change, size_t *len);
+int am355_list_splice_calls(const am355_ctx *ctx, uint64_t out[3]);   /* served | refused | device launches of the locate half */
+int am355_list_locate_limits(uint32_t out[3]);                        /* the sizes at which the kernels switch path, for the tests */
+
+/*
  * ElemIds of a Text resolved to POSITIONS (csrc/am355_position.hip): the inverse of am355_text_locate, and what keeps a caret, a
  * selection or a comment anchor alive while remote changes arrive -- the only stable name for a place in an RGA text is an elemId.
  * Query i is the element (ids[i].ctr, ids[i].actor) of the Text obj_ctr @ obj_actor; answer (*out)[i] is
@@ -744,6 +804,10 @@ int am355_test_carried_scan(am355_ctx *ctx, const uint32_t *v, uint32_t n, uint3
  * continue each other or name values outside the table, 2 = a `remove` record. *length: in, what the length word holds before the
  * pass; out, what it holds behind it -- the object's length when flags == 0, else as it was. */
 int am355_test_text_premises(am355_ctx *ctx, const am355_ir_edit *table, uint32_t n_recs, uint32_t begin, uint32_t R, uint32_t n_values, uint32_t *flags, uint32_t *length);
+/* The check pass of the calls on a plain list (am355_list_locate, am355_list_splice, am355_list_set) over a hand-made record table: as
+ * am355_test_text_premises, with the bit of the list calls beside the two premises -- 8 = an element whose first record carries
+ * AM355_EDIT_UPDATE. */
+int am355_test_list_premises(am355_ctx *ctx, const am355_ir_edit *table, uint32_t n_recs, uint32_t begin, uint32_t R, uint32_t n_values, uint32_t *flags, uint32_t *length);
 /* decoded op rows of the last replay, copied to caller arrays of length n_ops (any pointer may be NULL) */
 int am355_get_rows(am355_ctx *ctx, uint32_t *obj_actor, uint32_t *obj_ctr, uint32_t *key_actor, uint32_t *key_ctr, uint32_t *key_off,
                    uint32_t *key_len, uint32_t *action, uint32_t *val_tl, uint32_t *val_off, uint32_t *pred_num, uint32_t *id_ctr,
