@@ -1003,3 +1003,8 @@ int sync_bloom_impl(am355_ctx* c, const uint32_t* idx, uint32_t n, uint32_t num_
 // am355_list_set): likewise
 // ---------------------------------------------------------------------------------------------------------
 #include "am355_list_locate.hip"
+
+// ---------------------------------------------------------------------------------------------------------
+// keys of a map resolved to the op ids of their visible values, and the edit by key (am355_map_locate, am355_map_update): likewise
+// ---------------------------------------------------------------------------------------------------------
+#include "am355_map_locate.hip"

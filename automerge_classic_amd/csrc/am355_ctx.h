@@ -620,6 +620,11 @@ struct am355_ctx {
   DevBuf d_posq;                                   // result words | rec_pos | the queries and the results behind LOCATE_PINNED_RUNS
   HostBuf h_pos_out, h_pos_ids;                    // pinned: the results (valid until the next call) | the queries
   uint64_t n_position_served = 0, n_position_launches = 0;   // am355_text_position_calls
+  // am355_map_locate / am355_map_update (am355_map_locate.hip): keys of a map resolved to the records of their visible values
+  DevBuf d_mloc, d_mloc_hits, d_mloc_recs;         // result words | per-key words | the keys when they are copied up | scan workspace; the hits and the records behind LOCATE_PINNED_RUNS
+  HostBuf h_mloc_hits, h_mloc_recs, h_mloc_keys;   // pinned: the hits and the gathered records (valid until the next call) | the queried keys: offsets, then bytes
+  bool map_locate_thread = false;                  // am355_set_map_locate_thread: one thread per key instead of one wavefront (measurement)
+  uint64_t n_map_served = 0, n_map_refused = 0, n_map_launches = 0;   // am355_map_calls
   DevBuf d_map_alt, d_mapmerge;                    // the other map table | the stage's scratch
   am355_ir_map* map_alt_ptr = nullptr;             // whichever of the two map tables c->ir.map does NOT point to (null: not set up since the last carve)
   std::string resident_why;                        // why the last attempt fell back (diagnostics, AM355_TRACE)

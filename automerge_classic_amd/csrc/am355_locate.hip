@@ -200,27 +200,31 @@ struct SpliceActors {
 };
 
 // The request of a positional edit completed and applied: seq = the author's clock entry + 1, startOp = maxOp + 1, deps = the heads
-// without the author's last change, which am355_apply_local_change adds itself (backend.js:73-81, 88-89).
+// without the author's last change, which am355_apply_local_change adds itself (backend.js:73-81, 88-89). onto_nothing: seq 1, startOp 1, no deps.
 int splice_apply(am355_ctx* c, const SpliceActors& act, const uint8_t* author, size_t author_len, int64_t time, const uint8_t* message, uint32_t message_len,
                  const uint8_t* strings, uint32_t strings_len, const std::vector<am355_local_op>& ops, const std::vector<am355_local_value>& values,
-                 const std::vector<am355_local_pred>& preds, const uint8_t** change, size_t* len) {
+                 const std::vector<am355_local_pred>& preds, const uint8_t** change, size_t* len, bool onto_nothing = false) {
   am355_local_change lc{};
   lc.seq = 1;
-  uint32_t rank = 0;
-  if (actor_rank_of(c, author, author_len, &rank))
-    for (size_t k = 0; k < c->clock_actor.size(); k++)
-      if (c->clock_actor[k] == rank) lc.seq = c->clock_seq[k] + 1;
-  lc.start_op = c->max_op + 1;
+  lc.start_op = 1;
   lc.time = time;
   lc.message = message; lc.message_len = message_len;
-  std::vector<uint8_t> deps(c->heads);
-  uint32_t last = NONE32;
-  int rc;
-  if (lc.seq > 1 && c->h_hashes.p && (rc = staged_change_of(c, author, author_len, lc.seq - 1, &last))) return rc;
-  if (last != NONE32) {
-    const uint8_t* h = c->h_hashes.as<uint8_t>() + 32 * (size_t)last;
-    for (size_t k = 0; k + 32 <= deps.size(); k += 32)
-      if (memcmp(&deps[k], h, 32) == 0) { deps.erase(deps.begin() + k, deps.begin() + k + 32); break; }
+  std::vector<uint8_t> deps;
+  if (!onto_nothing) {   // (a context without a state is Backend.init(): no clock, no heads, maxOp 0)
+    uint32_t rank = 0;
+    if (actor_rank_of(c, author, author_len, &rank))
+      for (size_t k = 0; k < c->clock_actor.size(); k++)
+        if (c->clock_actor[k] == rank) lc.seq = c->clock_seq[k] + 1;
+    lc.start_op = c->max_op + 1;
+    deps = c->heads;
+    uint32_t last = NONE32;
+    int rc;
+    if (lc.seq > 1 && c->h_hashes.p && (rc = staged_change_of(c, author, author_len, lc.seq - 1, &last))) return rc;
+    if (last != NONE32) {
+      const uint8_t* h = c->h_hashes.as<uint8_t>() + 32 * (size_t)last;
+      for (size_t k = 0; k + 32 <= deps.size(); k += 32)
+        if (memcmp(&deps[k], h, 32) == 0) { deps.erase(deps.begin() + k, deps.begin() + k + 32); break; }
+    }
   }
   lc.deps = deps.data(); lc.n_deps = (uint32_t)(deps.size() / 32);
   lc.n_actors = (uint32_t)act.table.size(); lc.actor_off = act.off.data(); lc.actor_bytes = act.bytes.data(); lc.actor_rank = act.rank.data();

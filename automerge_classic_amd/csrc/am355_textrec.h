@@ -112,15 +112,15 @@ void launch_list_check(const TextRecs& t, uint32_t* words, hipStream_t st);
 
 // device words of the lookup and of a read (d_text): what kt_find found, then the totals and the flag word of kt_sizes
 enum TextWord { TW_INDEX = 0, TW_TYPE = 1, TW_BEGIN = 2, TW_END = 3, TW_BYTES = 4, TW_ELEMS = 5, TW_NONSTR = 6, TW_FLAGS = 7, TW_WORDS = 8 };
-// One thread per object: the object with that id leaves its index, type and edit range. (_root, index 0, has no id.)
-static __global__ __launch_bounds__(BLOCK) void kt_find(const am355_ir_object* __restrict__ obj, uint32_t n_obj, uint32_t ctr, uint32_t actor, uint32_t* __restrict__ words) {
+// One thread per object: the object with that id leaves its index, type and edit range -- or, maps != 0, its range of map records. (_root, index 0, has no id.)
+static __global__ __launch_bounds__(BLOCK) void kt_find(const am355_ir_object* __restrict__ obj, uint32_t n_obj, uint32_t ctr, uint32_t actor, uint32_t maps, uint32_t* __restrict__ words) {
   const uint32_t i = gtid();
   if (i == 0 || i >= n_obj) return;
   if (obj[i].id_ctr != ctr || obj[i].id_actor != actor) return;
   words[TW_INDEX] = i;
   words[TW_TYPE] = obj[i].type;
-  words[TW_BEGIN] = obj[i].edit_begin;
-  words[TW_END] = obj[i].edit_end;
+  words[TW_BEGIN] = maps ? obj[i].map_begin : obj[i].edit_begin;
+  words[TW_END] = maps ? obj[i].map_end : obj[i].edit_end;
 }
 
 }  // namespace am355
@@ -156,10 +156,9 @@ static inline int text_premise_error(am355_ctx* c, TextCall call, uint32_t flags
 enum TextOpenFlag : uint32_t { TO_CHANGE_STATE = 1,   // a document context becomes the state of its rebuilt changes first (as am355_apply_local_change)
                                TO_NO_QUEUE = 2 };     // refused on a state with queued changes
 struct TextObject { uint32_t index, actor_rank; TextRecs recs; };   // index in the object table | rank of the id's actor | its records
-// The opening of a call `who` on the Text (or, want_type 2, the plain list) (obj_ctr, obj_actor): the state it needs, the edit tables fresh, the object found -- from the host's copy
-// of the object table when it is the device's, else one launch over ir.obj (+ the launch that signals the four words; counted in *launches).
-static inline int text_open(am355_ctx* c, const char* who, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint32_t flags, uint64_t* launches, TextObject& o,
-                            uint32_t want_type = 4) {   // (4: a Text; 2: a plain list)
+// The state a call `who` on an object needs (shared by the calls on a Text, a plain list and a map): replayed, not sharded, a document
+// context turned into the state of its rebuilt changes and no queued changes where the flags ask for it.
+static inline int call_open_state(am355_ctx* c, const char* who, uint32_t flags) {
   if (!c->replayed) return fail(c, AM355_E_STATE, "%s: a replayed state is needed", who);
   if (c->shard_world > 1) return fail(c, AM355_E_UNSUPPORTED, "%s on a sharded context", who);
   (void)hipSetDevice(c->device);
@@ -169,39 +168,57 @@ static inline int text_open(am355_ctx* c, const char* who, uint64_t obj_ctr, con
     if (!c->replayed) return fail(c, AM355_E_STATE, "%s: a replayed state is needed", who);
   }
   if ((flags & TO_NO_QUEUE) && (!c->pending_change.empty() || c->n_pending)) return fail(c, AM355_E_UNSUPPORTED, "local change onto a state with queued changes: JS path");
-  { int frc = ensure_ir_fresh(c); if (frc) return frc; }   // (in-place list merges leave the edit tables stale: rebuilt once)
+  return AM355_OK;
+}
+// The object (obj_ctr, obj_actor), not _root: its index, the rank of its actor, its type and its range of edit records (maps: of map
+// records) -- from the host's copy of the object table when it is the device's, else one launch over ir.obj (+ the launch that signals the
+// four words; counted in *launches). No such object: AM355_E_ARG "no such object: <ctr>@<actor in hex>".
+struct FoundObject { uint32_t index, actor_rank, type, begin, end; };
+static inline int object_lookup(am355_ctx* c, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, bool maps, uint64_t* launches, FoundObject& f) {
   hipStream_t st = c->stream;
-  const uint32_t NO = c->counts.n_objects, NR = c->counts.n_erecs;
-  auto no_such = [&]() {   // "no such object: <ctr>@<actor in hex>"
+  const uint32_t NO = c->counts.n_objects;
+  auto no_such = [&]() {
     std::string id = std::to_string((unsigned long long)obj_ctr) + "@";
     for (size_t k = 0; k < actor_len; k++) { id.push_back("0123456789abcdef"[obj_actor[k] >> 4]); id.push_back("0123456789abcdef"[obj_actor[k] & 15]); }
     return fail(c, AM355_E_ARG, "no such object: %s", id.c_str());
   };
-  const char* not_wanted = want_type == 4 ? "not a Text object" : "not a list object";
-  if (obj_ctr == 0 && actor_len == 0) return fail(c, AM355_E_ARG, "%s", not_wanted);   // (_root: a map)
   uint32_t rank = 0;
   if (obj_ctr > 0xffffffffull || !actor_rank_of(c, obj_actor, actor_len, &rank)) return no_such();
   if (!c->d_text.ensure(TW_WORDS * 4) || !c->text_sig.ready()) return fail(c, AM355_E_NOMEM, "allocation failed (text)");
-  uint32_t oi = NONE32, type = 0, eb = 0, ee = 0;
+  uint32_t oi = NONE32, type = 0, b = 0, e = 0;
   if (c->h_tables_current && c->hir.objects && c->hir.n_objects == NO) {
     for (uint32_t i = 1; i < NO; i++)
       if (c->hir.objects[i].id_ctr == (uint32_t)obj_ctr && c->hir.objects[i].id_actor == rank) {
-        oi = i; type = c->hir.objects[i].type; eb = c->hir.objects[i].edit_begin; ee = c->hir.objects[i].edit_end;
+        const am355_ir_object& ho = c->hir.objects[i];
+        oi = i; type = ho.type; b = maps ? ho.map_begin : ho.edit_begin; e = maps ? ho.map_end : ho.edit_end;
         break;
       }
   } else if (NO > 1) {
     uint32_t* dw = c->d_text.as<uint32_t>();
     HIPCHK(c, hipMemsetAsync(dw, 0xff, 4 * 4, st));
-    AM355_LAUNCH_INDEPENDENT(kt_find, dim3((NO + BLOCK - 1) / BLOCK), dim3(BLOCK), st, (const am355_ir_object*)c->ir.obj, NO, (uint32_t)obj_ctr, rank, dw);
+    AM355_LAUNCH_INDEPENDENT(kt_find, dim3((NO + BLOCK - 1) / BLOCK), dim3(BLOCK), st, (const am355_ir_object*)c->ir.obj, NO, (uint32_t)obj_ctr, rank, maps ? 1u : 0u, dw);
     *launches += 2;
     HIPCHK(c, c->text_sig.fetch(dw, 4, 0, st));
     const uint32_t* hw = c->text_sig.words();
-    oi = hw[TW_INDEX]; type = hw[TW_TYPE]; eb = hw[TW_BEGIN]; ee = hw[TW_END];
+    oi = hw[TW_INDEX]; type = hw[TW_TYPE]; b = hw[TW_BEGIN]; e = hw[TW_END];
   }
   if (oi == NONE32) return no_such();
-  if (type != want_type) return fail(c, AM355_E_ARG, "%s", not_wanted);
-  if (eb > ee || ee > NR) return fail(c, AM355_E_DEVICE, "internal: edit range [%u, %u) of object %u outside the %u records", eb, ee, oi, NR);
-  o.index = oi; o.actor_rank = rank;
-  o.recs = TextRecs{(const am355_ir_edit*)c->ir.edit, eb, ee - eb, c->counts.n_edits};
+  f = FoundObject{oi, rank, type, b, e};
+  return AM355_OK;
+}
+// The opening of a call `who` on the Text (or, want_type 2, the plain list) (obj_ctr, obj_actor): the state it needs, the edit tables fresh, the object found.
+static inline int text_open(am355_ctx* c, const char* who, uint64_t obj_ctr, const uint8_t* obj_actor, size_t actor_len, uint32_t flags, uint64_t* launches, TextObject& o,
+                            uint32_t want_type = 4) {   // (4: a Text; 2: a plain list)
+  { int src = call_open_state(c, who, flags); if (src) return src; }
+  { int frc = ensure_ir_fresh(c); if (frc) return frc; }   // (in-place list merges leave the edit tables stale: rebuilt once)
+  const uint32_t NR = c->counts.n_erecs;
+  const char* not_wanted = want_type == 4 ? "not a Text object" : "not a list object";
+  if (obj_ctr == 0 && actor_len == 0) return fail(c, AM355_E_ARG, "%s", not_wanted);   // (_root: a map)
+  FoundObject f;
+  { int lrc = object_lookup(c, obj_ctr, obj_actor, actor_len, false, launches, f); if (lrc) return lrc; }
+  if (f.type != want_type) return fail(c, AM355_E_ARG, "%s", not_wanted);
+  if (f.begin > f.end || f.end > NR) return fail(c, AM355_E_DEVICE, "internal: edit range [%u, %u) of object %u outside the %u records", f.begin, f.end, f.index, NR);
+  o.index = f.index; o.actor_rank = f.actor_rank;
+  o.recs = TextRecs{(const am355_ir_edit*)c->ir.edit, f.begin, f.end - f.begin, c->counts.n_edits};
   return AM355_OK;
 }

@@ -54,6 +54,34 @@ ELEM_POS_DTYPE = np.dtype([("position", "<u4"), ("status", "<u4")])       # am35
 POS_UNKNOWN, POS_VISIBLE, POS_DELETED, POS_COUNTER = 0, 1, 2, 0x100       # AM355_POS_*
 IR_EDIT_DTYPE = np.dtype([(n, "<u4") for n in ("flags", "index", "id_ctr", "id_actor", "elem_ctr", "elem_actor", "first", "val_tl", "val_off", "pad")])   # am355_ir_edit
 EDIT_UPDATE, EDIT_REMOVE = 1, 8                                           # AM355_EDIT_*
+IR_MAP_DTYPE = np.dtype([("id_ctr", "<u4"), ("id_actor", "<u4"), ("key_off", "<u4"), ("key_len", "<u4"), ("val_tl", "<u4"), ("val_off", "<u4"), ("flags", "<u4"), ("pad", "<u4"),
+                         ("counter", "<i8")])                             # am355_ir_map
+MAP_HIT_DTYPE = np.dtype([("first", "<u4"), ("num", "<u4"), ("flags", "<u4"), ("pad", "<u4")])   # am355_map_hit
+MAP_OP_DTYPE = np.dtype([("kind", "<u4"), ("key_off", "<u4"), ("key_len", "<u4"), ("value", "<u4"), ("delta", "<i8")])   # am355_map_op
+MAP_COUNTER, MAP_CHILD, MAP_EMPTY = 1, 2, 4                               # AM355_MAP_*
+MOP_SET, MOP_DELETE, MOP_INC = 1, 2, 3                                    # AM355_MOP_*
+
+
+def decode_ir_value(val_tl, raw):
+    """A primitive value of the record tables (type/length word as in the valLen column, columnar.js:300-329; `raw`: its bytes) as
+    (value, datatype): what the reference's patch carries as {value, datatype}."""
+    tag = val_tl & 15
+    if tag <= 2:
+        return (None, False, True)[tag], None
+    if tag in (3, 4, 8, 9):
+        v, shift = 0, 0
+        for b in raw:
+            v |= (b & 0x7F) << shift
+            shift += 7
+        if tag != 3 and raw and raw[-1] & 0x40:
+            v -= 1 << shift
+        return v, {3: "uint", 4: "int", 8: "counter", 9: "timestamp"}[tag]
+    if tag == 5:
+        return float(np.frombuffer(bytes(raw), dtype="<f8")[0]), "float64"
+    if tag == 6:
+        b = bytes(raw)
+        return (b[3:] if b[:3] == b"\xef\xbb\xbf" else b).decode("utf-8"), None   # (TextDecoder drops a leading U+FEFF, encoding.js:9-17)
+    return bytes(raw), "bytes" if tag == 7 else tag
 
 
 class EngineError(RuntimeError):
@@ -411,6 +439,15 @@ def _bind(path):
         L.am355_text_position_calls.argtypes = [vp, vp]
         L.am355_text_position_limits.argtypes = [vp]
         for f in ("am355_text_position", "am355_rank_of_actor", "am355_text_position_calls", "am355_text_position_limits"):
+            getattr(L, f).restype = ctypes.c_int
+    if hasattr(L, "am355_map_update"):   # (libraries of earlier commits, loaded for an A/B run, end before these)
+        pvp, psz = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)
+        L.am355_map_locate.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_size_t, vp, vp, u32, pvp, pvp, ctypes.POINTER(u32)]
+        L.am355_map_update.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_size_t, vp, u32, vp, u32, vp, u32, vp, ctypes.c_size_t, ctypes.c_int64, vp, u32, pvp, psz]
+        L.am355_map_calls.argtypes = [vp, vp]
+        L.am355_map_locate_limits.argtypes = [vp]
+        L.am355_set_map_locate_thread.argtypes = [vp, ctypes.c_int]
+        for f in ("am355_map_locate", "am355_map_update", "am355_map_calls", "am355_map_locate_limits", "am355_set_map_locate_thread"):
             getattr(L, f).restype = ctypes.c_int
     L.am355_get_raw.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32)]
     L.am355_doc_changes.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_void_p)]
@@ -815,6 +852,103 @@ class Engine:
         out = (ctypes.c_uint32 * 3)()
         self._check(self._L.am355_list_locate_limits(out))
         return tuple(int(x) for x in out)
+
+    def map_locate(self, object_id, keys):
+        """Keys (str, or UTF-8 bytes) of a map or table resolved on the device to the records of their visible values (am355_map_locate):
+        (hits, recs). hits: MAP_HIT_DTYPE, one per key -- num values (0: absent) whose records are recs[first : first + num], in ascending
+        op id; flags: MAP_COUNTER / MAP_CHILD of the value the map shows (the last record). recs: IR_MAP_DTYPE, actors as ranks.
+        EngineError with code AM355_E_ARG: no such object / not a map object."""
+        ctr, actor, buf = self._object_id(object_id)
+        parts = [k.encode("utf-8") if isinstance(k, str) else bytes(k) for k in keys]
+        offs = np.zeros(len(parts) + 1, dtype=np.uint32)
+        np.cumsum([len(b) for b in parts], out=offs[1:])
+        blob = np.frombuffer(b"".join(parts) or b"\0", dtype=np.uint8)
+        ph, pr, nr = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint32()
+        self._check(self._L.am355_map_locate(self._h, ctr, ctypes.cast(buf, ctypes.c_void_p), len(actor), blob.ctypes.data, offs.ctypes.data, len(parts), ctypes.byref(ph),
+                                             ctypes.byref(pr), ctypes.byref(nr)))
+        hits, recs = np.zeros(len(parts), dtype=MAP_HIT_DTYPE), np.zeros(nr.value, dtype=IR_MAP_DTYPE)
+        if len(parts):
+            ctypes.memmove(hits.ctypes.data, ph, hits.nbytes)
+        if nr.value:
+            ctypes.memmove(recs.ctypes.data, pr, recs.nbytes)
+        return hits, recs
+
+    def map_get(self, object_id, keys):
+        """What the keys of a map hold: {key: {opId: value}} with every visible value under its op id, as `props` of the reference's patch
+        lists them ({} for an absent key). A primitive is {"value": v} (+ "datatype" for int / uint / float64 / counter / timestamp; a
+        counter's value is its total), a child object {"objectId": its id}. Built from the records of map_locate and the host's arena."""
+        keys = list(keys)
+        hits, recs = self.map_locate(object_id, keys)
+        a, o, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint32()
+        self._check(self._L.am355_get_raw(self._h, ctypes.byref(a), ctypes.byref(o), ctypes.byref(n)))
+        actors = {}
+        out = {}
+        for key, h in zip(keys, hits):
+            held = {}
+            for r in recs[int(h["first"]):int(h["first"]) + int(h["num"])]:
+                rank = int(r["id_actor"])
+                if rank not in actors:
+                    actors[rank] = self.actor_of_rank(rank)
+                op_id = f"{int(r['id_ctr'])}@{actors[rank]}"
+                flags, tl = int(r["flags"]), int(r["val_tl"])
+                if flags & MAP_CHILD:
+                    held[op_id] = {"objectId": op_id}
+                elif flags & MAP_COUNTER:
+                    held[op_id] = {"value": int(r["counter"]), "datatype": "counter"}
+                else:
+                    raw = ctypes.string_at(a.value + int(r["val_off"]), tl >> 4) if tl >> 4 else b""
+                    v, datatype = decode_ir_value(tl, raw)
+                    held[op_id] = {"value": v} if datatype is None else {"value": v, "datatype": datatype}
+            out[key] = held
+        return out
+
+    def map_update(self, object_id, ops, actor, time=0, message=""):
+        """One change on one map the engine holds (am355_map_update): what Automerge.change(doc, d => { d.a = 1; delete d.b;
+        d.n.increment(2) }) makes. ops: ("set", key, value) with value as for list_splice (see _list_values), ("del", key),
+        ("inc", key, delta); `actor`: the author's id in hex. Returns the binary change (b"" when no op came of it: deletions of absent
+        keys); apply_patch_json() then gives the patch. EngineError with code AM355_E_ARG and the reference's RangeError text for an empty
+        key, InvalidChanges with its text for an assignment onto a counter (RangeError) and for an increment of what is no counter
+        (TypeError). A set is always emitted: the engine holds no JS values to compare with."""
+        ctr, obj_actor, buf = self._object_id(object_id)
+        flat = np.zeros(len(ops), dtype=MAP_OP_DTYPE)
+        strings, values = bytearray(), []
+        for k, op in enumerate(ops):
+            kind = {"set": MOP_SET, "del": MOP_DELETE, "inc": MOP_INC}[op[0]]
+            key = op[1].encode("utf-8")
+            flat[k] = (kind, len(strings), len(key), len(values) if kind == MOP_SET else 0, int(op[2]) if kind == MOP_INC else 0)
+            strings.extend(key)
+            if kind == MOP_SET:
+                values.append(op[2])
+        vals, vblob, vlen = self._list_values(values)
+        vals["off"] += np.where(vals["tag"] == LV_UTF8, len(strings), 0).astype(np.uint32)   # (the values' strings stand behind the keys)
+        blob = np.frombuffer(bytes(strings) + (vblob.tobytes()[:vlen]) or b"\0", dtype=np.uint8)
+        author = np.frombuffer(bytes.fromhex(actor), dtype=np.uint8)
+        raw = message.encode("utf-8")
+        msg = np.frombuffer(raw or b"\0", dtype=np.uint8)
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._L.am355_map_update(self._h, ctr, ctypes.cast(buf, ctypes.c_void_p), len(obj_actor), flat.ctypes.data if len(ops) else None, len(ops), blob.ctypes.data,
+                                             len(strings) + vlen, vals.ctypes.data if vals.size else None, len(values), author.ctypes.data if author.size else None,
+                                             author.size, int(time), msg.ctypes.data, len(raw), ctypes.byref(p), ctypes.byref(n)))
+        if n.value:
+            self._n_changes = int(self.stats().n_changes)
+        return ctypes.string_at(p, n.value) if n.value else b""
+
+    def map_calls(self):
+        """(map_update calls served, refused, kernel launches of the locate half of map_locate and map_update)."""
+        out = (ctypes.c_uint64 * 3)()
+        self._check(self._L.am355_map_calls(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def map_locate_limits(self):
+        """(records an object is searched through by the last round alone, keys read from pinned memory, hits / records written straight to
+        pinned memory, G: the first gather has room for 2 n + G records)."""
+        out = (ctypes.c_uint32 * 4)()
+        self._check(self._L.am355_map_locate_limits(out))
+        return tuple(int(x) for x in out)
+
+    def set_map_locate_thread(self, on):
+        """on: map_locate searches with one thread per key instead of one wavefront (measurement switch; same answers)."""
+        self._check(self._L.am355_set_map_locate_thread(self._h, 1 if on else 0))
 
     def rank_of_actor(self, actor):
         """The rank of an actor (hex id) in the state's actor table (am355_rank_of_actor), None when the state does not know the actor.

@@ -1289,6 +1289,147 @@ static napi_value list_edit(napi_env env, napi_callback_info info, bool is_set) 
 static napi_value js_list_splice(napi_env env, napi_callback_info info) { return list_edit(env, info, false); }
 static napi_value js_list_set(napi_env env, napi_callback_info info) { return list_edit(env, info, true); }
 
+/* A primitive value of a map record as the patch carries it: { value } (+ datatype for int / uint / float64 / counter / timestamp; type/length
+ * word as in the valLen column, columnar.js:300-329). false: a type this binding does not read (bytes, unknown). */
+static bool map_value_object(napi_env env, const am355_ir_map *rec, const uint8_t *arena, uint64_t arena_len, napi_value *out) {
+  napi_value v;
+  const char *datatype = NULL;
+  const uint32_t tag = rec->val_tl & 15u, len = rec->val_tl >> 4;
+  if (napi_create_object(env, out) != napi_ok) return false;
+  if (rec->flags & AM355_MAP_COUNTER) {
+    if (napi_create_double(env, (double)rec->counter, &v) != napi_ok) return false;
+    datatype = "counter";
+  } else if (tag == 0) { if (napi_get_null(env, &v) != napi_ok) return false; }
+  else if (tag == 1 || tag == 2) { if (napi_get_boolean(env, tag == 2, &v) != napi_ok) return false; }
+  else {
+    if ((uint64_t)rec->val_off + len > arena_len) return false;
+    const uint8_t *p = arena + rec->val_off;
+    if (tag == 3 || tag == 4 || tag == 8 || tag == 9) {
+      uint64_t u = 0;
+      int shift = 0;
+      if (len == 0 || len > 10) return false;
+      for (uint32_t k = 0; k < len; k++, shift += 7) u |= (uint64_t)(p[k] & 0x7f) << shift;
+      if (tag != 3 && shift < 64 && (p[len - 1] & 0x40)) u |= ~(uint64_t)0 << shift;
+      if (napi_create_double(env, tag == 3 ? (double)u : (double)(int64_t)u, &v) != napi_ok) return false;
+      datatype = tag == 3 ? "uint" : tag == 4 ? "int" : tag == 8 ? "counter" : "timestamp";
+    } else if (tag == 5 && len == 8) {
+      double d;
+      memcpy(&d, p, 8);
+      if (napi_create_double(env, d, &v) != napi_ok) return false;
+      datatype = "float64";
+    } else if (tag == 6) {
+      const size_t skip = len >= 3 && p[0] == 0xef && p[1] == 0xbb && p[2] == 0xbf ? 3 : 0;   /* (TextDecoder drops a leading U+FEFF) */
+      if (napi_create_string_utf8(env, (const char *)p + skip, len - skip, &v) != napi_ok) return false;
+    } else return false;
+  }
+  if (napi_set_named_property(env, *out, "value", v) != napi_ok) return false;
+  if (datatype) {
+    if (napi_create_string_utf8(env, datatype, NAPI_AUTO_LENGTH, &v) != napi_ok || napi_set_named_property(env, *out, "datatype", v) != napi_ok) return false;
+  }
+  return true;
+}
+
+/* mapLocate(ctx, ctr, Uint8Array actor, Uint8Array keys, Uint32Array keyOff) -> [{ counter, child, ids: [opId, ...], values: [value, ...] }] per key =
+ * am355_map_locate: the op ids of the key's visible values in ascending order and what they hold ({ value, datatype } / { objectId }); counter /
+ * child: of the value the map shows (the last one). _root: ctr 0 and an empty actor. */
+static napi_value js_map_locate(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5], out, v;
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  double ctr = -1;
+  const uint8_t *actor = NULL, *keys = NULL;
+  size_t actor_len = 0, keys_len = 0, n_off = 0;
+  uint32_t *off = NULL;
+  if (argc < 5 || napi_get_value_double(env, argv[1], &ctr) != napi_ok || !get_u8_array(env, argv[2], &actor, &actor_len) || !get_u8_array(env, argv[3], &keys, &keys_len) ||
+      !get_u32_array(env, argv[4], &off, &n_off) || ctr < 0 || ctr > 4294967295.0 || n_off < 1 || n_off - 1 > 0xffffffffu || off[0] != 0 || off[n_off - 1] != keys_len) {
+    napi_throw_type_error(env, NULL, "mapLocate takes a counter, the actor's bytes, the keys' bytes and their offsets");
+    return NULL;
+  }
+  for (size_t k = 0; k + 1 < n_off; k++)
+    if (off[k] > off[k + 1]) { napi_throw_type_error(env, NULL, "mapLocate: key offsets out of order"); return NULL; }
+  const am355_map_hit *hits = NULL;
+  const am355_ir_map *recs = NULL;
+  uint32_t n_recs = 0;
+  const uint32_t n = (uint32_t)(n_off - 1);
+  int rc = am355_map_locate(ctx, (uint64_t)ctr, actor, actor_len, keys, off, n, &hits, &recs, &n_recs);
+  if (rc) return throw_engine(env, ctx, rc);
+  const uint8_t *arena = NULL;
+  const uint64_t *offsets = NULL;
+  uint32_t n_changes = 0;
+  rc = am355_get_raw(ctx, &arena, &offsets, &n_changes);
+  if (rc) return throw_engine(env, ctx, rc);
+  const uint64_t arena_len = offsets ? offsets[n_changes] : 0;
+  NAPI_CALL(env, napi_create_array_with_length(env, n, &out));
+  for (uint32_t k = 0; k < n; k++) {
+    napi_value o, ids, values;
+    NAPI_CALL(env, napi_create_object(env, &o));
+    NAPI_CALL(env, napi_get_boolean(env, (hits[k].flags & AM355_MAP_COUNTER) != 0, &v));
+    NAPI_CALL(env, napi_set_named_property(env, o, "counter", v));
+    NAPI_CALL(env, napi_get_boolean(env, (hits[k].flags & AM355_MAP_CHILD) != 0, &v));
+    NAPI_CALL(env, napi_set_named_property(env, o, "child", v));
+    NAPI_CALL(env, napi_create_array_with_length(env, hits[k].num, &ids));
+    NAPI_CALL(env, napi_create_array_with_length(env, hits[k].num, &values));
+    for (uint32_t q = 0; q < hits[k].num; q++) {
+      const am355_ir_map *rec = &recs[hits[k].first + q];   /* (inside the array: am355_map_locate checks every hit) */
+      napi_value id;
+      if (!id_string(env, ctx, rec->id_ctr, rec->id_actor, &id)) { napi_throw_error(env, NULL, "mapLocate: a record names an actor outside the table"); return NULL; }
+      NAPI_CALL(env, napi_set_element(env, ids, q, id));
+      if (rec->flags & AM355_MAP_CHILD) {
+        NAPI_CALL(env, napi_create_object(env, &v));
+        NAPI_CALL(env, napi_set_named_property(env, v, "objectId", id));
+      } else if (!map_value_object(env, rec, arena, arena_len, &v)) { napi_throw_error(env, NULL, "mapLocate: a value this binding does not read (bytes, or outside the arena)"); return NULL; }
+      NAPI_CALL(env, napi_set_element(env, values, q, v));
+    }
+    NAPI_CALL(env, napi_set_named_property(env, o, "ids", ids));
+    NAPI_CALL(env, napi_set_named_property(env, o, "values", values));
+    NAPI_CALL(env, napi_set_element(env, out, k, o));
+  }
+  return out;
+}
+
+/* mapUpdate(ctx, ctr, Uint8Array actor, Uint32Array ops, Uint8Array strings, Uint32Array values, Uint8Array author, time, Uint8Array message)
+ * -> Uint8Array (the binary change; empty: no op came of it) = am355_map_update. ops: six words per op -- kind, key offset, key length, value
+ * index, delta low word, delta high word (the layout of am355_map_op); values: six words per value (js/local_change.js flattenValues), their
+ * strings in `strings` beside the keys */
+static napi_value js_map_update(napi_env env, napi_callback_info info) {
+  size_t argc = 9;
+  napi_value argv[9];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  am355_ctx *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  double ctr = -1, time = 0;
+  const uint8_t *actor = NULL, *strings = NULL, *author = NULL, *message = NULL;
+  size_t actor_len = 0, strings_len = 0, author_len = 0, message_len = 0, n_op_words = 0, n_words = 0;
+  uint32_t *op_words = NULL, *words = NULL;
+  const size_t vw = sizeof(am355_local_value) / 4, ow = sizeof(am355_map_op) / 4;
+  if (argc < 9 || napi_get_value_double(env, argv[1], &ctr) != napi_ok || !get_u8_array(env, argv[2], &actor, &actor_len) || !get_u32_array(env, argv[3], &op_words, &n_op_words) ||
+      !get_u8_array(env, argv[4], &strings, &strings_len) || !get_u32_array(env, argv[5], &words, &n_words) || !get_u8_array(env, argv[6], &author, &author_len) ||
+      napi_get_value_double(env, argv[7], &time) != napi_ok || !get_u8_array(env, argv[8], &message, &message_len) || ctr < 0 || ctr > 4294967295.0 || n_op_words % ow ||
+      n_op_words / ow > 0xffffffffu || n_words % vw || n_words / vw > 0xffffffffu || strings_len > 0xffffffffu || message_len > 0xffffffffu || time != (double)(int64_t)time) {
+    napi_throw_type_error(env, NULL, "mapUpdate takes (ctx, counter, actor bytes, ops, strings, values, author bytes, time, message bytes)");
+    return NULL;
+  }
+  /* (copies: both structs hold a 64-bit word) */
+  am355_map_op *ops = (am355_map_op *)malloc(n_op_words ? n_op_words * 4 : 1);
+  am355_local_value *values = (am355_local_value *)malloc(n_words ? n_words * 4 : 1);
+  if (!ops || !values) { free(ops); free(values); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  if (n_op_words) memcpy(ops, op_words, n_op_words * 4);
+  if (n_words) memcpy(values, words, n_words * 4);
+  const uint8_t *bytes = NULL;
+  size_t len = 0;
+  int rc = am355_map_update(ctx, (uint64_t)ctr, actor, actor_len, ops, (uint32_t)(n_op_words / ow), strings, (uint32_t)strings_len, values, (uint32_t)(n_words / vw), author,
+                            author_len, (int64_t)time, message, (uint32_t)message_len, &bytes, &len);
+  free(ops);
+  free(values);
+  if (rc) return throw_engine(env, ctx, rc);
+  napi_value ab = copy_to_arraybuffer(env, bytes, len), change;
+  if (!ab) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &change));
+  return change;
+}
+
 /* rankOfActor(ctx, Uint8Array actor) -> the actor's rank in the engine's table, -1 when the state does not know the actor
  * (am355_rank_of_actor). Ranks are renumbered when a new actor arrives: asked per call. */
 static napi_value js_rank_of_actor(napi_env env, napi_callback_info info) {
@@ -1381,6 +1522,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"listLocate", NULL, js_list_locate, NULL, NULL, NULL, napi_enumerable, NULL},
       {"listSplice", NULL, js_list_splice, NULL, NULL, NULL, napi_enumerable, NULL},
       {"listSet", NULL, js_list_set, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"mapLocate", NULL, js_map_locate, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"mapUpdate", NULL, js_map_update, NULL, NULL, NULL, napi_enumerable, NULL},
       {"textPositions", NULL, js_text_positions, NULL, NULL, NULL, napi_enumerable, NULL},
       {"rankOfActor", NULL, js_rank_of_actor, NULL, NULL, NULL, napi_enumerable, NULL},
       {"bloomBuild", NULL, js_bloom_build, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -11,6 +11,8 @@
 //   load / save / getAllChanges after load                         (SURVEY.md a21, 8f-1, 8f-3)
 //   applyLocalChange(state, request) -> [state', patch, change]    (backend/backend.js:54-91) for the states applyChanges is served on:
 //                                                                  the change is built on the device (local_change.js, am355_apply_local_change)
+//   updateMap(state, objectId, ops, {actor, time, message}) / getMapValues(state, objectId, keys) / locateMap(state, objectId, keys)
+//     ADDITIONS: a map edited by key -- d.key = v, delete d.key, d.key.increment(n) -- and what its keys hold (am355_map_update / _locate; see below)
 //   positionsOfText(state, objectId, elemIds)   ADDITION: where elements of a Text stand now, deleted ones included (am355_text_position; see below)
 //   spliceList(state, objectId, start, deletions, values, {actor, time, message}) / setListItem(state, objectId, index, value, options) /
 //   locateList(state, objectId, first, n)   ADDITIONS: a plain list edited by position (am355_list_splice / _set / _locate; see below)
@@ -140,7 +142,7 @@ function contextOf(gen) {
   if (e) { e.used = ++tick; ctx = e.ctx }
   return e || null
 }
-const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, gpuChangesAdded: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0, gpuText: 0, textFallbacks: 0, gpuSplice: 0, spliceFallbacks: 0, gpuListSplice: 0, listSpliceFallbacks: 0, gpuPosition: 0, positionFallbacks: 0 }   // (diagnostics: which path served the calls)
+const counters = { gpuLoadChanges: 0, gpuLoad: 0, gpuSave: 0, gpuHistory: 0, gpuApplyChanges: 0, gpuApplyLocalChange: 0, gpuChangesAdded: 0, localFallbacks: 0, saveReplays: 0, fallbackToJs: 0, hydrations: 0, gpuText: 0, textFallbacks: 0, gpuSplice: 0, spliceFallbacks: 0, gpuListSplice: 0, listSpliceFallbacks: 0, gpuPosition: 0, positionFallbacks: 0, gpuMap: 0, mapFallbacks: 0, gpuMapLocate: 0, mapLocateFallbacks: 0 }   // (diagnostics: which path served the calls)
 
 function isFrozenCheck(backend) {
   // reference util.js:1-10
@@ -1230,21 +1232,22 @@ function gpuListEdit(backend, flat, call) {
   try {
     binaryChange = call(flat)
   } catch (e) {
-    // out of bounds, no such list, a counter: decided before the state is touched (am355.h); anything else may have dropped it
-    if (e.am355Code !== AM355_E_ARG && !(e.am355Code === AM355_E_INVALID && (e.message === COUNTER_IN_TEXT || e.message === COUNTER_ASSIGN))) at.entry.generation = 0
+    // out of bounds, no such list or map, a bad key, a counter rule: decided before the state is touched (am355.h); anything else may have dropped it
+    if (e.am355Code !== AM355_E_ARG && !(e.am355Code === AM355_E_INVALID && (e.message === COUNTER_IN_TEXT || e.message === COUNTER_ASSIGN || e.message === NOT_A_COUNTER))) at.entry.generation = 0
     throw e
   }
   return positionalResult(backend, at, knownBefore, binaryChange)
 }
-function listOnEngine(backend, m, flat, call) {
-  if (!engineServesText(backend, m)) return null
+// (counter / serves: the map calls count in their own word and are served for the empty document too, see updateMap)
+function listOnEngine(backend, m, flat, call, counter = 'gpuListSplice', serves = engineServesText) {
+  if (!serves(backend, m)) return null
   try {
     const result = gpuListEdit(backend, flat, call)
-    if (result) counters.gpuListSplice++
+    if (result) counters[counter]++
     return result
   } catch (e) {
     if (e.am355Code === AM355_E_ARG) throw new RangeError(e.message)
-    if (e.am355Code === AM355_E_INVALID && e.message === COUNTER_IN_TEXT) throw new TypeError(e.message)
+    if (e.am355Code === AM355_E_INVALID && (e.message === COUNTER_IN_TEXT || e.message === NOT_A_COUNTER)) throw new TypeError(e.message)
     if (e.am355Code === AM355_E_INVALID && e.message === COUNTER_ASSIGN) throw new RangeError(e.message)
     if (e.am355Code !== AM355_E_INVALID && e.am355Code !== AM355_E_UNSUPPORTED) throw e
     return null
@@ -1307,6 +1310,132 @@ function locateList(backend, objectId, first, n) {
   const elems = listElementsFromPatch(getPatch(backend), objectId)
   if (first + n > elems.length) throw new RangeError(`elements [${first}, ${first} + ${n}) are out of bounds for a list of length ${elems.length}`)
   return { length: elems.length, runs: listRunsOf(elems.slice(first, first + n)) }
+}
+
+// ---- a map edited by key: updateMap / getMapValues / locateMap (additions; nothing of backend/index.js:1-8 changes) ----
+// updateMap(backend, objectId, ops, { actor, time, message }) -> [backend', patch, binaryChange]: ONE change on ONE map (or '_root'), what
+// Automerge.change(doc, d => { d.a = 1; delete d.b; d.n.increment(2) }) makes, for a host WITHOUT a frontend document, under the
+// conditions of spliceList and with its ownership of actor and order. ops: { action: 'set', key, value } (a value as for spliceList),
+// { action: 'del', key }, { action: 'inc', key, value: delta }. The pred of each op names every visible value of its key
+// (context.js:576-586 getPred); a deletion of a key without a value makes no op, and a call that ends without one returns
+// [backend, null, null]. On a Table only { action: 'del', key: rowId } is served. A `set` ALWAYS makes its op (see setListItem).
+// A key named twice in one call is a RangeError on both paths (the frontend would name the first op as the second's pred: not built).
+// Counters: gpuMap / mapFallbacks count updateMap calls by the path that served them, gpuMapLocate / mapLocateFallbacks the reads.
+// Served by the engine (am355_map_update: every key located in one query on the device); otherwise, and on AM355_E_UNSUPPORTED, the JS
+// path: the `props` of the whole-document patch folded into preds and the shown value, the request built by context.js's rules
+// (:325-346, :351-362, :531-540, :546-573), this module's own applyLocalChange. An empty key assigned: the RangeError of context.js:294;
+// an assignment onto a key that shows a Counter: the RangeError of :334; an increment of a key that shows none: the TypeError of :550 --
+// on both paths.
+// locateMap(backend, objectId, keys) -> [{ counter, child, ids: [opId, ...], values: [...] }] per key, ids ascending (am355_map_locate, or
+// the same fold); getMapValues(backend, objectId, keys) -> { key: { opId: value } } with value = { value, datatype? } or { objectId }.
+const EMPTY_KEY = 'The key of a map entry must not be an empty string', NOT_A_COUNTER = 'Only counter values can be incremented'
+const KEY_TWICE = 'a key named twice in one call (the second op\'s pred would be the first op: not built)'
+const ROOT_ID = ['_root', '0', '']   // (the shape of an OBJECT_ID match)
+const MOP = { set: 1, del: 2, inc: 3 }
+const lamport = id => { const at = id.indexOf('@'); return [Number(id.slice(0, at)), id.slice(at + 1)] }
+const lamportAscending = (a, b) => { const x = lamport(a), y = lamport(b); return x[0] - y[0] || (x[1] < y[1] ? -1 : x[1] > y[1] ? 1 : 0) }
+function mapFromPatch(patch, objectId) {
+  let found = null
+  const walk = diff => {
+    if (found) return
+    if (diff.objectId === objectId) { found = diff; return }
+    if (diff.props) for (const key of Object.keys(diff.props)) for (const id of Object.keys(diff.props[key])) if (diff.props[key][id].objectId) walk(diff.props[key][id])
+    if (diff.edits) for (const e of diff.edits) if (e.value && e.value.objectId) walk(e.value)
+  }
+  walk(patch.diffs)
+  if (!found) throw new RangeError(`no such object: ${objectId}`)
+  if (found.type !== 'map' && found.type !== 'table') throw new RangeError('not a map object')
+  return found
+}
+function locateInPatch(found, key) {
+  const held = (found.props && Object.prototype.hasOwnProperty.call(found.props, key) && found.props[key]) || {}
+  const ids = Object.keys(held).sort(lamportAscending)
+  const values = ids.map(id => (held[id].objectId ? { objectId: held[id].objectId } : held[id].datatype ? { value: held[id].value, datatype: held[id].datatype } : { value: held[id].value }))
+  const shown = ids.length ? held[ids[ids.length - 1]] : null
+  return { counter: !!shown && shown.datatype === 'counter', child: !!shown && !!shown.objectId, ids, values }
+}
+// the engine serves a map call: a state it holds, or (for _root) the empty document, which a reset context is
+const engineServesMap = (backend, m) => engineServesText(backend, m) || (!JS_ONLY && spliceOnEngine && m === ROOT_ID && isEmptyRefState(backend))
+const EMPTY_WHOLE = { clock: {}, deps: [], maxOp: 0, pendingChanges: 0, diffs: { objectId: '_root', type: 'map', props: {} } }
+const wholePatch = backend => (isEmptyRefState(backend) ? EMPTY_WHOLE : getPatch(backend))
+function mapArgs(objectId) {
+  const m = objectId === '_root' ? ROOT_ID : typeof objectId === 'string' ? OBJECT_ID.exec(objectId) : null
+  if (!m) throw new RangeError(`no such object: ${objectId}`)
+  return m
+}
+const keyBytes = keys => {
+  const parts = keys.map(k => Buffer.from(k, 'utf8')), off = new Uint32Array(parts.length + 1)
+  parts.forEach((b, k) => { off[k + 1] = off[k] + b.length })
+  return [new Uint8Array(Buffer.concat(parts)), off]
+}
+function locateMap(backend, objectId, keys) {
+  isFrozenCheck(backend)
+  if (!Array.isArray(keys) || !keys.every(k => typeof k === 'string')) throw new TypeError('locateMap takes an array of keys')
+  const m = mapArgs(objectId)
+  if (engineServesText(backend, m)) {   // (an empty document holds no key: the fold below says so without a context)
+    try {
+      const [bytes, off] = keyBytes(keys)
+      const located = addon.mapLocate(ctx, Number(m[1]), hexBytes(m[2]), bytes, off)
+      counters.gpuMapLocate++
+      return located
+    } catch (e) {
+      if (e.am355Code === AM355_E_ARG) throw new RangeError(e.message)
+      if (e.am355Code === undefined) throw e
+    }
+  }
+  counters.mapLocateFallbacks++
+  const found = mapFromPatch(wholePatch(backend), objectId)
+  return keys.map(key => locateInPatch(found, key))
+}
+function getMapValues(backend, objectId, keys) {
+  const out = {}
+  locateMap(backend, objectId, keys).forEach((hit, k) => {
+    out[keys[k]] = {}
+    hit.ids.forEach((id, q) => { out[keys[k]][id] = hit.values[q] })
+  })
+  return out
+}
+function updateMap(backend, objectId, ops, options = {}) {
+  isFrozenCheck(backend)
+  if (!Array.isArray(ops) || !ops.every(op => op && MOP[op.action] && typeof op.key === 'string')) throw new TypeError('updateMap takes ops { action: set | del | inc, key, value }')
+  const list = ops.map(op => (op.action === 'set' ? listValue(op.value) : null))
+  if (!ops.every(op => op.action !== 'inc' || Number.isSafeInteger(op.value))) throw new TypeError('an increment is an integer')
+  const { actor, time, message } = listCallArgs('updateMap', objectId, options, [])
+  const m = mapArgs(objectId)
+  if (new Set(ops.map(op => op.key)).size !== ops.length) throw new RangeError(KEY_TWICE)
+  const flat = flattenValues(list.filter(v => v))
+  const served = listOnEngine(backend, m, flat, values => {
+    const [keys, off] = keyBytes(ops.map(op => op.key))
+    const strings = new Uint8Array(keys.length + values.strings.length), vals = Uint32Array.from(values.values), words = new Uint32Array(6 * ops.length)
+    strings.set(keys)
+    strings.set(values.strings, keys.length)
+    for (let k = 0; k < vals.length; k += 6) if (vals[k] === 6) vals[k + 1] += keys.length   // (AM355_LV_UTF8: the values' strings stand behind the keys)
+    let nValues = 0
+    ops.forEach((op, k) => {
+      const delta = op.action === 'inc' ? BigInt.asUintN(64, BigInt(op.value)) : 0n
+      words.set([MOP[op.action], off[k], off[k + 1] - off[k], op.action === 'set' ? nValues++ : 0, Number(delta & 0xffffffffn), Number(delta >> 32n)], 6 * k)
+    })
+    return addon.mapUpdate(ctx, Number(m[1]), hexBytes(m[2]), words, strings, vals, hexBytes(actor), time, new Uint8Array(Buffer.from(message, 'utf8')))
+  }, 'gpuMap', engineServesMap)
+  if (served) return served
+  counters.mapFallbacks++
+  const whole = wholePatch(backend), found = mapFromPatch(whole, objectId), out = []
+  ops.forEach((op, k) => {
+    const hit = locateInPatch(found, op.key), pred = hit.ids.slice().reverse()   // (the conflicts object lists the greatest op id first, apply_patch.js:61)
+    if (found.type === 'table' && (op.action !== 'del' || pred.length > 1)) throw new RangeError('on a table object only the deletion of a row is served')
+    if (op.action === 'set') {
+      if (op.key === '') throw new RangeError(EMPTY_KEY)
+      if (hit.counter) throw new RangeError(COUNTER_ASSIGN)
+      const o = { action: 'set', obj: objectId, key: op.key, insert: false, value: list[k].value, pred }
+      if (list[k].datatype) o.datatype = list[k].datatype
+      out.push(o)
+    } else if (op.action === 'inc') {
+      if (!hit.counter) throw new TypeError(NOT_A_COUNTER)
+      out.push({ action: 'inc', obj: objectId, key: op.key, value: op.value, insert: false, pred })
+    } else if (pred.length) out.push({ action: 'del', obj: objectId, key: op.key, insert: false, pred })
+  })
+  if (out.length === 0) return [backend, null, null]
+  return applyLocalChange(backend, { actor, seq: (whole.clock[actor] || 0) + 1, startOp: whole.maxOp + 1, deps: whole.deps.slice(), time, message, ops: out })
 }
 
 // ---- elemIds of a Text resolved to positions: positionsOfText (an addition; nothing of backend/index.js:1-8 changes) ----
@@ -1426,6 +1555,8 @@ module.exports = {
   spliceText, locateText,
   // additions: a plain list edited by position / positions resolved to ids and every pred, on the device (see above)
   spliceList, setListItem, locateList,
+  // additions: a map edited by key / keys resolved to the op ids and values they hold, on the device (see above)
+  updateMap, getMapValues, locateMap,
   // addition: elemIds of a Text resolved to positions, deleted elements included, on the device (see above)
   positionsOfText,
   // sync protocol: the reference's own backend/sync.js bound to this module (boundSync above)

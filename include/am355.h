@@ -700,7 +700,8 @@ int am355_actor_of_rank(const am355_ctx *ctx, uint32_t rank, const uint8_t **byt
  * launches of the locate half of the three calls. am355_list_locate_limits: out[0] = elements one workgroup of the locate kernel takes,
  * out[1] = elements up to which the scan is one workgroup, out[2] = runs, and preds, written straight into pinned memory (the ones behind
  * go to device memory and down in one copy each).
- * Not built: am355_text_position for lists, increments, a locate without the rebuild of stale edit tables.
+ * Not built: am355_text_position for lists, increments of a counter inside a list (a map's: am355_map_update), a locate without the
+ * rebuild of stale edit tables.
  */
 typedef struct { uint32_t elem_ctr, elem_actor, count, flags, pred_first, pred_num; } am355_list_run;   /* flags: AM355_RUN_COUNTER; actors: ranks */
 typedef struct { uint32_t actor, ctr; } am355_list_pred;                                               /* actor: a rank */
@@ -716,6 +717,78 @@ int am355_list_set(am355_ctx *ctx, uint64_t obj_ctr, const uint8_t *obj_actor, s
                    const uint8_t **change, size_t *len);
 int am355_list_splice_calls(const am355_ctx *ctx, uint64_t out[3]);   /* served | refused | device launches of the locate half */
 int am355_list_locate_limits(uint32_t out[3]);                        /* the sizes at which the kernels switch path, for the tests */
+
+/*
+ * A MAP edited by KEY (csrc/am355_map_locate.hip): doc.title = 'x', delete doc.draft, doc.votes.increment() for a host without a frontend
+ * document, and "what does this key hold". A change request names the op ids of EVERY visible value of the key it touches (`pred`,
+ * frontend/context.js:576-586 getPred); they stand in the map table, which is sorted by (object, key in UTF-16 code unit order, op id).
+ * am355_map_locate resolves n keys of the map or table obj_ctr @ obj_actor (_root: obj_ctr == 0 && actor_len == 0) in one query: key i is
+ * the UTF-8 bytes keys[key_off[i] .. key_off[i + 1]). (*hits)[i] = {first, num, flags, pad}: the key holds num visible values (0: the key
+ * is absent), whose am355_ir_map records -- copied as they are: value, counter total, flags, op id with the actor as a RANK -- are
+ * (*recs)[first .. first + num), in ascending op id (counter, then actor bytes): the order am355_local_op wants for preds. flags =
+ * AM355_MAP_COUNTER / AM355_MAP_CHILD of the value the map SHOWS, which is the last record (the greatest op id,
+ * frontend/apply_patch.js:57-79; AM355_MAP_COUNTER also for a counter nobody has incremented yet, whose record carries only the type of
+ * its `set` and no total). A record's {id_ctr, id_actor} is the pred; for a child object it is also the child's objectId.
+ * *n_recs = records gathered; a key asked for twice has its records twice (at most records of the object + n in all: beyond that
+ * AM355_E_ARG). *hits / *recs are pinned memory owned by the context, valid until the next call on ctx. n == 0 and an object without
+ * records launch nothing. On the device one wavefront searches per key, 64 pivots a round; before a record is copied the search has
+ * verified itself (the keys on both sides of the run differ in the right direction, the ids inside it ascend, every key read lies in
+ * the arena, no record is an AM355_MAP_EMPTY one): a miss is AM355_E_DEVICE, nothing is read or written out of range.
+ * It reads only: the state, what serves the next am355_apply_changes, the host copies of the tables and the flags that describe them
+ * stay as they were, and -- unlike the calls on a Text or a list -- edit tables that in-place merges left stale are NOT rebuilt: the
+ * object and map tables are current behind every such merge. Served for map (type 0) and table (type 6) objects on the contexts
+ * am355_object_text serves; AM355_E_STATE, sharded AM355_E_UNSUPPORTED, AM355_E_ARG "no such object: ..." as there; any other object:
+ * AM355_E_ARG "not a map object".
+ *
+ * am355_map_update: ONE change on ONE map -- what Automerge.change(doc, d => { d.a = 1; delete d.b; d.n.increment(2) }) makes. All keys of
+ * the call are located in one query; seq, startOp, deps and the application (small path, bulk path, patch, envelope) are those of
+ * am355_text_splice. Keys are ranges of `strings`, as the UTF-8 values are; op i:
+ *   AM355_MOP_SET     values[value] assigned (context.js:325-346, :289-309): one `set`, insert: false, pred = every id of the key. Value
+ *                     classes as for am355_list_splice. An empty key: AM355_E_ARG "The key of a map entry must not be an empty string";
+ *                     a key that shows a Counter: AM355_E_INVALID "Cannot overwrite a Counter object; use .increment() or .decrement()
+ *                     to change its value.". THE OP IS ALWAYS EMITTED: the reference skips an assignment of the value the key already
+ *                     shows without a conflict; the engine holds no JS values, a caller that wants that economy compares first.
+ *   AM355_MOP_DELETE  (:351-362) a `del` with every id as pred; a key without a value emits no op. On a TABLE object (:531-540
+ *                     deleteTableRow) this is the only kind served (one pred); anything else there: AM355_E_UNSUPPORTED.
+ *   AM355_MOP_INC     (:546-573) an `inc` of `delta` with every id as pred; a key that is absent or shows no Counter: AM355_E_INVALID
+ *                     "Only counter values can be incremented".
+ * A context that holds NO state (a fresh or reset one -- and, as for am355_apply_local_change, one whose state a refused apply dropped)
+ * is Backend.init(): _root without a key, seq 1, startOp 1, no deps; any other object is "no such object" there.
+ * The ops are judged in their order and the first exception is the call's. A call that ends without an op (deletions of absent keys, no
+ * ops) returns AM355_OK with *len = 0 and applies nothing. A key named twice in one call: AM355_E_ARG (the frontend would name the first
+ * op as the second's pred: not built). Assigning objects is not served: `child` ops are not in the flat request form. All of this, and
+ * the state errors of am355_list_splice (queued changes: AM355_E_UNSUPPORTED), is decided before the state is touched.
+ * am355_map_calls: out[0] am355_map_update calls served, out[1] refused (whatever the code), out[2] kernel launches of the locate half of
+ * both calls (the object lookup included; the library scan counts as one). am355_map_locate_limits: out[0] = records up to which an
+ * object is searched by the last round alone (more: narrowing rounds first), out[1] = keys read from pinned memory (more: one copy up),
+ * out[2] = hits, and records, written straight into pinned memory (the ones behind go to device memory and down in one copy each),
+ * out[3] = G: the result arrays of the first gather have room for 2 n + G records (they are not sized for the bound above: one key asked
+ * of a map of a million records would pin 40 MB); a call whose keys hold more -- many conflicting values per key -- learns the count in
+ * its one wait, gathers a second time into arrays of that size and waits once more. A key of more than 256 bytes is compared where it
+ * lies, not from LDS: a call that names one copies its keys up instead of reading them from pinned memory.
+ * am355_set_map_locate_thread: on != 0: one thread per key and two binary searches instead of the wavefront -- the same answers; a
+ * measurement switch (profiles/map_update_timings.txt), off by default.
+ * Not built: assigning objects, a key named twice, am355_map_update across several objects in one change.
+ */
+enum { AM355_MOP_SET = 1, AM355_MOP_DELETE = 2, AM355_MOP_INC = 3 };       /* am355_map_op.kind */
+typedef struct { uint32_t first, num, flags, pad; } am355_map_hit;         /* flags: AM355_MAP_COUNTER / AM355_MAP_CHILD of the shown value */
+typedef struct {
+  uint32_t kind;                   /* AM355_MOP_* */
+  uint32_t key_off, key_len;       /* the key: a range of `strings` */
+  uint32_t value;                  /* AM355_MOP_SET: index into `values` */
+  int64_t delta;                   /* AM355_MOP_INC */
+} am355_map_op;
+int am355_map_locate(am355_ctx *ctx, uint64_t obj_ctr, const uint8_t *obj_actor, size_t actor_len,
+                     const uint8_t *keys, const uint32_t *key_off, uint32_t n,   /* key i = keys[key_off[i] .. key_off[i+1]) */
+                     const am355_map_hit **hits, const am355_ir_map **recs, uint32_t *n_recs);
+int am355_map_update(am355_ctx *ctx, uint64_t obj_ctr, const uint8_t *obj_actor, size_t actor_len,
+                     const am355_map_op *ops, uint32_t n_ops, const uint8_t *strings, uint32_t strings_len,
+                     const am355_local_value *values, uint32_t n_values,
+                     const uint8_t *author, size_t author_len, int64_t time, const uint8_t *message, uint32_t message_len,
+                     const uint8_t **change, size_t *len);
+int am355_map_calls(const am355_ctx *ctx, uint64_t out[3]);          /* updates served | refused | device launches of the locate half */
+int am355_map_locate_limits(uint32_t out[4]);                        /* the sizes at which the kernels switch path, for the tests */
+int am355_set_map_locate_thread(am355_ctx *ctx, int on);
 
 /*
  * ElemIds of a Text resolved to POSITIONS (csrc/am355_position.hip): the inverse of am355_text_locate, and what keeps a caret, a
